@@ -2,7 +2,13 @@
 """Benchmark of the DiffuScene DDPM hot path on MI355X (contract: see the task brief / DESIGN.md section 6).
 
     python bench.py --gpus N --steps K --warmup W [--config living80|bedroom21|text|complete|arrange]
-                    [--mode both|sample|train] [--no-cpu-baseline] [--no-full-loop]
+                    [--mode both|sample|train] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-full-loop]]
+
+A plain run sets up, warms up, times ONE region of exactly K steps and prints the result line (`ms_per_step` = that region / K).
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (dump_outputs).  `--full` adds
+everything else: the headline as the median of three regions of K steps, the sampling and training rates apart, one whole
+1000-step loop, the dominant kernel's roofline, the CPU baseline and, on the default single-GPU run, the other configurations,
+the exact-f32 line and the public entry points (each in a child process).
 
 Workloads = the five BASELINE.json configs (`--config`, default = the headline one):
   living80   uncond living/dining rooms scaled to N=80, B=256 scenes per GPU, C=65            (BASELINE configs[2], metric)
@@ -225,7 +231,7 @@ class TrainRunner:
     def run(self, n):
         from diffuscene_amd.networks.diffusion_scene_layout_ddpm import train_on_batch
         for _ in range(n):
-            train_on_batch(self.model, self.opt, self.sample, self.tcfg)
+            self.loss = train_on_batch(self.model, self.opt, self.sample, self.tcfg)
 
 
 class phase:
@@ -317,6 +323,44 @@ def timed(ws, fn):
     fn()
     barrier(ws)
     return time.perf_counter() - t0
+
+
+DUMP_MAX_ENTRIES = 1 << 22         # per array written by --dump-outputs (16 MB of float32): larger ones are sampled
+
+
+def _dump_sample(t, seed):
+    """The whole tensor flattened, or -- above DUMP_MAX_ENTRIES -- its entries at a fixed set of sorted positions drawn from `seed`."""
+    import torch
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_MAX_ENTRIES:
+        return flat
+    idx = torch.randint(0, flat.numel(), (DUMP_MAX_ENTRIES,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(dirname, sr, tr, model):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as float32 / float64 .npy files (< 64 MB in all):
+      sample_x        the reverse-diffusion state after the last timed sampling step (B, N, C; sampled above 2^22 entries)
+      train_loss      the loss train_on_batch returned for the last timed training step
+      train_params    the flat parameter buffer after that step's Adam update, at 2^22 fixed positions (seed 0)
+      train_grads     the flat gradient buffer as that step left it, at the same positions
+    The inputs are seeded (build_model, synth_batch, the device generator), so the same arguments give the same inputs on every run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {}
+    if sr:
+        x = sr.g.x
+        arrays["sample_x"] = x if x.numel() <= DUMP_MAX_ENTRIES else _dump_sample(x, 1)
+    if tr:
+        arrays["train_loss"] = torch.tensor([tr.loss], dtype=torch.float64)
+        fs = model._dsc_flat
+        arrays["train_params"] = _dump_sample(fs.P, 0)
+        arrays["train_grads"] = _dump_sample(fs.G, 0)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().cpu().numpy())
+    log("outputs of the last timed step written to %s: %s" % (dirname, ", ".join(sorted(arrays))))
 
 
 def git_head():
@@ -895,6 +939,11 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak (default): the config's batch per GPU; strong: the config's batch is the GLOBAL batch, split over "
                          "the ranks (SURVEY.md 8e: B=256 global = 32 scenes per GPU at 8 GPUs, communication-dominated)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: median of three regions, sampling / training rates apart, "
+                         "the 1000-step loop, roofline, CPU baseline, other configurations (the --no-* options below trim it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sweep", action="store_true", help="cpu_baseline: sweep the host thread count on the full-batch steps (~5 minutes)")
     ap.add_argument("--no-full-loop", action="store_true")
@@ -1010,17 +1059,20 @@ def main():
         if tr:
             tr.run(n_t)
 
-    # Headline = the MEDIAN of three timed regions of exactly K steps each (barrier + synchronize on both sides, max over ranks per
-    # region): box-to-box and run-to-run spread (2-4 %) is larger than a single optimisation of the later rounds, so one region
-    # is not a measurement; min / max are reported beside it.
+    # Headline = ONE timed region of exactly K steps (barrier + synchronize on both sides, max over ranks); --full: the MEDIAN of
+    # three such regions: box-to-box and run-to-run spread (2-4 %) is larger than a single optimisation of the later rounds, so
+    # there min / max are reported beside it.
     regions = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 1):
         if sr:
             sr.reset()
         regions.append(timed(mw, region))
     log("timed regions: %s s for %d steps each (%d sample + %d train)" % (", ".join("%.3f" % r for r in regions), args.steps, n_s, n_t))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sr, tr, model)
+    nr = len(regions)
     parts = {}
-    if args.mode == "both":          # the two rates separately (outside the headline regions), median of three as well
+    if args.full and args.mode == "both":          # the two rates separately (outside the headline regions), median of three as well
         ps, pt = [], []
         for _ in range(3):
             sr.reset()
@@ -1028,7 +1080,7 @@ def main():
             pt.append(timed(mw, lambda: tr.run(n_t)) / max(n_t, 1))
         parts = {"sample": ps, "train": pt}
     full = None
-    if sr and not args.no_full_loop:
+    if args.full and sr and not args.no_full_loop:
         if tr:
             sr.sync_weights()        # the loop samples from the weights as the optimizer left them (derived copies re-made, untimed)
         full = sr.full_loop()
@@ -1038,14 +1090,14 @@ def main():
     if mw > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     tmax = [float(v) for v in tmax.tolist()]
-    regions = tmax[0:3]
-    dt = sorted(regions)[1]
+    regions = tmax[0:nr]
+    dt = sorted(regions)[nr // 2]
     if parts:
-        parts = {"sample": sorted(tmax[3:6]), "train": sorted(tmax[6:9])}
+        parts = {"sample": sorted(tmax[nr:nr + 3]), "train": sorted(tmax[nr + 3:nr + 6])}
     if full is not None:
-        full = tmax[9]
+        full = tmax[nr + 6]
     comm = None
-    if mw > 1 and tr:
+    if args.full and mw > 1 and tr:
         from diffuscene_amd import ddp
         comm = ddp.measure_allreduce(model, reps=5)         # the gradient exchange alone (no compute to hide behind)
 
@@ -1057,9 +1109,7 @@ def main():
             "metric": "denoiser steps/sec (%s) at B=%d, N=%d objects" % (what, B, N),
             "value": round(steps_per_s, 3), "unit": "steps/s", "n_gpus": ws, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "statistic": "median of 3 timed regions of %d steps each" % args.steps,
-            "regions_steps_per_s": {"min": round(args.steps * ws / max(regions), 3), "median": round(steps_per_s, 3),
-                                    "max": round(args.steps * ws / min(regions), 3)},
+            "statistic": ("median of 3 timed regions of %d steps each" if args.full else "one timed region of %d steps") % args.steps,
             "scaling": args.scaling, "vs_baseline": None,
             "dtype": dtype_label(), "data": "synthetic",
             "config": {"workload": "%s (%s), B=%d scenes per GPU, N=%d, C=%d, T=1000, mode=%s"
@@ -1068,6 +1118,9 @@ def main():
                        "parallelism": "dp%d" % ws if ws > 1 else "single"},
             "git_head": git_head(),
         }
+        if args.full:
+            out["regions_steps_per_s"] = {"min": round(args.steps * ws / max(regions), 3), "median": round(steps_per_s, 3),
+                                          "max": round(args.steps * ws / min(regions), 3)}
         F = forward_flops(kind, B, N, spec.get("text_len", 0))
         # a sampling step executes LESS than the reference's forward: the time MLP is a table, conditioning-only launches run once per
         # loop -- its rate is quoted on the flops the captured step executes (the plan's own launch list); training runs all of 3 F
@@ -1094,7 +1147,7 @@ def main():
                                     "what": "training step (ms, max over ranks, 6 steps) under each flush schedule of the gradient "
                                             "exchange, measured in this run; UNMEASURED ON HARDWARE before the first SCALE run"}
         plan = sr.g.plan if sr else None
-        if plan is None:
+        if plan is None and args.full:
             with torch.no_grad():
                 eng = model.diffusion.model.engine(device)
                 ctx_dim = 512 if kind == "arrange" else 128
@@ -1102,26 +1155,28 @@ def main():
                 cross = torch.zeros(B, spec["text_len"], 512, device=device) if kind == "text" else None
                 plan = eng.prepare(B, N, cond, cross)
                 plan.x_in.normal_(); plan.t_in.fill_(500); plan.run()
-        out["roofline"] = roofline_dominant_kernel(plan, N, args.config)
-        log("roofline done")
+        if args.full:
+            out["roofline"] = roofline_dominant_kernel(plan, N, args.config)
+            log("roofline done")
         # whole-model roofline fraction.  Exact-f32 arithmetic: algorithmic flops against the f32-MFMA peak.  Split arithmetic: only the
         # launches the library's dispatcher really runs on the split kernel (dsc_gemm_arithmetic on the plan's own argument structs)
         # execute 6 bf16 products per f32 product -- small launches stay on the f32-MFMA kernel (the text config: all of them) and are
         # counted once; quoted only when the split launches carry the bulk of the forward's GEMM flops
-        sf = split_flop_fraction(plan)
-        out["gemm_flops_on_split_kernel"] = round(sf, 4)
-        from diffuscene_amd import _lib
-        if not _lib.split_enabled():
-            out["model_frac_of_fp32_mfma_peak"] = round(out["model_tflops"] / PEAK_FP32_MFMA_TFLOPS, 4)
-        elif sf >= 0.9:
-            mult = 1.0 + (SPLIT_PRODUCTS - 1) * sf
-            out["model_executed_tflops"] = round(out["model_tflops"] * mult, 1)
-            out["model_frac_of_bf16_mfma_peak"] = round(out["model_tflops"] * mult / PEAK_BF16_MFMA_TFLOPS, 4)
-        if not args.no_cpu_baseline and ws == 1:          # the CPU baseline is a single-GPU-run figure (rank 0, N = 1 only)
+        if plan is not None:
+            sf = split_flop_fraction(plan)
+            out["gemm_flops_on_split_kernel"] = round(sf, 4)
+            from diffuscene_amd import _lib
+            if not _lib.split_enabled():
+                out["model_frac_of_fp32_mfma_peak"] = round(out["model_tflops"] / PEAK_FP32_MFMA_TFLOPS, 4)
+            elif sf >= 0.9:
+                mult = 1.0 + (SPLIT_PRODUCTS - 1) * sf
+                out["model_executed_tflops"] = round(out["model_tflops"] * mult, 1)
+                out["model_frac_of_bf16_mfma_peak"] = round(out["model_tflops"] * mult / PEAK_BF16_MFMA_TFLOPS, 4)
+        if args.full and not args.no_cpu_baseline and ws == 1:          # the CPU baseline is a single-GPU-run figure (rank 0, N = 1 only)
             out["cpu_baseline"] = cpu_baseline(spec, args.mode, sweep=args.cpu_sweep)
         default_run = (ws == 1 and args.config == "living80" and args.mode == "both" and not args.batch and not args.objects
                        and args.scaling == "weak")
-        if default_run and not args.no_other_configs:
+        if args.full and default_run and not args.no_other_configs:
             # everything else this repo quotes, in the driver's own run (outside the timed region above; its memory is released first)
             from diffuscene_amd import _lib
             del sr, tr, plan, model

@@ -81,6 +81,16 @@ def test_real_train_diffusion_script_drives_the_package(tmp_path, golden_dir, mo
         return 0.125
     monkeypatch.setattr(ours, "_train_on_batch", rec_train)
     monkeypatch.setattr(ours, "_validate_on_batch", rec_val)
+    # save_experiment_params stamps params.json with `git rev-parse HEAD` of the working directory; a checkout without .git has
+    # none, so that one command answers a fixed hash here (every other command runs as it is)
+    import subprocess
+    real_check_output = subprocess.check_output
+
+    def check_output(cmd, *a, **kw):
+        if list(cmd) == ["git", "rev-parse", "HEAD"]:
+            return b"0" * 40
+        return real_check_output(cmd, *a, **kw)
+    monkeypatch.setattr(subprocess, "check_output", check_output)
     import train_diffusion
     out = tmp_path / "out"
     train_diffusion.main([str(cfg_path), str(out), "--experiment_tag", "exp", "--seed", "3"])

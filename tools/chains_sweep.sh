@@ -8,7 +8,7 @@ O=$R/gpurun_out/${TAG}_chains_sweep.txt
 : > $O
 for c in text bedroom21 complete arrange living80; do
   for n in 1 2 4; do
-    DSC_CHAINS=$n timeout 300 python $R/bench.py --config $c --mode sample --steps 40 --warmup 10 --no-cpu-baseline --no-full-loop 2>/dev/null | tail -1 | \
+    DSC_CHAINS=$n timeout 300 python $R/bench.py --full --config $c --mode sample --steps 40 --warmup 10 --no-cpu-baseline --no-full-loop 2>/dev/null | tail -1 | \
       python -c "
 import json,sys
 d=json.loads(sys.stdin.read())

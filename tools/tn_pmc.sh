@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 : > $O/${TAG}_tn_pmc.txt
 for f in 1 2; do
   DSC_TN_FORM=$f timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE \
-    -d $O/${TAG}_tnpmc_$f -o p -- python $R/bench.py --mode train --steps 2 --warmup 2 --no-cpu-baseline --no-other-configs > $O/${TAG}_tnpmc_$f.log 2>&1
+    -d $O/${TAG}_tnpmc_$f -o p -- python $R/bench.py --full --mode train --steps 2 --warmup 2 --no-cpu-baseline --no-other-configs > $O/${TAG}_tnpmc_$f.log 2>&1
   python - <<PY >> $O/${TAG}_tn_pmc.txt
 import glob, sqlite3
 db = glob.glob("$O/${TAG}_tnpmc_$f/**/*.db", recursive=True)[0]
