@@ -136,6 +136,10 @@ SIGNATURES = {
                                    c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "dsc_device_error_count": (C.c_int64, [C.c_int32]),
     "dsc_add_scalar_i64": (C.c_int, [c_i64p, C.c_int32, C.c_int64, C.c_void_p]),
+    "dsc_ddim_step_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                    c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                    C.c_void_p]),
+    "dsc_ddim_advance_i64": (C.c_int, [c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int32, C.c_void_p]),
     "dsc_knn16_f32": (C.c_int, [c_f32p, C.c_int64, C.c_int32, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "dsc_rowsq_f32": (C.c_int, [c_f32p, C.c_int64, C.c_int32, C.c_int64, c_f32p, C.c_void_p]),
     "dsc_knn_cov_f32": (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, c_f32p, C.c_int64, C.c_void_p]),

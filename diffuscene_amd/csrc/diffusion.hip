@@ -58,6 +58,59 @@ __global__ void add_scalar_i64_kernel(int64_t* t, int count, int64_t delta) {
     if (i < count) t[i] += delta;
 }
 
+// One DDIM step (ddim_sample_loop, diffusion_ddpm.py:402-444, x_start / pred_noise as model_predictions(clip_x_start=True,
+// rederive_pred_noise=False), :242-264).  Every scene is at the same step: the step index k comes from a device counter and the
+// per-step scalars from device tables of S rows (t, t_next, sqrt(alpha_next), c, sigma), so the launch can be captured once and
+// replayed.  x_start is always clamped to [-1, 1] (the reference ignores clip_denoised here).  t_next < 0 (the last pair): out = x_start
+// and the noise is not read.  Each product and sum is rounded on its own, and the division is IEEE (no fast-math): bit-identical
+// to the reference's fp32 expressions.
+__global__ __launch_bounds__(256) void ddim_step_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ noise,
+                                                       const int64_t* __restrict__ step, const int64_t* __restrict__ times,
+                                                       const int64_t* __restrict__ times_next, const float* __restrict__ sqrt_an,
+                                                       const float* __restrict__ cnoise, const float* __restrict__ sigma,
+                                                       const float* __restrict__ ca, const float* __restrict__ cb,
+                                                       const float* __restrict__ ra, const float* __restrict__ rm,
+                                                       float* out,   // out may alias xt (in-place step)
+                                                       float* __restrict__ x0_out, int mean_type, int64_t inner, int S, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
+    const int64_t k = dsc_checked_index(step[0], S, first);
+    const int64_t tv = dsc_checked_index(times[k], T, first);
+    const bool last = times_next[k] < 0;
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float R = ra[tv], M = rm[tv];
+    const float an = sqrt_an[k], c = cnoise[k], sg = sigma[k];
+    const int64_t base = (int64_t)b * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = xt[base + i], m = mo[base + i];
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (x0_out) x0_out[base + i] = x0;
+        if (last) { out[base + i] = x0; continue; }
+        float pn;
+        if (mean_type == DSC_MEAN_EPS) pn = m;
+        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
+        const float u0 = x0 * an, u1 = c * pn;
+        const float u = u0 + u1;
+        const float nz = sg * noise[base + i];
+        out[base + i] = u + nz;
+    }
+}
+
+// Advance of the captured DDIM loop: step += 1, then t[i] = times[step] for the next model call.  One block: every thread reads the
+// counter before thread 0 stores it.
+__global__ __launch_bounds__(256) void ddim_advance_kernel(int64_t* step, const int64_t* __restrict__ times, int64_t* __restrict__ t,
+                                                          int count, int S) {
+    const int64_t k = step[0] + 1;
+    __syncthreads();
+    if (threadIdx.x == 0) step[0] = k;
+    const int64_t tv = times[dsc_checked_index(k, S, threadIdx.x == 0)];
+    for (int i = threadIdx.x; i < count; i += blockDim.x) t[i] = tv;
+}
+
 __global__ __launch_bounds__(256) void complete_overwrite_kernel(float* __restrict__ x, const float* __restrict__ partial,
                                                                 const float* __restrict__ noise,
                                                                 const int64_t* __restrict__ t, const float* __restrict__ sa,
@@ -144,6 +197,36 @@ extern "C" int dsc_add_scalar_i64(int64_t* t, int32_t count, int64_t delta, dsc_
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(add_scalar_i64_kernel, dim3((count + 255) / 256), dim3(256), 0,
                        static_cast<hipStream_t>(stream), t, count, delta);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_step_f32(const float* x_t, const float* model_out, const float* noise, const int64_t* step,
+                                 const int64_t* times, const int64_t* times_next, const float* sqrt_alpha_next,
+                                 const float* c_noise, const float* sigma, const float* ca, const float* cb,
+                                 const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float* out, float* x0_out,
+                                 int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
+                                 dsc_stream_t stream) {
+    if (!x_t || !model_out || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
+        !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, noise, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca, cb,
+                       sqrt_recip_ac, sqrt_recipm1_ac, out, x0_out, mean_type, inner, num_steps, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_advance_i64(int64_t* step, const int64_t* times, int64_t* t, int32_t count, int32_t num_steps,
+                                    dsc_stream_t stream) {
+    if (!step || !times || !t || count < 1 || num_steps < 1) return DSC_EINVAL;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_advance_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), step, times, t, count,
+                       num_steps);
     DSC_LAUNCH_CHECK();
     return 0;
 }

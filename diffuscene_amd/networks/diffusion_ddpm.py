@@ -128,6 +128,8 @@ class GaussianDiffusion:
         self._sigma_large = torch.exp(0.5 * self._logvar_large)
         self._dev = {}
         self._graphs = {}
+        self._ddim_host = {}
+        self._ddim_dev = {}
 
     # ------------------------------------------------------------------ device-resident tables
     _TABLE_NAMES = ("betas", "alphas_cumprod", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod",
@@ -326,10 +328,85 @@ class GaussianDiffusion:
         assert imgs[-1].shape == shape
         return imgs
 
-    def ddim_sample_loop(self, *args, **kwargs):
-        # the reference implementation (:401-444) reads an undefined self.self_condition and calls
-        # model_predictions without denoise_fn: it cannot run; no shipped script reaches it.
-        raise NotImplementedError("ddim_sample_loop is dead code in the reference (diffusion_ddpm.py:419-420)")
+    # ------------------------------------------------------------------ DDIM (reference :401-444)
+    def ddim_schedule(self, sampling_timesteps, ddim_sampling_eta):
+        """Host side of ddim_sample_loop: the (t, t_next) pairs exactly as the reference derives them (:409-411: float32 linspace,
+        truncating .int(), the last pair ends at -1) and the (3, S) float32 rows [sqrt(alpha_next), c, sigma] from the reference's own
+        scalar expressions (:428-432; zeros on the final pair, which takes x_start).  Cached per (S, eta)."""
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        key = (S, eta)
+        hit = self._ddim_host.get(key)
+        if hit is not None:
+            return hit
+        times = torch.linspace(-1, self.num_timesteps - 1, steps=S + 1)
+        times = list(reversed(times.int().tolist()))
+        pairs = list(zip(times[:-1], times[1:]))
+        coef = torch.zeros((3, S), dtype=torch.float32)
+        for k, (time, time_next) in enumerate(pairs):
+            if time_next < 0:
+                continue
+            alpha = self.alphas_cumprod[time]
+            alpha_next = self.alphas_cumprod[time_next]
+            sigma = eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)).sqrt()
+            c = (1 - alpha_next - sigma ** 2).sqrt()
+            coef[0, k] = alpha_next.sqrt()
+            coef[1, k] = c
+            coef[2, k] = sigma
+        self._ddim_host[key] = (pairs, coef)
+        return pairs, coef
+
+    def ddim_tables(self, sampling_timesteps, ddim_sampling_eta, device):
+        """Device copy of ddim_schedule: (pairs, times (S,) int64, times_next (S,) int64, coef (3, S) fp32), once per (S, eta, device)."""
+        pairs, coef = self.ddim_schedule(sampling_timesteps, ddim_sampling_eta)
+        device = torch.device(device)
+        key = (len(pairs), float(ddim_sampling_eta), device)
+        hit = self._ddim_dev.get(key)
+        if hit is None:
+            self.tables(device)                 # the device check
+            times = torch.tensor([p[0] for p in pairs], dtype=torch.int64).to(device)
+            times_next = torch.tensor([p[1] for p in pairs], dtype=torch.int64).to(device)
+            hit = (pairs, times, times_next, coef.to(device))
+            self._ddim_dev[key] = hit
+        return hit
+
+    def ddim_step(self, x_t, model_output, noise, step, dtab, out=None, x0_out=None):
+        """One DDIM update at the step held by the device counter ``step`` (dtab = ddim_tables(...)): the fused HIP kernel."""
+        _, times, times_next, coef = dtab
+        tb = self.tables(x_t.device)
+        ca, cb = self._coeffs(tb)
+        return ops.ddim_step(x_t, model_output, noise, step, times, times_next, coef, ca, cb, tb["sqrt_recip_alphas_cumprod"],
+                             tb["sqrt_recipm1_alphas_cumprod"], _MEAN[self.model_mean_type], out=out, x0_out=x0_out)
+
+    @torch.no_grad()
+    def ddim_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
+                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None):
+        """DDIM sampling, reference :402-444 (its two call-site slips bridged: model_predictions gets ``denoise_fn``, and there is no
+        self-conditioning).  Draw order: x_T, then one draw per pair except the last ((t, -1) takes x_start): S draws in all.
+        x_start is always clamped to [-1, 1], as in the reference, whatever ``clip_denoised`` says.  The network runs on the static
+        plan, each update is one HIP kernel (dsc_ddim_step_f32); by default (``graph=None``, the rules of p_sample_loop) the loop is a
+        replayed hipGraph step.  ``return_all_timesteps=True`` returns the S + 1 states (eager loop)."""
+        assert isinstance(shape, (tuple, list))
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        self.ddim_sampling_eta, self.sampling_timesteps = eta, S          # the reference keeps both on the instance (:404-405)
+        if not return_all_timesteps and _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_ddim_sample_loop
+            return graph_ddim_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn)
+        dtab = self.ddim_tables(S, eta, device)
+        pairs = dtab[0]
+        step = torch.zeros((1,), dtype=torch.int64, device=device)
+        t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(pairs[0][0])
+        img = noise_fn(size=shape, dtype=torch.float, device=device)
+        imgs = [img]
+        for time, time_next in pairs:
+            model_output = denoise_fn(img, t_, condition, condition_cross)
+            last = time_next < 0
+            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
+            img = self.ddim_step(img.contiguous(), model_output.contiguous(), noise.contiguous(), step, dtab)
+            imgs.append(img)
+            if not last:
+                ops.ddim_advance(step, dtab[1], t_)
+        assert img.shape == tuple(shape)
+        return imgs if return_all_timesteps else img
 
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
@@ -482,6 +559,17 @@ class GaussianDiffusion:
             return total_bpd_b.mean(), vals_bt_.mean(), prior_bpd_b.mean(), mse_bt_.mean()
 
 
+def _check_ddim(num_timesteps, sampling_timesteps, ddim_sampling_eta):
+    """(S, eta) of a DDIM call, or ValueError: 1 <= S <= T, 0 <= eta <= 1 (eta > 1 takes the root of a negative number, :431)."""
+    S = sampling_timesteps
+    if isinstance(S, bool) or not isinstance(S, (int, np.integer)) or not 1 <= int(S) <= num_timesteps:
+        raise ValueError("sampling_timesteps must be an integer in [1, %d], got %r" % (num_timesteps, S))
+    eta = float(ddim_sampling_eta)
+    if not 0.0 <= eta <= 1.0:
+        raise ValueError("ddim_sampling_eta must lie in [0, 1], got %r" % (ddim_sampling_eta,))
+    return int(S), eta
+
+
 def _use_graph(graph, noise_fn, denoise_fn=None):
     """Does this reverse loop run as the replayed hipGraph step (sampler.py)?  ``graph=True`` / ``False`` decide; None (what the
     reference's call sites pass) = yes by default since round 6 -- the captured loop is bit-identical to the eager one and not
@@ -549,8 +637,12 @@ class DiffusionPoint(nn.Module):
                                                        condition_cross=condition_cross, noise_fn=noise_fn, freq=freq,
                                                        clip_denoised=clip_denoised, keep_running=keep_running)
 
-    def gen_samples_ddim(self, *args, **kwargs):
-        return self.diffusion.ddim_sample_loop(*args, **kwargs)
+    def gen_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, clip_denoised=True,
+                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None):
+        return self.diffusion.ddim_sample_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                               condition_cross=condition_cross, noise_fn=noise_fn, clip_denoised=clip_denoised,
+                                               sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                               return_all_timesteps=return_all_timesteps, graph=graph)
 
     def complete_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                          clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):

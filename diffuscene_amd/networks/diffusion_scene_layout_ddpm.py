@@ -228,8 +228,15 @@ class DiffusionSceneLayout_DDPM(Module):
 
     # ------------------------------------------------------------------------------------ sampling
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
-               input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None):
-        """reference :228-310"""
+               input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
+               sampling_timesteps=None, ddim_sampling_eta=0.0):
+        """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
+        switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
+        unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
+        defines no strided completion or re-arrangement: those refuse it."""
+        if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
+            raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
+                                      "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
         device = room_mask.device
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept: it advances the CPU RNG (:232)
         condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
@@ -255,6 +262,10 @@ class DiffusionSceneLayout_DDPM(Module):
                                                    condition_cross=condition_cross, clip_denoised=clip_denoised,
                                                    partial_boxes=partial_boxes)
         print('unconditional / conditional generation sampling')
+        if sampling_timesteps is not None:
+            return self.diffusion.gen_samples_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
+                                                   clip_denoised=clip_denoised, sampling_timesteps=sampling_timesteps,
+                                                   ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj))
         if ret_traj:
             return self.diffusion.gen_sample_traj(noise.shape, device, freq=freq, condition=condition,
                                                   condition_cross=condition_cross, clip_denoised=clip_denoised)
@@ -263,9 +274,10 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
-                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False):
+                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
+                        ddim_sampling_eta=0.0):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
-                              clip_denoised=clip_denoised, batch_seeds=batch_seeds)
+                              clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -345,10 +357,10 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
-                                batch_seeds=None, keep_empty=False):
+                                batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
         """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
-                              batch_seeds=batch_seeds)
+                              batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -359,6 +371,13 @@ class DiffusionSceneLayout_DDPM(Module):
         for k in ("translations", "sizes", "angles") + (("objfeats",) if self.objfeat_dim > 0 else ()):
             out[k] = samples_dict[k].detach().to("cpu")[:, keep, :].contiguous()
         return out
+
+
+def _ddim_kwargs(sampling_timesteps, ddim_sampling_eta):
+    """The DDIM keywords ``sample`` receives: none at all on the DDPM path, so that call stays what it was."""
+    if sampling_timesteps is None:
+        return {}
+    return dict(sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
 
 
 def train_on_batch(model, optimizer, sample_params, config):

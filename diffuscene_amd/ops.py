@@ -388,6 +388,41 @@ def add_scalar_i64(t, delta):
     return t
 
 
+def ddim_step(x_t, model_out, noise, step, times, times_next, coef, ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, mean_type,
+              out=None, x0_out=None):
+    """One DDIM step (see the C header).  ``step`` is the (1,) int64 device counter, ``times`` / ``times_next`` the (S,) int64 pairs and
+    ``coef`` the (3, S) fp32 rows [sqrt(alpha_next), c, sigma]; ``noise`` is not read on the final pair (pass any tensor of x_t's shape)."""
+    _c(x_t, "x_t"); _c(model_out, "model_out"); _c(noise, "noise")
+    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
+    S = times.numel()
+    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
+    if model_out.shape != x_t.shape or noise.shape != x_t.shape:
+        raise RuntimeError("diffuscene_amd: ddim_step operands of different shapes")
+    if out is None:
+        out = torch.empty_like(x_t)
+    b = x_t.shape[0]
+    _lib.check(_lib.fn("dsc_ddim_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), step.data_ptr(),
+                                            times.data_ptr(), times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
+                                            coef[2].data_ptr(), ca.data_ptr() if ca is not None else None,
+                                            cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
+                                            sqrt_recipm1_ac.data_ptr(), out.data_ptr(),
+                                            x0_out.data_ptr() if x0_out is not None else None, mean_type, b,
+                                            x_t.numel() // b, S, _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac),
+                                            stream_ptr()), "dsc_ddim_step_f32")
+    return out
+
+
+def ddim_advance(step, times, t):
+    """step += 1; t[:] = times[step] (device-side, capturable)."""
+    _dev(step, "step", torch.int64); _dev(t, "t", torch.int64); _dev(times, "times", torch.int64)
+    if not times.is_contiguous():
+        raise RuntimeError("diffuscene_amd: times must be contiguous")
+    _lib.check(_lib.fn("dsc_ddim_advance_i64")(step.data_ptr(), times.data_ptr(), t.data_ptr(), t.numel(), times.numel(),
+                                               stream_ptr()), "dsc_ddim_advance_i64")
+    return t
+
+
 def postfilter_compact(samples, empty_col, per_scene=False, keep_empty=False):
     """(B,N,C) generated scenes -> (packed (B,N,C) with the kept slots first, counts (B,) int32); see the C header."""
     _c(samples, "samples")

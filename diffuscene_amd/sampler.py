@@ -5,6 +5,7 @@ reverse step -- the denoiser launch plan (~140 kernels), the noise draw and the 
 captured once into a hipGraph whose only state is device-resident (x_t, the int64 timestep vector, the
 conditioning buffers of the plan) and replayed T times; the timestep is decremented by a kernel inside the graph.
 RNG draw order is the reference's: x_T first, then one draw per step (also at t == 0).
+DDIM (ddim_sample_loop, :402-444) has its own captured step (_DDIMGraph): plan run, draw, fused DDIM step, advance kernel.
 """
 import torch
 
@@ -208,6 +209,127 @@ def graph_sample_loop(diff, denoise_fn, shape, device, condition, condition_cros
             out[:, :partial_boxes.shape[1], :] = partial_boxes          # clean objects restored after the last step (:471-473)
         from ._lib import check_indices
         check_indices("graph_sample_loop")     # DSC_CHECK_INDICES=1 (debugging; synchronises)
+        return out
+
+
+class _DDIMGraph:
+    """The captured DDIM loop (reference ddim_sample_loop, diffusion_ddpm.py:402-444).  ``graph``: plan run, noise draw, the fused
+    step (dsc_ddim_step_f32) and the advance kernel (step += 1, t = times[step]), replayed S - 1 times; ``final``: plan run and the
+    draw-free last step ((t, -1) -> x_start), replayed once.  The step counter and the per-step tables (t, t_next, sqrt(alpha_next), c,
+    sigma) are captured by pointer: this object owns them and ``run`` refreshes them IN PLACE (eta is not part of the cache key), so
+    a live graph never points at a freed table."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False):
+        B, N, C = shape
+        self.shape, self.S = shape, S
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        ra, rm = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
+        mean_type = _MEAN[diff.model_mean_type]
+        self.x = torch.empty(shape, device=device, dtype=torch.float32)
+        self.t = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.step = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.times = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.times_next = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.coef = torch.zeros((3, S), device=device, dtype=torch.float32)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((S,) + tuple(shape), device=device) if replay else None    # x_T, then S - 1 step draws
+        xv = self.x.view(B * N, C)
+
+        def step(final):
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            if final:
+                noise = self.x                                   # not read on the last pair
+            elif self.replay:
+                noise = self.noise_buf.index_select(0, self.draw)[0]
+                ops.add_scalar_i64(self.draw, 1)
+            else:
+                noise = torch.randn(shape, dtype=torch.float, device=device)
+            ops.ddim_step(self.x, plan.out.view(B, N, C), noise, self.step, self.times, self.times_next, self.coef, ca, cb,
+                          ra, rm, mean_type, out=self.x)
+            if not final:
+                ops.ddim_advance(self.step, self.times, self.t)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  With all-zero tables
+        # every index of the warm-up is in range (the advance moves the counter to 1 < S only when there is a non-final step).
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x.normal_()
+        kinds = ([False] if S > 1 else []) + [True]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in kinds:
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = None
+        if S > 1:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                step(False)
+        self.final = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.final, pool=self.graph.pool() if self.graph is not None else None):
+            step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+
+    def run(self, x_T, dtab, noise_buffer=None):
+        pairs, times, times_next, coef = dtab
+        assert len(pairs) == self.S
+        self.check_current()
+        self.times.copy_(times)                 # in place: the graphs hold these pointers
+        self.times_next.copy_(times_next)
+        self.coef.copy_(coef)
+        self.x.copy_(x_T)
+        self.step.zero_()
+        self.t.fill_(pairs[0][0])
+        if self.replay:
+            self.noise_buf.copy_(noise_buffer[:self.S])
+            self.draw.fill_(1)                                  # draw 0 was x_T
+        for _ in range(self.S - 1):
+            self.graph.replay()
+        self.final.replay()
+        return self.x.clone()
+
+
+def graph_ddim_sample_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta,
+                           noise_fn=torch.randn):
+    """ddim_sample_loop as replayed hipGraphs; bit-identical to the eager loop (same kernels, same draws in the same order)."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    S = int(sampling_timesteps)
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay and noise_fn.buffer.shape[0] < S:
+            raise ValueError("NoiseReplay holds %d draws, DDIM with S = %d makes %d" % (noise_fn.buffer.shape[0], S, S))
+        dtab = diff.ddim_tables(S, eta, device)
+        key = (("ddim", S), id(model), tuple(shape), str(device), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
+               None if condition_cross is None else tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _DDIMGraph(diff, model, tuple(shape), device, condition, condition_cross, S, replay)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(shape[0], shape[1], condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], dtab, noise_fn.buffer)
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, dtab)
+        from ._lib import check_indices
+        check_indices("graph_ddim_sample_loop")
         return out
 
 

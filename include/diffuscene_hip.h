@@ -292,6 +292,26 @@ int dsc_p_sample_f32(const float* x_t, const float* model_out, const float* nois
 /* In-graph timestep bookkeeping for the captured reverse loop (:365-366): t[i] += delta. */
 int dsc_add_scalar_i64(int64_t* t, int32_t count, int64_t delta, dsc_stream_t stream);
 
+/* One step of ddim_sample_loop (:402-444) for all b scenes, with x_start / pred_noise of model_predictions(clip_x_start=True,
+ * rederive_pred_noise=False) (:242-264).  k = *step (device counter, clamped to [0, num_steps)); t = times[k], t_next = times_next[k]:
+ *   x0 = clamp(ca[t]*x_t - cb[t]*model_out, -1, 1)   (ca, cb as dsc_p_sample_f32; mean_type x0: clamp(model_out))
+ *   pred_noise = model_out (eps)  |  (sqrt_recip_ac[t]*x_t - x0) / sqrt_recipm1_ac[t] (x0, v)
+ *   t_next <  0: out = x0 (noise is not read)
+ *   t_next >= 0: out = ((x0 * sqrt_alpha_next[k]) + (c_noise[k] * pred_noise)) + (sigma[k] * noise)
+ * Every product and sum is rounded separately and the division is IEEE: bit-identical to the fp32 CPU expressions.  The three
+ * per-step tables (num_steps rows) are tabulated by the host with the reference's expressions.  out may alias x_t; x0_out may be NULL. */
+int dsc_ddim_step_f32(const float* x_t, const float* model_out, const float* noise, const int64_t* step,
+                      const int64_t* times, const int64_t* times_next, const float* sqrt_alpha_next,
+                      const float* c_noise, const float* sigma, const float* ca, const float* cb,
+                      const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float* out, float* x0_out,
+                      int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
+                      dsc_stream_t stream);
+
+/* Step bookkeeping of the captured DDIM loop (:424-425): *step += 1, then t[i] = times[*step] for i < count (the timestep of the
+ * next model call).  One launch, no host work between replays. */
+int dsc_ddim_advance_i64(int64_t* step, const int64_t* times, int64_t* t, int32_t count, int32_t num_steps,
+                         dsc_stream_t stream);
+
 /* Post-filter of generated scenes (delete_empty_from_network_samples, diffusion_scene_layout_ddpm.py:351-406): slot i is
  * dropped when samples[.., i, empty_col] >= 0 (and keep_empty == 0).  mode 0: the decision of batch row 0 is applied to every
  * scene (the reference's loop, :379); mode 1: per scene.  packed (b, n, c): kept rows first, original order, zero tail;
