@@ -206,6 +206,10 @@ SIGNATURES = {
     "dsc_transpose_f32": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "dsc_complete_overwrite_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, c_f32p, c_f32p, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "dsc_complete_overwrite_ragged_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "dsc_p_sample_inpaint_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                           c_f32p, c_f32p, c_f32p, c_f32p] + [C.c_int32] * 7 + [C.c_void_p]),
 }
 
 _lib = None

@@ -125,6 +125,70 @@ __global__ __launch_bounds__(256) void complete_overwrite_kernel(float* __restri
     }
 }
 
+// complete_overwrite_kernel with a per-scene row count: scene b writes rows [0, counts[b]) of x (n rows), reading rows of partial /
+// noise (pmax rows per scene; rows >= counts[b] are padding and never read).  counts[b] is clamped into [0, pmax] and an
+// out-of-range value counted like a bad timestep.  The grid covers pmax rows; a scene with count 0 writes nothing.
+__global__ __launch_bounds__(256) void complete_overwrite_ragged_kernel(float* __restrict__ x, const float* __restrict__ partial,
+                                                                       const float* __restrict__ noise,
+                                                                       const int64_t* __restrict__ counts,
+                                                                       const int64_t* __restrict__ t, const float* __restrict__ sa,
+                                                                       const float* __restrict__ sb, int n, int pmax, int c, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const int64_t tv = dsc_checked_index(t[b], T, first);
+    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    const float a = sa[tv], s = sb[tv];
+    const int64_t pbase = (int64_t)b * pmax * c;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+        const float p0 = a * partial[pbase + i], p1 = s * noise[pbase + i];
+        x[(int64_t)b * n * c + i] = p0 + p1;   // rows [0,count) of scene b are its first count*c elements
+    }
+}
+
+// Fused step of the ragged completion loop: p_sample_kernel on rows >= counts[b]; rows < counts[b] (the given objects, whose
+// posterior step the next overwrite would discard) get what the loop writes there next -- q_sample(partial, t - 1, noise_p) when
+// t > 0 (the overwrite that precedes the next model call), partial itself when t == 0 (the final restore; noise_p is not read).
+// Same expressions, same rounding as p_sample_kernel and complete_overwrite_kernel: bit-identical to their composition.
+__global__ __launch_bounds__(256) void p_sample_inpaint_kernel(const float* xt, const float* __restrict__ mo,
+                                                              const float* __restrict__ noise, const float* __restrict__ partial,
+                                                              const float* __restrict__ noise_p,
+                                                              const int64_t* __restrict__ counts, const int64_t* __restrict__ t,
+                                                              const float* __restrict__ ca, const float* __restrict__ cb,
+                                                              const float* __restrict__ c1, const float* __restrict__ c2,
+                                                              const float* __restrict__ sigma, const float* __restrict__ sa,
+                                                              const float* __restrict__ sb, float* out,   // out may alias xt
+                                                              int mean_type, int clip, int n, int pmax, int c, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const int64_t tv = dsc_checked_index(t[b], T, first);
+    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float k1 = c1[tv], k2 = c2[tv];
+    const float sg = (tv != 0) ? sigma[tv] : 0.f;
+    const bool renoise = tv > 0;
+    const float a = renoise ? sa[tv - 1] : 0.f, s = renoise ? sb[tv - 1] : 0.f;
+    const int64_t inner = (int64_t)n * c;
+    const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < cnt) {
+            const float pv = partial[pbase + i];
+            if (renoise) { const float p0 = a * pv, p1 = s * noise_p[pbase + i]; out[base + i] = p0 + p1; }
+            else out[base + i] = pv;
+            continue;
+        }
+        const float x = xt[base + i], m = mo[base + i];
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float m0 = k1 * x0, m1 = k2 * x;
+        const float mean = m0 + m1;
+        const float nz = sg * noise[base + i];
+        out[base + i] = mean + nz;
+    }
+}
+
 // Post-filter of generated scenes (reference delete_empty_from_network_samples, diffusion_scene_layout_ddpm.py:351-406): slot i
 // of a scene is dropped when its 'empty' logit (column empty_col) is >= 0.  The reference takes that decision from BATCH ROW 0
 // for every scene of the batch (:379, mode 0, kept as the drop-in default); mode 1 decides per scene, which is what batched
@@ -252,6 +316,39 @@ extern "C" int dsc_complete_overwrite_f32(float* x, const float* partial, const 
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(complete_overwrite_kernel, dim3(grid_x((int64_t)p * c), b), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, partial, noise, t, sqrt_ac, sqrt_1mac, n, p, c, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_complete_overwrite_ragged_f32(float* x, const float* partial, const float* noise, const int64_t* counts,
+                                                 const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int32_t b,
+                                                 int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x || !partial || !noise || !counts || !t || !sqrt_ac || !sqrt_1mac || b < 1 || n < 1 || pmax < 1 || pmax > n || c < 1 ||
+        num_timesteps < 1)
+        return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(complete_overwrite_ragged_kernel, dim3(grid_x((int64_t)pmax * c), b), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), x, partial, noise, counts, t, sqrt_ac, sqrt_1mac, n, pmax, c, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
+                                        const float* noise_p, const int64_t* counts, const int64_t* t, const float* ca,
+                                        const float* cb, const float* coef1, const float* coef2, const float* sigma,
+                                        const float* sqrt_ac, const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip,
+                                        int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !noise || !partial || !noise_p || !counts || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
+        !out || b < 1 || n < 1 || pmax < 1 || pmax > n || c < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, noise, partial, noise_p, counts, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
+                       mean_type, clip, n, pmax, c, num_timesteps);
     DSC_LAUNCH_CHECK();
     return 0;
 }

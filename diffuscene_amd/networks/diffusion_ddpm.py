@@ -436,6 +436,48 @@ class GaussianDiffusion:
         assert img_t.shape == shape
         return img_t
 
+    @torch.no_grad()
+    def p_sample_loop_complete_ragged(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
+                                      clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None):
+        """Scene completion of a batch whose scenes are given DIFFERENT numbers of objects.  ``partial_boxes`` is (B, Pmax, C) with
+        1 <= Pmax <= N, ``num_partial`` the (B,) integer counts, 0 <= num_partial[b] <= Pmax; rows >= num_partial[b] of scene b are
+        padding and never read.  Scene b is the reference's p_sample_loop_complete (:447-476) run on that scene alone with
+        partial_boxes[b, :num_partial[b]]: a count of 0 is plain generation, a count of N returns the given scene.  Draw order: x_T,
+        then per step noise_fn(size=(B, Pmax, C)) (rows at or beyond the count are ignored) followed by noise_fn(size=(B, N, C)).
+        This eager loop is built from the unfused pieces -- ragged overwrite, p_sample, restore; the graph path (the default, by the
+        rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B, N, C = shape
+        if partial_boxes is None or num_partial is None:
+            raise ValueError("p_sample_loop_complete_ragged needs partial_boxes (B, Pmax, C) and num_partial (B,)")
+        if partial_boxes.dim() != 3 or partial_boxes.shape[0] != B or partial_boxes.shape[2] != C or not 1 <= partial_boxes.shape[1] <= N:
+            raise ValueError("partial_boxes must be (%d, 1 <= Pmax <= %d, %d), got %s" % (B, N, C, tuple(partial_boxes.shape)))
+        partial_boxes = partial_boxes.contiguous()
+        pmax = partial_boxes.shape[1]
+        counts = ops.ragged_counts(num_partial, B, pmax, device)
+        total_steps = self._total_steps(keep_running)
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_complete_ragged_loop
+            print('last:', 0, self.num_timesteps, len(self.betas))
+            return graph_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised,
+                                              total_steps, noise_fn, partial_boxes, counts)
+        tb = self.tables(device)
+        img_t = noise_fn(size=shape, dtype=torch.float, device=device).clone()   # overwritten in place below
+        for t in reversed(range(0, total_steps)):
+            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
+            noise = noise_fn(size=partial_boxes.shape, dtype=torch.float, device=device)
+            ops.complete_overwrite_ragged(img_t, partial_boxes, noise.contiguous(), counts, t_, tb["sqrt_alphas_cumprod"],
+                                          tb["sqrt_one_minus_alphas_cumprod"])
+            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
+                                  condition_cross=condition_cross, noise_fn=noise_fn,
+                                  clip_denoised=clip_denoised, return_pred_xstart=False)
+            if t == 0:
+                print('last:', t, self.num_timesteps, len(self.betas))
+                given = torch.arange(pmax, device=device)[None, :, None] < counts[:, None, None]
+                img_t[:, :pmax, :] = torch.where(given, partial_boxes, img_t[:, :pmax, :])
+        assert img_t.shape == tuple(shape)
+        return img_t
+
     def p_sample_loop_arrange(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                               clip_denoised=True, keep_running=False, input_boxes=None, graph=None):
         """Re-arrangement, reference :478-506: diffuse [translation | angle] only, re-assemble at t == 0."""
@@ -650,6 +692,14 @@ class DiffusionPoint(nn.Module):
                                                      condition_cross=condition_cross, noise_fn=noise_fn,
                                                      clip_denoised=clip_denoised, keep_running=keep_running,
                                                      partial_boxes=partial_boxes, graph=graph)
+
+    def complete_samples_ragged(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
+                                clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None):
+        """complete_samples for a batch with per-scene numbers of given objects (p_sample_loop_complete_ragged)."""
+        return self.diffusion.p_sample_loop_complete_ragged(self._denoise, shape=shape, device=device, condition=condition,
+                                                            condition_cross=condition_cross, noise_fn=noise_fn,
+                                                            clip_denoised=clip_denoised, keep_running=keep_running,
+                                                            partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
 
     def arrange_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                         clip_denoised=True, keep_running=False, input_boxes=None, graph=None):

@@ -363,6 +363,91 @@ class DiffusionSceneLayout_DDPM(Module):
                               batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
+    def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
+        """Normalise the given objects of ``complete_scene_batched``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor
+        with counts (``num_partial=None``: every scene is given all Pmax rows) -> ((B, num_points, C) float32 on ``device``, rows at or
+        beyond a scene's count ZERO, and the counts as a list of B ints).  ValueError names the offending scene."""
+        if isinstance(partial_boxes, (list, tuple)):
+            if num_partial is not None:
+                raise ValueError("num_partial goes with a padded (B, Pmax, C) tensor; a list of scenes carries its own counts")
+            if len(partial_boxes) != batch_size:
+                raise ValueError("partial_boxes lists %d scenes for a batch of %d" % (len(partial_boxes), batch_size))
+            scenes = []
+            for b, boxes in enumerate(partial_boxes):
+                if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2:
+                    raise ValueError("scene %d: partial boxes must be a (P, %d) tensor" % (b, point_dim))
+                scenes.append(boxes)
+            counts = [int(boxes.shape[0]) for boxes in scenes]
+        else:
+            if not isinstance(partial_boxes, torch.Tensor) or partial_boxes.dim() != 3:
+                raise ValueError("partial_boxes must be a list of (P_b, %d) tensors or a padded (B, Pmax, %d) tensor"
+                                 % (point_dim, point_dim))
+            if partial_boxes.shape[0] != batch_size:
+                raise ValueError("partial_boxes holds %d scenes for a batch of %d" % (partial_boxes.shape[0], batch_size))
+            pmax = int(partial_boxes.shape[1])
+            if num_partial is None:
+                counts = [pmax] * batch_size
+            else:
+                counts = num_partial.tolist() if isinstance(num_partial, torch.Tensor) else list(num_partial)
+                if len(counts) != batch_size:
+                    raise ValueError("num_partial has %d entries for a batch of %d" % (len(counts), batch_size))
+                for b, v in enumerate(counts):
+                    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= pmax:
+                        raise ValueError("scene %d: num_partial %r outside [0, %d], the rows of partial_boxes" % (b, v, pmax))
+                counts = [int(v) for v in counts]
+            scenes = [partial_boxes[b, :counts[b]] for b in range(batch_size)]
+        padded = torch.zeros((batch_size, num_points, point_dim), dtype=torch.float32, device=device)
+        for b, boxes in enumerate(scenes):
+            if boxes.shape[-1] != point_dim:
+                raise ValueError("scene %d: partial boxes have %d channels, the model has %d" % (b, boxes.shape[-1], point_dim))
+            if counts[b] > num_points:
+                raise ValueError("scene %d: %d given objects, more than num_points = %d" % (b, counts[b], num_points))
+            if counts[b]:
+                padded[b, :counts[b]] = boxes.to(device=device, dtype=torch.float32)
+        return padded, counts
+
+    @torch.no_grad()
+    def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
+                               clip_denoised=False, batch_seeds=None, keep_empty=False):
+        """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
+        (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
+        partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
+        (without it: all Pmax rows of every scene).  0 <= P_b <= num_points; 0 is plain generation.  The given rows are padded with
+        zeros to ``num_points``, so one captured graph serves every mix of counts and a ``room_partial_condition`` model sees the
+        reference's cat([partial, zeros]) of each scene.  Returns a list of B dicts; given rows are filtered like any other row."""
+        device = room_mask.device
+        if batch_size is None:
+            batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
+        noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
+        condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
+        if self.room_partial_condition:
+            condition = torch.cat([condition, self.fc_partial_condition(padded)], dim=-1).contiguous()
+        if self.room_arrange_condition:
+            raise ValueError("complete_scene_batched: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
+        condition_cross = self._text_condition(None, None, device)
+        print('scene completion sampling')
+        samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
+                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts)
+        return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
+
+    @torch.no_grad()
+    def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
+                              batch_seeds=None, keep_empty=False):
+        """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
+        each post-filtered on its own."""
+        if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
+            raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
+        if batch_size is None:
+            batch_size = int(input_boxes.shape[0])
+        if input_boxes.shape[0] != batch_size:
+            raise ValueError("input_boxes holds %d scenes for a batch of %d" % (input_boxes.shape[0], batch_size))
+        if input_boxes.shape[1] != num_points or input_boxes.shape[2] != point_dim:
+            raise ValueError("input_boxes: every scene must be (%d, %d), got %s" % (num_points, point_dim, tuple(input_boxes.shape[1:])))
+        samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, clip_denoised=clip_denoised,
+                              batch_seeds=batch_seeds)
+        return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
+
     @torch.no_grad()
     def delete_empty_boxes(self, samples_dict, device="cpu", keep_empty=False):
         cl = samples_dict["class_labels"].detach().to("cpu")

@@ -445,6 +445,75 @@ def complete_overwrite(x, partial, noise, t, sqrt_ac, sqrt_1mac):
     return x
 
 
+def ragged_counts(counts, b, pmax, device):
+    """Per-scene row counts of the ragged completion kernels as a (b,) int64 device tensor.  Counts that are still on the host (a
+    sequence, a CPU tensor) are checked against [0, pmax] here -- ValueError names the scene -- and uploaded; a device tensor is taken
+    as it is (the kernels clamp an out-of-range count and count it: dsc_device_error_count)."""
+    if isinstance(counts, torch.Tensor) and counts.device.type != "cpu":
+        _dev(counts, "counts", torch.int64)
+        if tuple(counts.shape) != (b,) or not counts.is_contiguous():
+            raise RuntimeError("diffuscene_amd: counts must be a contiguous (%d,) int64 tensor" % b)
+        return counts
+    host = counts.tolist() if isinstance(counts, torch.Tensor) else list(counts)
+    if isinstance(counts, torch.Tensor) and (counts.dim() != 1 or counts.dtype.is_floating_point or counts.dtype == torch.bool):
+        raise ValueError("counts must be a 1-d integer tensor, got %s %s" % (tuple(counts.shape), counts.dtype))
+    if len(host) != b:
+        raise ValueError("counts has %d entries for a batch of %d scenes" % (len(host), b))
+    for i, v in enumerate(host):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= pmax:
+            raise ValueError("scene %d: count %r outside [0, %d]" % (i, v, pmax))
+    return torch.tensor([int(v) for v in host], dtype=torch.int64).to(device)
+
+
+def _ragged_args(x, partial, noise_p, counts):
+    _c(x, "x"); _c(partial, "partial"); _c(noise_p, "partial noise")
+    b, n, c = x.shape
+    pmax = partial.shape[1]
+    if tuple(partial.shape) != (b, pmax, c) or tuple(noise_p.shape) != (b, pmax, c) or not 1 <= pmax <= n:
+        raise RuntimeError("diffuscene_amd: partial / noise must be (%d, Pmax <= %d, %d), got %s / %s"
+                           % (b, n, c, tuple(partial.shape), tuple(noise_p.shape)))
+    return b, n, pmax, c, ragged_counts(counts, b, pmax, x.device)
+
+
+def _scene_t(t, b):
+    _dev(t, "t", torch.int64)
+    if tuple(t.shape) != (b,) or not t.is_contiguous():
+        raise RuntimeError("diffuscene_amd: t must be a contiguous (%d,) int64 tensor" % b)
+
+
+def complete_overwrite_ragged(x, partial, noise, counts, t, sqrt_ac, sqrt_1mac):
+    """complete_overwrite with per-scene counts: rows [0, counts[b]) of scene b <- q_sample(partial, t, noise); see the C header."""
+    b, n, pmax, c, cnt = _ragged_args(x, partial, noise, counts)
+    _scene_t(t, b)
+    _lib.check(_lib.fn("dsc_complete_overwrite_ragged_f32")(x.data_ptr(), partial.data_ptr(), noise.data_ptr(), cnt.data_ptr(),
+                                                            t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), b, n, pmax, c,
+                                                            _table_rows(sqrt_ac, sqrt_1mac), stream_ptr()),
+               "dsc_complete_overwrite_ragged_f32")
+    return x
+
+
+def p_sample_inpaint(x_t, model_out, noise, partial, noise_p, counts, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, mean_type,
+                     clip, out=None):
+    """Fused step of the ragged completion loop: p_sample on rows >= counts[b]; the given rows get the re-noising of step t - 1
+    (t > 0) or ``partial`` itself (t == 0).  See the C header."""
+    _c(model_out, "model_out"); _c(noise, "noise")
+    b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
+    _scene_t(t, b)
+    if out is None:
+        out = torch.empty_like(x_t)
+    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
+        raise RuntimeError("diffuscene_amd: p_sample_inpaint operands of different shapes")
+    _lib.check(_lib.fn("dsc_p_sample_inpaint_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
+                                                   noise_p.data_ptr(), cnt.data_ptr(), t.data_ptr(),
+                                                   ca.data_ptr() if ca is not None else None,
+                                                   cb.data_ptr() if cb is not None else None,
+                                                   coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), sqrt_ac.data_ptr(),
+                                                   sqrt_1mac.data_ptr(), out.data_ptr(), mean_type, 1 if clip else 0, b, n, pmax, c,
+                                                   _table_rows(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac), stream_ptr()),
+               "dsc_p_sample_inpaint_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------- training (backward) kernels
 
 _scratch = {}

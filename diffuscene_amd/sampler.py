@@ -6,6 +6,7 @@ captured once into a hipGraph whose only state is device-resident (x_t, the int6
 conditioning buffers of the plan) and replayed T times; the timestep is decremented by a kernel inside the graph.
 RNG draw order is the reference's: x_T first, then one draw per step (also at t == 0).
 DDIM (ddim_sample_loop, :402-444) has its own captured step (_DDIMGraph): plan run, draw, fused DDIM step, advance kernel.
+Batched completion with per-scene counts has another (_RaggedCompleteGraph): plan run, two draws, fused inpainting step, decrement.
 """
 import torch
 
@@ -34,6 +35,27 @@ class NoiseReplay:
             return n
         n = self.buffer[self.i]
         self.i += 1
+        assert tuple(n.shape) == tuple(size), (tuple(n.shape), tuple(size))
+        return n
+
+
+class RaggedNoiseReplay(NoiseReplay):
+    """NoiseReplay for the ragged completion loop, which may be given Pmax == N rows -- the shape test of NoiseReplay cannot tell the
+    two draws apart then.  This one goes by the loop's protocol: call 0 is x_T, then calls alternate partial draw, main draw."""
+
+    def __init__(self, buffer, partial_buffer):
+        super().__init__(buffer, partial_buffer)   # (T+1, B, N, C) and (T, B, Pmax, C)
+        self.calls = 0
+
+    def __call__(self, size=None, dtype=None, device=None):
+        partial = self.calls % 2 == 1
+        self.calls += 1
+        if partial:
+            n = self.partial_buffer[self.ip]
+            self.ip += 1
+        else:
+            n = self.buffer[self.i]
+            self.i += 1
         assert tuple(n.shape) == tuple(size), (tuple(n.shape), tuple(size))
         return n
 
@@ -330,6 +352,171 @@ def graph_ddim_sample_loop(diff, denoise_fn, shape, device, condition, condition
             out = g.run(x_T, dtab)
         from ._lib import check_indices
         check_indices("graph_ddim_sample_loop")
+        return out
+
+
+class _RaggedCompleteGraph:
+    """The captured ragged completion loop (p_sample_loop_complete_ragged).  ``graph``: plan run, the main draw, the partial draw of
+    the NEXT step, the fused update (dsc_p_sample_inpaint_f32: posterior step on the free rows, re-noised given objects on the
+    others) and the timestep decrement, replayed total_steps - 1 times; ``final``: plan run, the main draw and the fused update at
+    t == 0 (given rows restored, no partial draw -- so the loop draws exactly what the eager one draws, in its order).  The first
+    overwrite, at t = total_steps - 1, is one standalone launch in ``run``.  The per-scene counts and the padded given objects live in
+    buffers of this object, captured by pointer and refreshed in place: one graph serves every mix of counts.
+    ``fused=False`` captures the same step from the unfused kernels (partial draw, ragged overwrite, plan run, main draw, p_sample,
+    decrement; restore after the loop) -- the comparison of tools/bench_complete.py."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, pmax, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
+        B, N, C = shape
+        self.shape, self.pmax, self.fused = shape, pmax, fused
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        self.tb = tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        sigma = diff._sigma(tb)
+        mean_type = _MEAN[diff.model_mean_type]
+        sa, sb = tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"]
+        k1, k2 = tb["posterior_mean_coef1"], tb["posterior_mean_coef2"]
+        pshape = (B, pmax, C)
+        self.x = torch.empty(shape, device=device, dtype=torch.float32)
+        self.t = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.partial = torch.zeros(pshape, device=device, dtype=torch.float32)
+        self.counts = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.pdraw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((diff.num_timesteps + 1,) + tuple(shape), device=device) if replay else None
+        self.pnoise_buf = torch.zeros((diff.num_timesteps,) + pshape, device=device) if replay else None
+        xv = self.x.view(B * N, C)
+
+        def draw_main():
+            if not self.replay:
+                return torch.randn(shape, dtype=torch.float, device=device)
+            n = self.noise_buf.index_select(0, self.draw)[0]
+            ops.add_scalar_i64(self.draw, 1)
+            return n
+
+        def draw_partial():
+            if not self.replay:
+                return torch.randn(pshape, dtype=torch.float, device=device)
+            n = self.pnoise_buf.index_select(0, self.pdraw)[0]
+            ops.add_scalar_i64(self.pdraw, 1)
+            return n
+
+        def model_call():
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            return plan.out.view(B, N, C)
+
+        def step(final):
+            if not fused:
+                ops.complete_overwrite_ragged(self.x, self.partial, draw_partial(), self.counts, self.t, sa, sb)
+                mo = model_call()
+                ops.p_sample(self.x, mo, draw_main(), self.t, ca, cb, k1, k2, sigma, mean_type, clip_denoised, out=self.x)
+                ops.add_scalar_i64(self.t, -1)
+                return
+            mo = model_call()
+            noise = draw_main()
+            pn = self.partial if final else draw_partial()          # not read at t == 0
+            ops.p_sample_inpaint(self.x, mo, noise, self.partial, pn, self.counts, self.t, ca, cb, k1, k2, sigma, sa, sb, mean_type,
+                                 clip_denoised, out=self.x)
+            if not final:
+                ops.add_scalar_i64(self.t, -1)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  Counts are all zero
+        # and t goes 1 -> 0: every index of the warm-up is in range.
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x.normal_()
+        self.t.fill_(1)
+        kinds = [False, True] if fused else [False]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in kinds:
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            step(False)
+        self.final = None
+        if fused:
+            self.final = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.final, pool=self.graph.pool()):
+                step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+        self.t.fill_(0)
+
+    def run(self, x_T, total_steps, partial, counts, noise_buffer=None, partial_noise=None):
+        self.check_current()
+        B, N, C = self.shape
+        self.x.copy_(x_T)
+        self.t.fill_(total_steps - 1)
+        self.partial.copy_(partial)             # in place: the graphs hold these pointers
+        self.counts.copy_(counts)
+        if self.replay:
+            self.noise_buf[:noise_buffer.shape[0]].copy_(noise_buffer)
+            self.pnoise_buf[:partial_noise.shape[0]].copy_(partial_noise)
+            self.draw.fill_(1)                                  # draw 0 was x_T
+            self.pdraw.fill_(1 if self.fused else 0)            # fused: partial draw 0 feeds the standalone overwrite below
+        if not self.fused:
+            for _ in range(total_steps):
+                self.graph.replay()
+            out = self.x.clone()
+            given = torch.arange(self.pmax, device=out.device)[None, :, None] < self.counts[:, None, None]
+            out[:, :self.pmax, :] = torch.where(given, self.partial, out[:, :self.pmax, :])
+        else:
+            pn = self.pnoise_buf[0] if self.replay else torch.randn((B, self.pmax, C), dtype=torch.float, device=self.x.device)
+            ops.complete_overwrite_ragged(self.x, self.partial, pn, self.counts, self.t, self.tb["sqrt_alphas_cumprod"],
+                                          self.tb["sqrt_one_minus_alphas_cumprod"])
+            for _ in range(total_steps - 1):
+                self.graph.replay()
+            self.final.replay()
+            out = self.x.clone()
+        self.t.fill_(0)                         # a valid row for a replay too many (see _StepGraph.run)
+        return out
+
+
+def graph_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps,
+                               noise_fn=torch.randn, partial_boxes=None, counts=None, fused=True):
+    """p_sample_loop_complete_ragged as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same
+    order, the same generator state afterwards).  ``counts`` is the (B,) int64 device tensor of ops.ragged_counts.  The cache key
+    holds Pmax but not the counts."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    pmax = partial_boxes.shape[1]
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay and (noise_fn.partial_buffer is None or noise_fn.buffer.shape[0] < total_steps + 1
+                       or noise_fn.partial_buffer.shape[0] < total_steps
+                       or tuple(noise_fn.partial_buffer.shape[1:]) != (B, pmax, C)):
+            raise ValueError("ragged completion replays %d main draws (B, N, C) and %d partial draws (B, Pmax, C)"
+                             % (total_steps + 1, total_steps))
+        key = (("ragged", bool(fused)), id(model), tuple(shape), pmax, str(device), bool(clip_denoised), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
+               None if condition_cross is None else tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _RaggedCompleteGraph(diff, model, tuple(shape), pmax, device, condition, condition_cross, clip_denoised, replay, fused)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], total_steps, partial_boxes, counts, noise_fn.buffer[:total_steps + 1],
+                        noise_fn.partial_buffer[:total_steps])
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, total_steps, partial_boxes, counts)
+        from ._lib import check_indices
+        check_indices("graph_complete_ragged_loop")
         return out
 
 

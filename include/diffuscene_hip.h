@@ -325,6 +325,26 @@ int dsc_complete_overwrite_f32(float* x, const float* partial, const float* nois
                                const float* sqrt_ac, const float* sqrt_1mac,
                                int32_t b, int32_t n, int32_t p, int32_t c, int32_t num_timesteps, dsc_stream_t stream);
 
+/* dsc_complete_overwrite_f32 with a device vector of per-scene row counts (batched completion of scenes that are given
+ * different numbers of objects): scene i writes rows [0, counts[i]) of x (b, n, c) from rows of partial / noise (b, pmax, c);
+ * rows >= counts[i] of partial / noise are padding and never read, a count of 0 writes nothing.  counts (b,) int64, each in
+ * [0, pmax], pmax <= n; an out-of-range count is clamped into that range and counted by dsc_device_error_count. */
+int dsc_complete_overwrite_ragged_f32(float* x, const float* partial, const float* noise, const int64_t* counts,
+                                      const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac,
+                                      int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream);
+
+/* Fused step of the ragged completion loop, one launch after the model call.  Rows >= counts[i] of scene i: dsc_p_sample_f32.
+ * Rows < counts[i] (the given objects):
+ *   t[i] >  0: out = sqrt_ac[t-1] * partial + sqrt_1mac[t-1] * noise_p   (the overwrite that precedes the next model call)
+ *   t[i] == 0: out = partial                                              (the final restore; noise_p is not read)
+ * partial / noise_p are (b, pmax, c), x_t / model_out / noise / out (b, n, c); counts as dsc_complete_overwrite_ragged_f32.
+ * Bit-identical to dsc_p_sample_f32 followed by dsc_complete_overwrite_ragged_f32 at t - 1 (or by the restore).  out may alias x_t. */
+int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
+                             const float* noise_p, const int64_t* counts, const int64_t* t, const float* ca, const float* cb,
+                             const float* coef1, const float* coef2, const float* sigma, const float* sqrt_ac,
+                             const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip,
+                             int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: hand-written backward of the denoiser (the reference relies on torch autograd through
  * denoise_net.py; train_on_batch, diffusion_scene_layout_ddpm.py:456-473).  Input gradients
