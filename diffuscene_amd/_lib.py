@@ -210,6 +210,7 @@ SIGNATURES = {
                                                     C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "dsc_p_sample_inpaint_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p,
                                            c_f32p, c_f32p, c_f32p, c_f32p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "dsc_ddim_inpaint_step_f32": (C.c_int, [c_f32p] * 5 + [c_i64p] * 4 + [c_f32p] * 10 + [C.c_int32] * 7 + [C.c_void_p]),
 }
 
 _lib = None

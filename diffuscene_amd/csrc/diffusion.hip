@@ -189,6 +189,61 @@ __global__ __launch_bounds__(256) void p_sample_inpaint_kernel(const float* xt, 
     }
 }
 
+// Fused step of the strided (DDIM) ragged completion loop: ddim_step_kernel on rows >= counts[b]; rows < counts[b] (the given
+// objects, whose update the next overwrite would discard) get what the loop writes there next -- q_sample(partial, t_next, noise_p)
+// when t_next >= 0 (the overwrite that precedes the next model call), partial itself on the last pair (the final restore; neither
+// noise nor noise_p is read there).  Same expressions, same rounding as ddim_step_kernel and complete_overwrite_ragged_kernel:
+// bit-identical to their composition.
+__global__ __launch_bounds__(256) void ddim_inpaint_step_kernel(const float* xt, const float* __restrict__ mo,
+                                                               const float* __restrict__ noise, const float* __restrict__ partial,
+                                                               const float* __restrict__ noise_p,
+                                                               const int64_t* __restrict__ counts, const int64_t* __restrict__ step,
+                                                               const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
+                                                               const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
+                                                               const float* __restrict__ sigma, const float* __restrict__ ca,
+                                                               const float* __restrict__ cb, const float* __restrict__ ra,
+                                                               const float* __restrict__ rm, const float* __restrict__ sa,
+                                                               const float* __restrict__ sb, float* out,   // out may alias xt
+                                                               int mean_type, int n, int pmax, int c, int S, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;                                  // one count per out-of-range scene
+    const bool first_all = first && blockIdx.y == 0;                                         // one count per launch
+    const int64_t k = dsc_checked_index(step[0], S, first_all);
+    const int64_t tv = dsc_checked_index(times[k], T, first_all);
+    const int64_t tn_raw = times_next[k];
+    const bool last = tn_raw < 0;
+    const int64_t tn = last ? 0 : dsc_checked_index(tn_raw, T, first_all);
+    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float R = ra[tv], M = rm[tv];
+    const float an = sqrt_an[k], cn = cnoise[k], sg = sigma[k];
+    const float a = last ? 0.f : sa[tn], s = last ? 0.f : sb[tn];
+    const int64_t inner = (int64_t)n * c;
+    const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < cnt) {
+            const float pv = partial[pbase + i];
+            if (!last) { const float p0 = a * pv, p1 = s * noise_p[pbase + i]; out[base + i] = p0 + p1; }
+            else out[base + i] = pv;
+            continue;
+        }
+        const float x = xt[base + i], m = mo[base + i];
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (last) { out[base + i] = x0; continue; }
+        float pn;
+        if (mean_type == DSC_MEAN_EPS) pn = m;
+        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
+        const float u0 = x0 * an, u1 = cn * pn;
+        const float u = u0 + u1;
+        const float nz = sg * noise[base + i];
+        out[base + i] = u + nz;
+    }
+}
+
 // Post-filter of generated scenes (reference delete_empty_from_network_samples, diffusion_scene_layout_ddpm.py:351-406): slot i
 // of a scene is dropped when its 'empty' logit (column empty_col) is >= 0.  The reference takes that decision from BATCH ROW 0
 // for every scene of the batch (:379, mode 0, kept as the drop-in default); mode 1 decides per scene, which is what batched
@@ -349,6 +404,28 @@ extern "C" int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out
     hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x_t, model_out, noise, partial, noise_p, counts, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
                        mean_type, clip, n, pmax, c, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
+                                         const float* noise_p, const int64_t* counts, const int64_t* step, const int64_t* times,
+                                         const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise,
+                                         const float* sigma, const float* ca, const float* cb, const float* sqrt_recip_ac,
+                                         const float* sqrt_recipm1_ac, const float* sqrt_ac, const float* sqrt_1mac, float* out,
+                                         int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_steps,
+                                         int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !noise || !partial || !noise_p || !counts || !step || !times || !times_next || !sqrt_alpha_next ||
+        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || n < 1 || pmax < 1 ||
+        pmax > n || c < 1 || num_steps < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_inpaint_step_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, noise, partial, noise_p, counts, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
+                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, n, pmax, c, num_steps, num_timesteps);
     DSC_LAUNCH_CHECK();
     return 0;
 }

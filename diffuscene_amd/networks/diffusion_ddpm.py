@@ -478,6 +478,76 @@ class GaussianDiffusion:
         assert img_t.shape == tuple(shape)
         return img_t
 
+    @torch.no_grad()
+    def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
+                                  sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None):
+        """Strided (DDIM) scene completion of a batch with per-scene numbers of given objects.  Scene b is ddim_sample_loop (reference
+        :402-444) run on that scene alone with ONE addition taken from p_sample_loop_complete (:447-476): before every model call at pair
+        (t, t_next) the first num_partial[b] rows of the state are overwritten in place with q_sample(partial_boxes[b], t, fresh noise);
+        after the last pair the given rows are restored to the clean objects.  The DDIM update reads x_t only through x_start and
+        pred_noise, so the overwrite in front of the model call is the whole change.  ``partial_boxes`` / ``num_partial`` as in
+        p_sample_loop_complete_ragged: a count of 0 is plain gen_samples_ddim on the main draws, a count of N returns the given scene.
+        Draw order: x_T (B, N, C); then per pair a partial draw (B, Pmax, C), the model call and a main draw (B, N, C); the last pair
+        (t, -1) makes the partial draw but no main draw -- 2 S draws in all.  x_start is always clamped to [-1, 1], as in
+        ddim_sample_loop.  The given rows are re-noised with fresh noise at every pair whatever eta is: at eta = 0 the free rows are
+        deterministic given x_T AND the partial draws, not given x_T alone.
+        This eager loop is built from the unfused pieces -- ragged overwrite at the pair's t, model call, ddim_step, ddim_advance,
+        restore; the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
+        dsc_ddim_inpaint_step_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B, N, C = shape
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        if partial_boxes is None or num_partial is None:
+            raise ValueError("ddim_complete_ragged_loop needs partial_boxes (B, Pmax, C) and num_partial (B,)")
+        if partial_boxes.dim() != 3 or partial_boxes.shape[0] != B or partial_boxes.shape[2] != C or not 1 <= partial_boxes.shape[1] <= N:
+            raise ValueError("partial_boxes must be (%d, 1 <= Pmax <= %d, %d), got %s" % (B, N, C, tuple(partial_boxes.shape)))
+        partial_boxes = partial_boxes.contiguous()
+        pmax = partial_boxes.shape[1]
+        counts = ops.ragged_counts(num_partial, B, pmax, device)
+        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_ddim_complete_ragged_loop
+            return graph_ddim_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn,
+                                                   partial_boxes, counts)
+        tb = self.tables(device)
+        dtab = self.ddim_tables(S, eta, device)
+        pairs = dtab[0]
+        step = torch.zeros((1,), dtype=torch.int64, device=device)
+        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
+        img = noise_fn(size=shape, dtype=torch.float, device=device).clone()     # overwritten in place below
+        for time, time_next in pairs:
+            noise_p = noise_fn(size=partial_boxes.shape, dtype=torch.float, device=device)
+            ops.complete_overwrite_ragged(img, partial_boxes, noise_p.contiguous(), counts, t_, tb["sqrt_alphas_cumprod"],
+                                          tb["sqrt_one_minus_alphas_cumprod"])
+            model_output = denoise_fn(img, t_, condition, condition_cross)
+            last = time_next < 0
+            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
+            img = self.ddim_step(img, model_output.contiguous(), noise.contiguous(), step, dtab)
+            if not last:
+                ops.ddim_advance(step, dtab[1], t_)
+        given = torch.arange(pmax, device=device)[None, :, None] < counts[:, None, None]
+        img[:, :pmax, :] = torch.where(given, partial_boxes, img[:, :pmax, :])
+        assert img.shape == tuple(shape)
+        return img
+
+    @torch.no_grad()
+    def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
+                          ddim_sampling_eta=0., input_boxes=None, graph=None):
+        """Strided (DDIM) re-arrangement: ddim_sample_loop on the sub-shape (B, N, translation_dim + angle_dim) under the arrange
+        condition, then the re-assembly of p_sample_loop_arrange (reference :496-503).  Draws: those of ddim_sample_loop on the
+        sub-shape (S in all)."""
+        assert isinstance(shape, (tuple, list))
+        _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        if input_boxes is None or tuple(input_boxes.shape) != tuple(shape):
+            raise ValueError("ddim_arrange_loop needs input_boxes of shape %s" % (tuple(shape),))
+        sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
+        img = self.ddim_sample_loop(denoise_fn, sub, device, condition, condition_cross, noise_fn=noise_fn,
+                                    sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph)
+        tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
+        img = torch.cat([img[:, :, 0:tr], input_boxes[:, :, tr:tr + sz], img[:, :, tr:], input_boxes[:, :, bb:]], dim=-1).contiguous()
+        assert img.shape == tuple(shape)
+        return img
+
     def p_sample_loop_arrange(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                               clip_denoised=True, keep_running=False, input_boxes=None, graph=None):
         """Re-arrangement, reference :478-506: diffuse [translation | angle] only, re-assemble at t == 0."""
@@ -700,6 +770,22 @@ class DiffusionPoint(nn.Module):
                                                             condition_cross=condition_cross, noise_fn=noise_fn,
                                                             clip_denoised=clip_denoised, keep_running=keep_running,
                                                             partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
+
+    def complete_samples_ragged_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
+                                     sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None):
+        """complete_samples_ragged in S strided steps (ddim_complete_ragged_loop)."""
+        return self.diffusion.ddim_complete_ragged_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                                        condition_cross=condition_cross, noise_fn=noise_fn,
+                                                        sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                                        partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
+
+    def arrange_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
+                             sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None):
+        """arrange_samples in S strided steps (ddim_arrange_loop)."""
+        return self.diffusion.ddim_arrange_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                                condition_cross=condition_cross, noise_fn=noise_fn,
+                                                sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                                input_boxes=input_boxes, graph=graph)
 
     def arrange_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                         clip_denoised=True, keep_running=False, input_boxes=None, graph=None):

@@ -182,6 +182,18 @@ class DiffusionSceneLayout_DDPM(Module):
         tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
         return torch.cat([boxes[:, :, tr:tr + sz], boxes[:, :, bb:]], dim=-1).contiguous()
 
+    def _sampling_conditions(self, room_mask, num_points, device, text=None, padded_partial=None, input_boxes=None):
+        """(condition, condition_cross) of a sampling call, reference :233-262: the base condition, then the embedding of the given
+        objects padded with zeros to ``num_points`` (room_partial_condition) and of the kept channels of ``input_boxes``
+        (room_arrange_condition), and the text features.  One copy for ``sample`` and the batched / strided entry points."""
+        condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
+        if self.room_partial_condition:
+            condition = torch.cat([condition, self.fc_partial_condition(padded_partial)], dim=-1).contiguous()
+        if self.room_arrange_condition:
+            condition = torch.cat([condition, self.fc_arrange_condition(self._arrange_input(input_boxes))],
+                                  dim=-1).contiguous()
+        return condition, self._text_condition(text, text, device)
+
     # ------------------------------------------------------------------------------------ training
     def get_loss(self, sample_params):
         """reference :131-226"""
@@ -233,22 +245,21 @@ class DiffusionSceneLayout_DDPM(Module):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
-        defines no strided completion or re-arrangement: those refuse it."""
+        defines no strided completion or re-arrangement, so this drop-in method refuses the combination; strided inpainting lives on
+        the scene-level entry points (``complete_scene_batched``, ``arrange_scene_batched``, ``complete_scene``, ``arrange_scene`` with
+        ``sampling_timesteps``), over ``complete_samples_ragged_ddim`` / ``arrange_samples_ddim``."""
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
                                       "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
         device = room_mask.device
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept: it advances the CPU RNG (:232)
-        condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
+        padded = None
         if self.room_partial_condition:
             zeros = torch.zeros((batch_size, num_points - partial_boxes.shape[1], partial_boxes.shape[2]),
                                 device=device)
-            cond_p = self.fc_partial_condition(torch.cat([partial_boxes, zeros], dim=1).contiguous())
-            condition = torch.cat([condition, cond_p], dim=-1).contiguous()
-        if self.room_arrange_condition:
-            condition = torch.cat([condition, self.fc_arrange_condition(self._arrange_input(input_boxes))],
-                                  dim=-1).contiguous()
-        condition_cross = self._text_condition(text, text, device)
+            padded = torch.cat([partial_boxes, zeros], dim=1).contiguous()
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, text=text, padded_partial=padded,
+                                                               input_boxes=input_boxes)
         if self.text_condition and not (self.text_glove_embedding or self.text_clip_embedding):
             print('after bert:', condition_cross.shape)
         if input_boxes is not None:
@@ -289,16 +300,62 @@ class DiffusionSceneLayout_DDPM(Module):
         return {num_step * i: self.delete_empty_from_network_samples(s, device=device, keep_empty=keep_empty)
                 for i, s in enumerate(traj)}
 
+    def _check_strided(self, sampling_timesteps, ddim_sampling_eta):
+        """(S, eta) of a strided call, ValueError before any loop runs."""
+        from .diffusion_ddpm import _check_ddim
+        return _check_ddim(int(self.config["diffusion_kwargs"].get("time_num", 1000)), sampling_timesteps, ddim_sampling_eta)
+
+    def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta):
+        """The strided completion call behind complete_scene / complete_scene_batched: the condition assembly of ``sample`` (the CPU
+        draw included), then ``complete_samples_ragged_ddim``."""
+        device = room_mask.device
+        torch.randn((batch_size, num_points, point_dim))           # CPU draw kept, as in sample (:232)
+        if self.room_arrange_condition:
+            raise ValueError("scene completion: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
+        print('scene completion sampling')
+        return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
+                                                           condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
+                                                           sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+
+    def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta):
+        """The strided re-arrangement call behind arrange_scene / arrange_scene_batched: the condition assembly of ``sample`` (the CPU
+        draw included), then ``arrange_samples_ddim``."""
+        device = room_mask.device
+        torch.randn((batch_size, num_points, point_dim))           # CPU draw kept, as in sample (:232)
+        if self.room_partial_condition:
+            raise ValueError("re-arrangement: a room_partial_condition model completes scenes (complete_scene_batched)")
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, input_boxes=input_boxes)
+        print('scene arrangement sampling')
+        return self.diffusion.arrange_samples_ddim((batch_size, num_points, point_dim), device, condition=condition,
+                                                   condition_cross=condition_cross, input_boxes=input_boxes,
+                                                   sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+
     @torch.no_grad()
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
-                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False):
+                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
+                       ddim_sampling_eta=0.0):
+        """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
+        every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
+        x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part."""
+        if sampling_timesteps is not None:
+            S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta)
+            return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
                               ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds)
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene(self, room_mask, num_points, point_dim, input_boxes, batch_size=1, ret_traj=False, ddim=False,
-                      clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False):
+                      clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
+                      ddim_sampling_eta=0.0):
+        """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop."""
+        if sampling_timesteps is not None:
+            S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta)
+            return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, ret_traj=ret_traj,
                               ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds)
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
@@ -408,24 +465,30 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
-                               clip_denoised=False, batch_seeds=None, keep_empty=False):
+                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
+                               ddim_sampling_eta=0.0):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
         (without it: all Pmax rows of every scene).  0 <= P_b <= num_points; 0 is plain generation.  The given rows are padded with
         zeros to ``num_points``, so one captured graph serves every mix of counts and a ``room_partial_condition`` model sees the
-        reference's cat([partial, zeros]) of each scene.  Returns a list of B dicts; given rows are filtered like any other row."""
+        reference's cat([partial, zeros]) of each scene.  Returns a list of B dicts; given rows are filtered like any other row.
+        ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim``: S DDIM steps at ``ddim_sampling_eta``, the
+        given rows re-noised with fresh noise before every model call -- so at eta = 0 the free rows are deterministic given x_T and
+        those draws, not given x_T alone; x_start always clamped, ``clip_denoised`` ignored) instead of the T-step one."""
         device = room_mask.device
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        if sampling_timesteps is not None:
+            S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta)
+            return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
-        condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
-        if self.room_partial_condition:
-            condition = torch.cat([condition, self.fc_partial_condition(padded)], dim=-1).contiguous()
         if self.room_arrange_condition:
             raise ValueError("complete_scene_batched: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
-        condition_cross = self._text_condition(None, None, device)
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
         print('scene completion sampling')
         samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                          clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts)
@@ -433,9 +496,9 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
-                              batch_seeds=None, keep_empty=False):
+                              batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
         """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
-        each post-filtered on its own."""
+        each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead."""
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
             raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
         if batch_size is None:
@@ -444,6 +507,10 @@ class DiffusionSceneLayout_DDPM(Module):
             raise ValueError("input_boxes holds %d scenes for a batch of %d" % (input_boxes.shape[0], batch_size))
         if input_boxes.shape[1] != num_points or input_boxes.shape[2] != point_dim:
             raise ValueError("input_boxes: every scene must be (%d, %d), got %s" % (num_points, point_dim, tuple(input_boxes.shape[1:])))
+        if sampling_timesteps is not None:
+            S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta)
+            return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)

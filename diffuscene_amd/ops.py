@@ -514,6 +514,33 @@ def p_sample_inpaint(x_t, model_out, noise, partial, noise_p, counts, t, ca, cb,
     return out
 
 
+def ddim_inpaint_step(x_t, model_out, noise, partial, noise_p, counts, step, times, times_next, coef, ca, cb, sqrt_recip_ac,
+                      sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, mean_type, out=None):
+    """Fused step of the strided (DDIM) ragged completion loop: ddim_step on rows >= counts[b]; the given rows get the re-noising at
+    ``times_next[step]`` or, on the last pair, ``partial`` itself (``noise`` and ``noise_p`` are not read there).  Tables as ddim_step,
+    counts / partial as p_sample_inpaint.  See the C header."""
+    _c(model_out, "model_out"); _c(noise, "noise")
+    b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
+    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
+    S = times.numel()
+    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
+    if out is None:
+        out = torch.empty_like(x_t)
+    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
+        raise RuntimeError("diffuscene_amd: ddim_inpaint_step operands of different shapes")
+    _lib.check(_lib.fn("dsc_ddim_inpaint_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
+                                                    noise_p.data_ptr(), cnt.data_ptr(), step.data_ptr(), times.data_ptr(),
+                                                    times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
+                                                    ca.data_ptr() if ca is not None else None,
+                                                    cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
+                                                    sqrt_recipm1_ac.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
+                                                    out.data_ptr(), mean_type, b, n, pmax, c, S,
+                                                    _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac),
+                                                    stream_ptr()), "dsc_ddim_inpaint_step_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------- training (backward) kernels
 
 _scratch = {}

@@ -7,6 +7,11 @@ conditioning buffers of the plan) and replayed T times; the timestep is decremen
 RNG draw order is the reference's: x_T first, then one draw per step (also at t == 0).
 DDIM (ddim_sample_loop, :402-444) has its own captured step (_DDIMGraph): plan run, draw, fused DDIM step, advance kernel.
 Batched completion with per-scene counts has another (_RaggedCompleteGraph): plan run, two draws, fused inpainting step, decrement.
+Strided (DDIM) batched completion (_DDIMCompleteGraph, ddim_complete_ragged_loop) combines the two: one standalone partial draw and
+ragged overwrite at times[0], then S - 1 replays of [plan run, main draw k, partial draw k + 1, fused dsc_ddim_inpaint_step_f32,
+advance] and one replay of the draw-free final step.  Draw order (eager and captured): x_T, then per pair a partial draw (B, Pmax, C),
+the model call and a main draw (B, N, C); the last pair makes the partial draw only -- 2 S draws.  Strided re-arrangement is
+_DDIMGraph on the sub-shape.
 """
 import torch
 
@@ -44,7 +49,7 @@ class RaggedNoiseReplay(NoiseReplay):
     two draws apart then.  This one goes by the loop's protocol: call 0 is x_T, then calls alternate partial draw, main draw."""
 
     def __init__(self, buffer, partial_buffer):
-        super().__init__(buffer, partial_buffer)   # (T+1, B, N, C) and (T, B, Pmax, C)
+        super().__init__(buffer, partial_buffer)   # (T+1, B, N, C) and (T, B, Pmax, C); the DDIM loop: (S, B, N, C) and (S, B, Pmax, C)
         self.calls = 0
 
     def __call__(self, size=None, dtype=None, device=None):
@@ -517,6 +522,177 @@ def graph_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condi
             out = g.run(x_T, total_steps, partial_boxes, counts)
         from ._lib import check_indices
         check_indices("graph_complete_ragged_loop")
+        return out
+
+
+class _DDIMCompleteGraph:
+    """The captured strided completion loop (ddim_complete_ragged_loop): the draw shift of _RaggedCompleteGraph applied to _DDIMGraph.
+    ``graph`` (only when S > 1): plan run, main draw k, the partial draw of pair k + 1, the fused update (dsc_ddim_inpaint_step_f32:
+    DDIM step on the free rows, the given objects re-noised at t_next on the others) and the advance kernel, replayed S - 1 times;
+    ``final``: plan run and the draw-free fused step of the last pair (x_start on the free rows, the given rows restored), replayed
+    once from ``graph``'s pool.  The first overwrite, at times[0], is one standalone draw and launch in ``run`` -- so the loop draws what
+    the eager one draws, in its order.  The tables, the step counter, the padded given objects and the counts live in buffers of this
+    object, captured by pointer and refreshed in place: one graph serves every eta and every mix of counts.
+    ``fused=False`` captures the same step from the unfused kernels (partial draw, ragged overwrite, plan run, main draw, ddim_step,
+    advance; restore after the loop) -- the comparison of tools/bench_ddim_complete.py."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, pmax, device, condition, condition_cross, S, replay=False, fused=True):
+        B, N, C = shape
+        self.shape, self.pmax, self.S, self.fused = shape, pmax, S, fused
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        self.tb = tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        ra, rm = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
+        sa, sb = tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"]
+        mean_type = _MEAN[diff.model_mean_type]
+        pshape = (B, pmax, C)
+        self.x = torch.empty(shape, device=device, dtype=torch.float32)
+        self.t = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.step = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.times = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.times_next = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.coef = torch.zeros((3, S), device=device, dtype=torch.float32)
+        self.partial = torch.zeros(pshape, device=device, dtype=torch.float32)
+        self.counts = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.pdraw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((S,) + tuple(shape), device=device) if replay else None     # x_T, then S - 1 main draws
+        self.pnoise_buf = torch.zeros((S,) + pshape, device=device) if replay else None           # one partial draw per pair
+        xv = self.x.view(B * N, C)
+
+        def draw_main():
+            if not self.replay:
+                return torch.randn(shape, dtype=torch.float, device=device)
+            n = self.noise_buf.index_select(0, self.draw)[0]
+            ops.add_scalar_i64(self.draw, 1)
+            return n
+
+        def draw_partial():
+            if not self.replay:
+                return torch.randn(pshape, dtype=torch.float, device=device)
+            n = self.pnoise_buf.index_select(0, self.pdraw)[0]
+            ops.add_scalar_i64(self.pdraw, 1)
+            return n
+
+        def model_call():
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            return plan.out.view(B, N, C)
+
+        def step(final):
+            if not fused:
+                ops.complete_overwrite_ragged(self.x, self.partial, draw_partial(), self.counts, self.t, sa, sb)
+                mo = model_call()
+                noise = self.x if final else draw_main()             # not read on the last pair
+                ops.ddim_step(self.x, mo, noise, self.step, self.times, self.times_next, self.coef, ca, cb, ra, rm, mean_type,
+                              out=self.x)
+            else:
+                mo = model_call()
+                noise = self.x if final else draw_main()             # neither is read on the last pair
+                pn = self.partial if final else draw_partial()
+                ops.ddim_inpaint_step(self.x, mo, noise, self.partial, pn, self.counts, self.step, self.times, self.times_next,
+                                      self.coef, ca, cb, ra, rm, sa, sb, mean_type, out=self.x)
+            if not final:
+                ops.ddim_advance(self.step, self.times, self.t)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  Tables, counts and the
+        # step counter are all zero: every index of the warm-up is in range (the advance moves the counter to 1 < S only when there is
+        # a non-final step; times_next[.] = 0 reads row 0 of the schedule).
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x.normal_()
+        kinds = ([False] if S > 1 else []) + [True]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in kinds:
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = None
+        if S > 1:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                step(False)
+        self.final = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.final, pool=self.graph.pool() if self.graph is not None else None):
+            step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+        self.step.zero_()
+
+    def run(self, x_T, dtab, partial, counts, noise_buffer=None, partial_noise=None):
+        pairs, times, times_next, coef = dtab
+        assert len(pairs) == self.S
+        self.check_current()
+        B, N, C = self.shape
+        self.times.copy_(times)                 # in place: the graphs hold these pointers
+        self.times_next.copy_(times_next)
+        self.coef.copy_(coef)
+        self.x.copy_(x_T)
+        self.step.zero_()
+        self.t.fill_(pairs[0][0])
+        self.partial.copy_(partial)
+        self.counts.copy_(counts)
+        if self.replay:
+            self.noise_buf.copy_(noise_buffer[:self.S])
+            self.pnoise_buf.copy_(partial_noise[:self.S])
+            self.draw.fill_(1)                                  # draw 0 was x_T
+            self.pdraw.fill_(1 if self.fused else 0)            # fused: partial draw 0 feeds the standalone overwrite below
+        if self.fused:
+            pn = self.pnoise_buf[0] if self.replay else torch.randn((B, self.pmax, C), dtype=torch.float, device=self.x.device)
+            ops.complete_overwrite_ragged(self.x, self.partial, pn, self.counts, self.t, self.tb["sqrt_alphas_cumprod"],
+                                          self.tb["sqrt_one_minus_alphas_cumprod"])
+        for _ in range(self.S - 1):
+            self.graph.replay()
+        self.final.replay()
+        out = self.x.clone()
+        if not self.fused:
+            given = torch.arange(self.pmax, device=out.device)[None, :, None] < self.counts[:, None, None]
+            out[:, :self.pmax, :] = torch.where(given, self.partial, out[:, :self.pmax, :])
+        return out
+
+
+def graph_ddim_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta,
+                                    noise_fn=torch.randn, partial_boxes=None, counts=None, fused=True):
+    """ddim_complete_ragged_loop as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order,
+    the same generator state afterwards).  ``counts`` is the (B,) int64 device tensor of ops.ragged_counts.  The cache key holds S and
+    Pmax; it holds neither eta nor the counts."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    S = int(sampling_timesteps)
+    pmax = partial_boxes.shape[1]
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay and (noise_fn.partial_buffer is None or noise_fn.buffer.shape[0] < S or noise_fn.partial_buffer.shape[0] < S
+                       or tuple(noise_fn.partial_buffer.shape[1:]) != (B, pmax, C)):
+            raise ValueError("strided ragged completion replays %d main draws (B, N, C) and %d partial draws (B, Pmax, C)" % (S, S))
+        dtab = diff.ddim_tables(S, eta, device)
+        key = (("ddim_ragged", S, bool(fused)), id(model), tuple(shape), pmax, str(device), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
+               None if condition_cross is None else tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _DDIMCompleteGraph(diff, model, tuple(shape), pmax, device, condition, condition_cross, S, replay, fused)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], dtab, partial_boxes, counts, noise_fn.buffer, noise_fn.partial_buffer)
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, dtab, partial_boxes, counts)
+        from ._lib import check_indices
+        check_indices("graph_ddim_complete_ragged_loop")
         return out
 
 

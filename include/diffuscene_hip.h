@@ -345,6 +345,21 @@ int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out, const flo
                              const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip,
                              int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream);
 
+/* Fused step of the strided (DDIM) ragged completion loop, one launch after the model call.  k, t = times[k], t_next = times_next[k]
+ * as dsc_ddim_step_f32.  Rows >= counts[i] of scene i: dsc_ddim_step_f32.  Rows < counts[i] (the given objects):
+ *   t_next >= 0: out = sqrt_ac[t_next] * partial + sqrt_1mac[t_next] * noise_p   (the overwrite that precedes the next model call)
+ *   t_next <  0: out = partial                                                    (the final restore; noise and noise_p are not read)
+ * partial / noise_p are (b, pmax, c), x_t / model_out / noise / out (b, n, c); counts as dsc_complete_overwrite_ragged_f32.  The step
+ * index, times[k], times_next[k] (where non-negative) and counts[i] are clamped into range and counted by dsc_device_error_count.
+ * Bit-identical to dsc_ddim_step_f32 followed by dsc_complete_overwrite_ragged_f32 at t_next (or by the restore).  out may alias x_t. */
+int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
+                              const float* noise_p, const int64_t* counts, const int64_t* step, const int64_t* times,
+                              const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise, const float* sigma,
+                              const float* ca, const float* cb, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
+                              const float* sqrt_ac, const float* sqrt_1mac, float* out, int32_t mean_type,
+                              int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_steps, int32_t num_timesteps,
+                              dsc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: hand-written backward of the denoiser (the reference relies on torch autograd through
  * denoise_net.py; train_on_batch, diffusion_scene_layout_ddpm.py:456-473).  Input gradients
