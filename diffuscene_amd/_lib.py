@@ -21,6 +21,7 @@ TILE_WAVE_GN, TILE_WAVE_DENSE, TILE_WAVE_GN_64 = 10, 11, 12
 GEMM_ROW_INVARIANT = 1          # dsc_gemm_args.flags (include/diffuscene_hip.h)
 WS_MAX = 64
 MAX_TOKENS_PER_SCENE = 160
+STATS_MAX_OBJECTS, STATS_ONE_WAVE_MAX = 160, 32      # DSC_STATS_* (dsc_scene_stats_f32)
 
 _ERR = {-1: "DSC_EINVAL (bad shape / null pointer)", -2: "DSC_EALIGN (16-byte alignment required)",
         -3: "DSC_ERANGE (size outside kernel limits)"}
@@ -186,6 +187,9 @@ SIGNATURES = {
     "dsc_attention_bwd_f32": (C.c_int, [c_f32p, C.c_int64] * 7 + [C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "dsc_retrieve_nearest_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_int32, C.c_int32, C.c_void_p, c_f32p, C.c_void_p]),
+    "dsc_box_bounds_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int32, C.c_int32, c_f32p, C.c_void_p]),
+    "dsc_scene_stats_f32": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p]),
     "dsc_encode_scene_batch_f32": (C.c_int, [c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, c_i64p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_double), c_f32p,
                                              C.c_int64, c_i64p, C.c_int32, C.c_int32, C.c_void_p]),

@@ -433,10 +433,10 @@ extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_ou
 unsigned dsc_bad_index_diffusion(bool reset) { return dsc_read_bad_index_count(reset); }
 
 // Number of out-of-range device indices (timesteps outside [0, num_timesteps)) that kernels had to clamp since the
-// last reset -- 0 in every correct run.  Synchronising (device-to-host reads of two counters): a test / debugging facility.
+// last reset -- 0 in every correct run.  Synchronising (device-to-host reads of the per-unit counters): a test / debugging facility.
 extern "C" int64_t dsc_device_error_count(int32_t reset) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    const unsigned a = dsc_bad_index_diffusion(reset != 0), b = dsc_bad_index_train(reset != 0);
-    if (a == 0xffffffffu || b == 0xffffffffu) return -1;
-    return (int64_t)a + b;
+    const unsigned a = dsc_bad_index_diffusion(reset != 0), b = dsc_bad_index_train(reset != 0), c = dsc_bad_index_retrieval(reset != 0);
+    if (a == 0xffffffffu || b == 0xffffffffu || c == 0xffffffffu) return -1;
+    return (int64_t)a + b + c;
 }

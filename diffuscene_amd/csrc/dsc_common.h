@@ -154,6 +154,7 @@ static inline unsigned dsc_read_bad_index_count(bool reset) {
 // per-unit readers behind dsc_device_error_count (diffusion.hip)
 unsigned dsc_bad_index_diffusion(bool reset);
 unsigned dsc_bad_index_train(bool reset);
+unsigned dsc_bad_index_retrieval(bool reset);
 // clamp only (GEMM prologues: no counter, no branch)
 __device__ __forceinline__ int64_t dsc_clamp_index(int64_t v, int64_t n) { return (v < 0 || n < 1) ? 0 : (v >= n ? n - 1 : v); }    // (n < 1: row 0, never row -1)
 

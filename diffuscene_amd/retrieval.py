@@ -24,6 +24,12 @@ class ShapeCodeIndex:
         self.feats = torch.from_numpy(np.ascontiguousarray(feats)).to(self.device)
         self.labels = torch.tensor([self.label_to_id[o.label] for o in self.objects], dtype=torch.int32, device=self.device)
         self.sizes = torch.from_numpy(np.stack([np.asarray(o.size, dtype=np.float64) for o in self.objects])).to(self.device)
+        # model_ids[index.closest(...)] is the `model_jids` argument of the reference's computer_symmetry (scene_synthesis/utils.py:75:
+        # the parent directory name of raw_model_path); objects without a path are their own model
+        numbering = {}
+        keys = [("jid", p.split("/")[-2]) if isinstance(p, str) and p.count("/") >= 1 else ("row", i)
+                for i, p in enumerate(getattr(o, "raw_model_path", None) for o in self.objects)]
+        self.model_ids = torch.tensor([numbering.setdefault(k, len(numbering)) for k in keys], dtype=torch.int32, device=self.device)
 
     def __len__(self):
         return len(self.objects)

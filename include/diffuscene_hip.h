@@ -496,6 +496,34 @@ int dsc_retrieve_nearest_f32(const float* query_feats, const int32_t* query_labe
                              dsc_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Scene statistics after sampling: the box-level numbers of the reference's iou_states.txt (scripts/utils.py:559-747,
+ * computer_intersection / computer_symmetry) for `batch` scenes in two launches.  counts[b] (int32) objects of scene b are
+ * valid; rows at or beyond it are never read (they may hold NaN).  A count outside [0, nmax] is clamped into that range and
+ * counted by dsc_device_error_count.
+ * ------------------------------------------------------------------------------------------- */
+#define DSC_STATS_MAX_OBJECTS 160
+#define DSC_STATS_ONE_WAVE_MAX 32     /* nmax up to here: one-wave blocks; above: four waves */
+
+/* bounds[b][k] = <x1, y1, z1, x2, y2, z2>: min / max over the eight corners (+-sizes).dot(R) + translations with R of
+ * scene_synthesis/utils.py:48-53 (rotation about y by angles[b][k]); float64 arithmetic, rounded once to float32.
+ * translations, sizes (half extents) [batch][nmax][3], angles [batch][nmax].  Rows at or beyond counts[b] are written as zeros. */
+int dsc_box_bounds_f32(const float* translations, const float* sizes, const float* angles, const int32_t* counts,
+                       int32_t batch, int32_t nmax, float* bounds, dsc_stream_t stream);
+
+/* Per scene, over the pairs i < j < counts[b] of bounds [batch][nmax][6]: pairs with IoU > 0, pairs passing judge_if_symmetry
+ * (float64 on the float32 bounds; equal class id = first arg-max of class_scores [batch][nmax][num_classes], and equal
+ * model_ids [batch][nmax] unless NULL), float64 sums of the float32 per-pair IoU and overlap volume (fp32 arithmetic in the
+ * order of axis_aligned_bbox_overlaps_3d, scripts/utils.py:607-647) and of the float32 box volumes; class_counts
+ * [batch][num_classes]; pair_iou [batch][nmax][nmax] (strict upper triangle, the rest zero) or NULL.
+ * nmax <= DSC_STATS_MAX_OBJECTS.  One workgroup per scene; block_threads 0 (one wave up to DSC_STATS_ONE_WAVE_MAX objects, four
+ * above), 64 or 256.  The summation order depends on counts[b] alone: a scene's results are the same bits for every nmax and
+ * block size, and from run to run. */
+int dsc_scene_stats_f32(const float* bounds, const float* class_scores, const int32_t* model_ids, const int32_t* counts,
+                        int32_t batch, int32_t nmax, int32_t num_classes, int32_t block_threads,
+                        int32_t* num_intersecting, int32_t* num_symmetry, double* iou_sum, double* overlap_sum,
+                        double* volume_sum, int32_t* class_counts, float* pair_iou, dsc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training input pipeline: one launch turns B scenes of the HBM-resident cached dataset into the padded
  * (B, N, C) training batch -- RotationAugmentation (threed_front_dataset.py:313-371), Jitter (:559-567),
  * Scale_CosinAngle_ObjfeatsNorm (:481-513), Permutation (:570-584) and the Diffusion padding wrapper (:888-925) fused.
