@@ -215,6 +215,12 @@ SIGNATURES = {
     "dsc_p_sample_inpaint_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p,
                                            c_f32p, c_f32p, c_f32p, c_f32p] + [C.c_int32] * 7 + [C.c_void_p]),
     "dsc_ddim_inpaint_step_f32": (C.c_int, [c_f32p] * 5 + [c_i64p] * 4 + [c_f32p] * 10 + [C.c_int32] * 7 + [C.c_void_p]),
+    "dsc_masked_overwrite_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, c_i64p, c_f32p, c_f32p, C.c_int32, C.c_int64, C.c_int32,
+                                           C.c_void_p]),
+    "dsc_p_sample_masked_f32": (C.c_int, [c_f32p] * 5 + [C.c_void_p, c_i64p] + [c_f32p] * 8 + [C.c_int32] * 3 + [C.c_int64, C.c_int32,
+                                                                                                                  C.c_void_p]),
+    "dsc_ddim_masked_step_f32": (C.c_int, [c_f32p] * 5 + [C.c_void_p] + [c_i64p] * 3 + [c_f32p] * 10 + [C.c_int32] * 2 +
+                                 [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 _lib = None

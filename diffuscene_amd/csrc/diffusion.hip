@@ -244,6 +244,117 @@ __global__ __launch_bounds__(256) void ddim_inpaint_step_kernel(const float* xt,
     }
 }
 
+// Element-wise in-painting (p_sample_loop_masked, ddim_masked_loop): the set of given elements is a (b, n, c) byte mask, any non-zero
+// byte = given, instead of a row prefix.  known / noise / mask have x's shape.  Masked elements: x = sa[t] * known + sb[t] * noise;
+// the others are neither read nor written.
+__global__ __launch_bounds__(256) void masked_overwrite_kernel(float* __restrict__ x, const float* __restrict__ known,
+                                                              const float* __restrict__ noise, const uint8_t* __restrict__ mask,
+                                                              const int64_t* __restrict__ t, const float* __restrict__ sa,
+                                                              const float* __restrict__ sb, int64_t inner, int T) {
+    const int b = blockIdx.y;
+    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
+    const float a = sa[tv], s = sb[tv];
+    const int64_t base = (int64_t)b * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if (!mask[base + i]) continue;
+        const float p0 = a * known[base + i], p1 = s * noise[base + i];
+        x[base + i] = p0 + p1;
+    }
+}
+
+// Fused step of the masked loop: p_sample_kernel on the free elements; a given element (whose posterior step the next overwrite
+// would discard) gets what the loop writes there next -- q_sample(known, t - 1, noise_k) when t > 0, known itself when t == 0 (the
+// final select; noise_k is not read).  A given element reads mask, known and noise_k only; a free one mask, xt, mo and noise only:
+// an all-free launch moves p_sample_kernel's bytes plus one byte per element.  Same expressions, same rounding as p_sample_kernel and
+// masked_overwrite_kernel: bit-identical to their composition.
+__global__ __launch_bounds__(256) void p_sample_masked_kernel(const float* xt, const float* __restrict__ mo,
+                                                             const float* __restrict__ noise, const float* __restrict__ known,
+                                                             const float* __restrict__ noise_k, const uint8_t* __restrict__ mask,
+                                                             const int64_t* __restrict__ t,
+                                                             const float* __restrict__ ca, const float* __restrict__ cb,
+                                                             const float* __restrict__ c1, const float* __restrict__ c2,
+                                                             const float* __restrict__ sigma, const float* __restrict__ sa,
+                                                             const float* __restrict__ sb, float* out,   // out may alias xt
+                                                             int mean_type, int clip, int64_t inner, int T) {
+    const int b = blockIdx.y;
+    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float k1 = c1[tv], k2 = c2[tv];
+    const float sg = (tv != 0) ? sigma[tv] : 0.f;
+    const bool renoise = tv > 0;
+    const float a = renoise ? sa[tv - 1] : 0.f, s = renoise ? sb[tv - 1] : 0.f;
+    const int64_t base = (int64_t)b * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if (mask[base + i]) {
+            const float kv = known[base + i];
+            if (renoise) { const float p0 = a * kv, p1 = s * noise_k[base + i]; out[base + i] = p0 + p1; }
+            else out[base + i] = kv;
+            continue;
+        }
+        const float x = xt[base + i], m = mo[base + i];
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float m0 = k1 * x0, m1 = k2 * x;
+        const float mean = m0 + m1;
+        const float nz = sg * noise[base + i];
+        out[base + i] = mean + nz;
+    }
+}
+
+// Fused step of the strided (DDIM) masked loop: ddim_step_kernel on the free elements; a given element gets q_sample(known, t_next,
+// noise_k) when t_next >= 0, known itself on the last pair (neither noise nor noise_k is read there).  Reads per element as
+// p_sample_masked_kernel; index checks as ddim_inpaint_step_kernel.  Bit-identical to ddim_step_kernel followed by
+// masked_overwrite_kernel at t_next (or by the final select).
+__global__ __launch_bounds__(256) void ddim_masked_step_kernel(const float* xt, const float* __restrict__ mo,
+                                                              const float* __restrict__ noise, const float* __restrict__ known,
+                                                              const float* __restrict__ noise_k, const uint8_t* __restrict__ mask,
+                                                              const int64_t* __restrict__ step,
+                                                              const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
+                                                              const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
+                                                              const float* __restrict__ sigma, const float* __restrict__ ca,
+                                                              const float* __restrict__ cb, const float* __restrict__ ra,
+                                                              const float* __restrict__ rm, const float* __restrict__ sa,
+                                                              const float* __restrict__ sb, float* out,   // out may alias xt
+                                                              int mean_type, int64_t inner, int S, int T) {
+    const int b = blockIdx.y;
+    const bool first_all = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;           // one count per launch
+    const int64_t k = dsc_checked_index(step[0], S, first_all);
+    const int64_t tv = dsc_checked_index(times[k], T, first_all);
+    const int64_t tn_raw = times_next[k];
+    const bool last = tn_raw < 0;
+    const int64_t tn = last ? 0 : dsc_checked_index(tn_raw, T, first_all);
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float R = ra[tv], M = rm[tv];
+    const float an = sqrt_an[k], cn = cnoise[k], sg = sigma[k];
+    const float a = last ? 0.f : sa[tn], s = last ? 0.f : sb[tn];
+    const int64_t base = (int64_t)b * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if (mask[base + i]) {
+            const float kv = known[base + i];
+            if (!last) { const float p0 = a * kv, p1 = s * noise_k[base + i]; out[base + i] = p0 + p1; }
+            else out[base + i] = kv;
+            continue;
+        }
+        const float x = xt[base + i], m = mo[base + i];
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (last) { out[base + i] = x0; continue; }
+        float pn;
+        if (mean_type == DSC_MEAN_EPS) pn = m;
+        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
+        const float u0 = x0 * an, u1 = cn * pn;
+        const float u = u0 + u1;
+        const float nz = sg * noise[base + i];
+        out[base + i] = u + nz;
+    }
+}
+
 // Post-filter of generated scenes (reference delete_empty_from_network_samples, diffusion_scene_layout_ddpm.py:351-406): slot i
 // of a scene is dropped when its 'empty' logit (column empty_col) is >= 0.  The reference takes that decision from BATCH ROW 0
 // for every scene of the batch (:379, mode 0, kept as the drop-in default); mode 1 decides per scene, which is what batched
@@ -426,6 +537,59 @@ extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_ou
     hipLaunchKernelGGL(ddim_inpaint_step_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x_t, model_out, noise, partial, noise_p, counts, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
                        cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, n, pmax, c, num_steps, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_masked_overwrite_f32(float* x, const float* known, const float* noise, const uint8_t* mask, const int64_t* t,
+                                        const float* sqrt_ac, const float* sqrt_1mac, int32_t b, int64_t inner,
+                                        int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x || !known || !noise || !mask || !t || !sqrt_ac || !sqrt_1mac || b < 1 || inner < 1 || num_timesteps < 1) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(masked_overwrite_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x, known, noise, mask, t, sqrt_ac, sqrt_1mac, inner, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_p_sample_masked_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
+                                       const float* noise_k, const uint8_t* mask, const int64_t* t, const float* ca, const float* cb,
+                                       const float* coef1, const float* coef2, const float* sigma, const float* sqrt_ac,
+                                       const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip, int32_t b, int64_t inner,
+                                       int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !noise || !known || !noise_k || !mask || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
+        !out || b < 1 || inner < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(p_sample_masked_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
+                       mean_type, clip, inner, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
+                                        const float* noise_k, const uint8_t* mask, const int64_t* step, const int64_t* times,
+                                        const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise,
+                                        const float* sigma, const float* ca, const float* cb, const float* sqrt_recip_ac,
+                                        const float* sqrt_recipm1_ac, const float* sqrt_ac, const float* sqrt_1mac, float* out,
+                                        int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
+                                        dsc_stream_t stream) {
+    if (!x_t || !model_out || !noise || !known || !noise_k || !mask || !step || !times || !times_next || !sqrt_alpha_next ||
+        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || inner < 1 ||
+        num_steps < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_masked_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, noise, known, noise_k, mask, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
+                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, inner, num_steps, num_timesteps);
     DSC_LAUNCH_CHECK();
     return 0;
 }

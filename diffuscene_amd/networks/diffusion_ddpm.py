@@ -530,6 +530,86 @@ class GaussianDiffusion:
         assert img.shape == tuple(shape)
         return img
 
+    def _masked_inputs(self, shape, device, known, mask, what):
+        B, N, C = shape
+        if known is None or mask is None:
+            raise ValueError("%s needs known (B, N, C) and mask (B, N, C) or (B, N)" % what)
+        if not isinstance(known, torch.Tensor) or tuple(known.shape) != (B, N, C):
+            raise ValueError("known must be a (%d, %d, %d) tensor, got %s" % (B, N, C, tuple(getattr(known, "shape", ()))))
+        return known.to(device=device, dtype=torch.float32).contiguous(), ops.known_mask(mask, (B, N, C), device)
+
+    @torch.no_grad()
+    def p_sample_loop_masked(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
+                             keep_running=False, known=None, mask=None, graph=None):
+        """Element-wise in-painting in T steps.  ``known`` is (B, N, C) f32 in the network's encoding, ``mask`` (B, N, C) or (B, N) bool /
+        uint8 (ops.known_mask), non-zero = this element is given.  Scene b is the reference's p_sample_loop_complete (:447-476) on that
+        scene alone with its two torch.cat's replaced by a select: before the model call at step t,
+        x = where(mask, q_sample(known, t, fresh noise), x); after the p_sample at t == 0, x = where(mask, known, x).  Draw order: x_T
+        (B, N, C), then per step a known-draw noise_fn(size=(B, N, C)) -- full shape whatever the mask is -- followed by the p_sample draw
+        (B, N, C): the draws of p_sample_loop_complete_ragged at Pmax == N, so a mask of whole rows [0, counts[b]) returns what that loop
+        returns, bit for bit under the same seed.  An all-zero mask is plain generation on the main draws, an all-ones mask returns
+        ``known``.  This eager loop is built from the unfused pieces -- masked overwrite, p_sample, select; the graph path (the default,
+        by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B, N, C = shape
+        known, mask = self._masked_inputs(shape, device, known, mask, "p_sample_loop_masked")
+        total_steps = self._total_steps(keep_running)
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_masked_loop
+            return graph_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised, total_steps,
+                                     noise_fn, known, mask)
+        tb = self.tables(device)
+        img_t = noise_fn(size=shape, dtype=torch.float, device=device).clone()   # overwritten in place below
+        for t in reversed(range(0, total_steps)):
+            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
+            noise_k = noise_fn(size=shape, dtype=torch.float, device=device)
+            ops.masked_overwrite(img_t, known, noise_k.contiguous(), mask, t_, tb["sqrt_alphas_cumprod"],
+                                 tb["sqrt_one_minus_alphas_cumprod"])
+            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
+                                  condition_cross=condition_cross, noise_fn=noise_fn,
+                                  clip_denoised=clip_denoised, return_pred_xstart=False)
+        img_t = torch.where(mask != 0, known, img_t)
+        assert img_t.shape == tuple(shape)
+        return img_t
+
+    @torch.no_grad()
+    def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
+                         ddim_sampling_eta=0., known=None, mask=None, graph=None):
+        """Element-wise in-painting in S strided (DDIM) steps; ``known`` / ``mask`` as in p_sample_loop_masked.  Scene b is ddim_sample_loop
+        (reference :402-444) on that scene alone: before every model call at pair (t, t_next),
+        x = where(mask, q_sample(known, t, fresh noise), x); after the last pair, x = where(mask, known, x).  x_start is always clamped
+        to [-1, 1] (there is no ``clip_denoised``).  Draw order: that of ddim_complete_ragged_loop at Pmax == N -- x_T, then per pair a
+        known-draw (B, N, C), the model call and a main draw (B, N, C), the last pair without the main draw: 2 S draws -- so a mask of
+        whole rows [0, counts[b]) returns what that loop returns, bit for bit.  The eager loop is built from the unfused pieces; the
+        graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B, N, C = shape
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        known, mask = self._masked_inputs(shape, device, known, mask, "ddim_masked_loop")
+        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_ddim_masked_loop
+            return graph_ddim_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn, known, mask)
+        tb = self.tables(device)
+        dtab = self.ddim_tables(S, eta, device)
+        pairs = dtab[0]
+        step = torch.zeros((1,), dtype=torch.int64, device=device)
+        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
+        img = noise_fn(size=shape, dtype=torch.float, device=device).clone()     # overwritten in place below
+        for time, time_next in pairs:
+            noise_k = noise_fn(size=shape, dtype=torch.float, device=device)
+            ops.masked_overwrite(img, known, noise_k.contiguous(), mask, t_, tb["sqrt_alphas_cumprod"],
+                                 tb["sqrt_one_minus_alphas_cumprod"])
+            model_output = denoise_fn(img, t_, condition, condition_cross)
+            last = time_next < 0
+            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
+            img = self.ddim_step(img, model_output.contiguous(), noise.contiguous(), step, dtab)
+            if not last:
+                ops.ddim_advance(step, dtab[1], t_)
+        img = torch.where(mask != 0, known, img)
+        assert img.shape == tuple(shape)
+        return img
+
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
                           ddim_sampling_eta=0., input_boxes=None, graph=None):
@@ -778,6 +858,21 @@ class DiffusionPoint(nn.Module):
                                                         condition_cross=condition_cross, noise_fn=noise_fn,
                                                         sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
                                                         partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
+
+    def inpaint_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, clip_denoised=True,
+                        keep_running=False, known=None, mask=None, graph=None):
+        """Element-wise in-painting: the elements marked by ``mask`` are held at ``known`` (p_sample_loop_masked)."""
+        return self.diffusion.p_sample_loop_masked(self._denoise, shape=shape, device=device, condition=condition,
+                                                   condition_cross=condition_cross, noise_fn=noise_fn, clip_denoised=clip_denoised,
+                                                   keep_running=keep_running, known=known, mask=mask, graph=graph)
+
+    def inpaint_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, sampling_timesteps=50,
+                             ddim_sampling_eta=0., known=None, mask=None, graph=None):
+        """inpaint_samples in S strided steps (ddim_masked_loop)."""
+        return self.diffusion.ddim_masked_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                               condition_cross=condition_cross, noise_fn=noise_fn,
+                                               sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                               known=known, mask=mask, graph=graph)
 
     def arrange_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                              sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None):

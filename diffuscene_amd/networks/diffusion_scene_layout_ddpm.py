@@ -515,6 +515,118 @@ class DiffusionSceneLayout_DDPM(Module):
                               batch_seeds=batch_seeds)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
+    # ------------------------------------------------------------------------------------ element-wise in-painting
+    ATTRIBUTES = ("translations", "sizes", "angles", "class_labels", "objfeats")
+
+    def _attribute_channels(self, name):
+        """Channel range [lo, hi) of an attribute in a scene row, the slices of ``_split_boxes`` ('class_labels' with the 'empty' column)."""
+        tr, sz, bb, nc = self.translation_dim, self.size_dim, self.bbox_dim, self.class_dim
+        if name == "objfeats" and self.objfeat_dim <= 0:
+            raise ValueError("attributes: 'objfeats' on a model without object features (objfeat_dim = 0)")
+        spans = {"translations": (0, tr), "sizes": (tr, tr + sz), "angles": (tr + sz, bb), "class_labels": (bb, bb + nc),
+                 "objfeats": (bb + nc, bb + nc + self.objfeat_dim)}
+        if name not in spans:
+            raise ValueError("attributes: %r is not one of %s" % (name, self.ATTRIBUTES))
+        return spans[name]
+
+    def attribute_mask(self, rows, attributes, batch_size, num_points):
+        """The (B, N, C) bool mask (CPU) of ``inpaint_scene_batched`` that marks ``attributes`` -- a subset of ATTRIBUTES, mapped to the
+        channel ranges ``_split_boxes`` slices -- of the objects ``rows`` as given.  ``rows``: one count per scene (an int for all
+        scenes, a sequence or 1-d integer tensor of B counts: rows [0, count)), a sequence of B index lists, or a (B, N) bool tensor.
+        Masks combine with ``|``.  ValueError names the scene or argument."""
+        B, N, C = int(batch_size), int(num_points), int(self.config["point_dim"])
+        if isinstance(attributes, str):
+            attributes = (attributes,)
+        chan = torch.zeros(C, dtype=torch.bool)
+        for name in attributes:
+            lo, hi = self._attribute_channels(name)
+            if hi > C:
+                raise ValueError("attributes: %r spans channels [%d, %d) of a %d-channel model" % (name, lo, hi, C))
+            chan[lo:hi] = True
+        sel = torch.zeros((B, N), dtype=torch.bool)
+        if isinstance(rows, torch.Tensor) and rows.dtype == torch.bool:
+            if tuple(rows.shape) != (B, N):
+                raise ValueError("rows: a bool tensor must be (%d, %d), got %s" % (B, N, tuple(rows.shape)))
+            sel = rows.to("cpu").clone()
+        else:
+            if isinstance(rows, torch.Tensor):
+                if rows.dim() > 1 or rows.dtype.is_floating_point:
+                    raise ValueError("rows: an integer tensor must hold one count per scene, got %s %s" % (tuple(rows.shape), rows.dtype))
+                rows = rows.tolist()
+            if isinstance(rows, int) and not isinstance(rows, bool):
+                rows = [rows] * B
+            if not isinstance(rows, (list, tuple)) or len(rows) != B:
+                raise ValueError("rows: one count or index list per scene (%d scenes) or a (%d, %d) bool tensor" % (B, B, N))
+            for b, r in enumerate(rows):
+                if isinstance(r, torch.Tensor) and r.dim() == 1 and not r.dtype.is_floating_point and r.dtype != torch.bool:
+                    r = r.tolist()
+                if isinstance(r, (list, tuple)):
+                    for i in r:
+                        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < N:
+                            raise ValueError("scene %d: row index %r outside [0, %d)" % (b, i, N))
+                        sel[b, i] = True
+                elif isinstance(r, int) and not isinstance(r, bool):
+                    if not 0 <= r <= N:
+                        raise ValueError("scene %d: row count %r outside [0, %d]" % (b, r, N))
+                    sel[b, :r] = True
+                else:
+                    raise ValueError("scene %d: rows must be a count or a list of indices, got %r" % (b, r))
+        return sel[:, :, None] & chan[None, None, :]
+
+    @torch.no_grad()
+    def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
+                              clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
+        """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
+        scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
+        always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
+        the network's encoding, or a list of B (n_b <= num_points, point_dim) tensors, padded with zeros -- padded rows are never
+        known.  ``known_mask``: (B, N, C) or (B, N) bool / uint8, e.g. from ``attribute_mask``.  Works on the ordinary unconditional,
+        instance- or text-conditioned model (``text`` as in ``sample``); ``room_partial_condition`` / ``room_arrange_condition`` models
+        are refused, their condition tensors already encode a prefix / a sub-shape.  Returns a list of B dicts; given elements are
+        filtered like any others (a row whose given 'empty' logit is >= 0 is dropped)."""
+        from .. import ops
+        if self.room_partial_condition or self.room_arrange_condition:
+            raise ValueError("inpaint_scene_batched: a room_partial_condition / room_arrange_condition model conditions on a prefix / a "
+                             "sub-shape of the scene (complete_scene_batched, arrange_scene_batched)")
+        device = room_mask.device
+        if batch_size is None:
+            batch_size = len(boxes) if isinstance(boxes, (list, tuple)) else int(boxes.shape[0])
+        B, N, C = int(batch_size), int(num_points), int(point_dim)
+        if isinstance(boxes, (list, tuple)):
+            if len(boxes) != B:
+                raise ValueError("boxes lists %d scenes for a batch of %d" % (len(boxes), B))
+            known = torch.zeros((B, N, C), dtype=torch.float32, device=device)
+            valid = torch.zeros((B, N), dtype=torch.bool)
+            for b, sc in enumerate(boxes):
+                if not isinstance(sc, torch.Tensor) or sc.dim() != 2 or sc.shape[1] != C or sc.shape[0] > N:
+                    raise ValueError("scene %d: boxes must be a (n <= %d, %d) tensor, got %s" % (b, N, C, tuple(getattr(sc, "shape", ()))))
+                known[b, :sc.shape[0]] = sc.to(device=device, dtype=torch.float32)
+                valid[b, :sc.shape[0]] = True
+        else:
+            if not isinstance(boxes, torch.Tensor) or tuple(boxes.shape) != (B, N, C):
+                raise ValueError("boxes must be a (%d, %d, %d) tensor or a list of %d (n, %d) tensors, got %s"
+                                 % (B, N, C, B, C, tuple(getattr(boxes, "shape", ()))))
+            known = boxes.to(device=device, dtype=torch.float32).contiguous()
+            valid = None
+        try:
+            mask = ops.known_mask(known_mask, (B, N, C), "cpu" if valid is not None else device)
+        except ValueError as e:
+            raise ValueError("known_mask: %s" % e) from None
+        if valid is not None:
+            mask = (mask * valid[:, :, None].to(torch.uint8)).to(device).contiguous()
+        if sampling_timesteps is not None:
+            S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+        torch.randn((B, N, C))                                     # CPU draw kept, as in sample (:232)
+        condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
+        print('scene in-painting sampling')
+        if sampling_timesteps is not None:
+            samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
+                                                          known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta)
+        else:
+            samples = self.diffusion.inpaint_samples((B, N, C), device, condition=condition, condition_cross=condition_cross,
+                                                     clip_denoised=clip_denoised, known=known, mask=mask)
+        return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
+
     @torch.no_grad()
     def delete_empty_boxes(self, samples_dict, device="cpu", keep_empty=False):
         cl = samples_dict["class_labels"].detach().to("cpu")

@@ -541,6 +541,95 @@ def ddim_inpaint_step(x_t, model_out, noise, partial, noise_p, counts, step, tim
     return out
 
 
+def known_mask(mask, shape, device):
+    """The element-wise "given" mask of the masked (in-painting) kernels as a contiguous uint8 (B, N, C) tensor on ``device``.
+    ``mask``: bool or uint8, (B, N, C) -- one flag per element -- or (B, N) -- whole rows; any non-zero byte means given.  A uint8
+    (B, N, C) tensor already on the device is taken as it is.  ValueError on any other dtype or shape."""
+    b, n, c = (int(v) for v in shape)
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError("mask must be a bool / uint8 tensor of shape (%d, %d, %d) or (%d, %d), got %s" % (b, n, c, b, n, type(mask).__name__))
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be bool or uint8, got %s" % mask.dtype)
+    if tuple(mask.shape) == (b, n):
+        mask = mask[:, :, None].expand(b, n, c)
+    elif tuple(mask.shape) != (b, n, c):
+        raise ValueError("mask must be (%d, %d, %d) or (%d, %d), got %s" % (b, n, c, b, n, tuple(mask.shape)))
+    if mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8)
+    return mask.to(device).contiguous()
+
+
+def _masked_args(x, known, noise_k, mask):
+    _c(x, "x"); _c(known, "known"); _c(noise_k, "known noise"); _dev(mask, "mask", torch.uint8)
+    if not mask.is_contiguous():
+        raise RuntimeError("diffuscene_amd: mask must be contiguous")
+    if known.shape != x.shape or noise_k.shape != x.shape or mask.shape != x.shape or x.dim() < 2:
+        raise RuntimeError("diffuscene_amd: known / noise / mask must have the shape of x %s, got %s / %s / %s"
+                           % (tuple(x.shape), tuple(known.shape), tuple(noise_k.shape), tuple(mask.shape)))
+    b = x.shape[0]
+    return b, x.numel() // b
+
+
+def masked_overwrite(x, known, noise, mask, t, sqrt_ac, sqrt_1mac):
+    """x[i] <- q_sample(known, t, noise)[i] where mask[i] != 0 (uint8, x's shape: ops.known_mask); the rest of x is untouched.  See the C
+    header."""
+    b, inner = _masked_args(x, known, noise, mask)
+    _scene_t(t, b)
+    _lib.check(_lib.fn("dsc_masked_overwrite_f32")(x.data_ptr(), known.data_ptr(), noise.data_ptr(), mask.data_ptr(), t.data_ptr(),
+                                                   sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), b, inner, _table_rows(sqrt_ac, sqrt_1mac),
+                                                   stream_ptr()), "dsc_masked_overwrite_f32")
+    return x
+
+
+def p_sample_masked(x_t, model_out, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, mean_type, clip,
+                    out=None):
+    """Fused step of the masked loop: p_sample on the free elements; the given ones get the re-noising of step t - 1 (t > 0) or
+    ``known`` itself (t == 0; ``noise_k`` is not read there).  See the C header."""
+    _c(model_out, "model_out"); _c(noise, "noise")
+    b, inner = _masked_args(x_t, known, noise_k, mask)
+    _scene_t(t, b)
+    if out is None:
+        out = torch.empty_like(x_t)
+    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
+        raise RuntimeError("diffuscene_amd: p_sample_masked operands of different shapes")
+    _lib.check(_lib.fn("dsc_p_sample_masked_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
+                                                  noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(),
+                                                  ca.data_ptr() if ca is not None else None,
+                                                  cb.data_ptr() if cb is not None else None,
+                                                  coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), sqrt_ac.data_ptr(),
+                                                  sqrt_1mac.data_ptr(), out.data_ptr(), mean_type, 1 if clip else 0, b, inner,
+                                                  _table_rows(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac), stream_ptr()),
+               "dsc_p_sample_masked_f32")
+    return out
+
+
+def ddim_masked_step(x_t, model_out, noise, known, noise_k, mask, step, times, times_next, coef, ca, cb, sqrt_recip_ac,
+                     sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, mean_type, out=None):
+    """Fused step of the strided (DDIM) masked loop: ddim_step on the free elements; the given ones get the re-noising at
+    ``times_next[step]`` or, on the last pair, ``known`` itself (``noise`` and ``noise_k`` are not read there).  Tables as ddim_step.
+    See the C header."""
+    _c(model_out, "model_out"); _c(noise, "noise")
+    b, inner = _masked_args(x_t, known, noise_k, mask)
+    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
+    S = times.numel()
+    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
+    if out is None:
+        out = torch.empty_like(x_t)
+    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
+        raise RuntimeError("diffuscene_amd: ddim_masked_step operands of different shapes")
+    _lib.check(_lib.fn("dsc_ddim_masked_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
+                                                   noise_k.data_ptr(), mask.data_ptr(), step.data_ptr(), times.data_ptr(),
+                                                   times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
+                                                   ca.data_ptr() if ca is not None else None,
+                                                   cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
+                                                   sqrt_recipm1_ac.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
+                                                   out.data_ptr(), mean_type, b, inner, S,
+                                                   _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac),
+                                                   stream_ptr()), "dsc_ddim_masked_step_f32")
+    return out
+
+
 # ---------------------------------------------------------------------------------- training (backward) kernels
 
 _scratch = {}

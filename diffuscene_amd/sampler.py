@@ -12,6 +12,9 @@ ragged overwrite at times[0], then S - 1 replays of [plan run, main draw k, part
 advance] and one replay of the draw-free final step.  Draw order (eager and captured): x_T, then per pair a partial draw (B, Pmax, C),
 the model call and a main draw (B, N, C); the last pair makes the partial draw only -- 2 S draws.  Strided re-arrangement is
 _DDIMGraph on the sub-shape.
+Element-wise in-painting (_MaskedGraph, _DDIMMaskedGraph: p_sample_loop_masked / ddim_masked_loop) is the two completion graphs with
+the row prefix replaced by a (B, N, C) byte mask and full-shape known-draws: the same draw shift, the fused dsc_p_sample_masked_f32 /
+dsc_ddim_masked_step_f32, one graph per shape for every mask.
 """
 import torch
 
@@ -693,6 +696,282 @@ def graph_ddim_complete_ragged_loop(diff, denoise_fn, shape, device, condition, 
             out = g.run(x_T, dtab, partial_boxes, counts)
         from ._lib import check_indices
         check_indices("graph_ddim_complete_ragged_loop")
+        return out
+
+
+class _MaskedGraph:
+    """The captured masked (element-wise in-painting) loop (p_sample_loop_masked): _RaggedCompleteGraph with the fused masked step.
+    ``graph``: plan run, the main draw of t, the known-draw of t - 1, the fused update (dsc_p_sample_masked_f32: posterior step on the
+    free elements, the given ones re-noised for the next model call) and the timestep decrement, replayed total_steps - 1 times;
+    ``final``: plan run, the main draw and the fused update at t == 0 (given elements set to ``known``, no known-draw) -- so the loop
+    draws exactly what the eager one draws, in its order.  The first overwrite, at t = total_steps - 1, is one standalone draw and
+    launch in ``run``.  ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 live in buffers of this object, captured by pointer and
+    refreshed in place: one graph serves every mask."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False):
+        B, N, C = shape
+        self.shape = shape
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        self.tb = tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        sigma = diff._sigma(tb)
+        mean_type = _MEAN[diff.model_mean_type]
+        sa, sb = tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"]
+        k1, k2 = tb["posterior_mean_coef1"], tb["posterior_mean_coef2"]
+        self.x = torch.empty(shape, device=device, dtype=torch.float32)
+        self.t = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.known = torch.zeros(shape, device=device, dtype=torch.float32)
+        self.mask = torch.zeros(shape, device=device, dtype=torch.uint8)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.kdraw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((diff.num_timesteps + 1,) + tuple(shape), device=device) if replay else None
+        self.knoise_buf = torch.zeros((diff.num_timesteps,) + tuple(shape), device=device) if replay else None
+        xv = self.x.view(B * N, C)
+
+        def draw(buf, counter):
+            if not self.replay:
+                return torch.randn(shape, dtype=torch.float, device=device)
+            n = buf.index_select(0, counter)[0]
+            ops.add_scalar_i64(counter, 1)
+            return n
+
+        def step(final):
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            noise = draw(self.noise_buf, self.draw)
+            nk = self.known if final else draw(self.knoise_buf, self.kdraw)          # not read at t == 0
+            ops.p_sample_masked(self.x, plan.out.view(B, N, C), noise, self.known, nk, self.mask, self.t, ca, cb, k1, k2, sigma, sa, sb,
+                                mean_type, clip_denoised, out=self.x)
+            if not final:
+                ops.add_scalar_i64(self.t, -1)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  The mask is all zero
+        # and t goes 1 -> 0: every index of the warm-up is in range.
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x.normal_()
+        self.t.fill_(1)
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in (False, True):
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            step(False)
+        self.final = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.final, pool=self.graph.pool()):
+            step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+        self.t.fill_(0)
+
+    def run(self, x_T, total_steps, known, mask, noise_buffer=None, known_noise=None):
+        self.check_current()
+        self.x.copy_(x_T)
+        self.t.fill_(total_steps - 1)
+        self.known.copy_(known)                 # in place: the graphs hold these pointers
+        self.mask.copy_(mask)
+        if self.replay:
+            self.noise_buf[:noise_buffer.shape[0]].copy_(noise_buffer)
+            self.knoise_buf[:known_noise.shape[0]].copy_(known_noise)
+            self.draw.fill_(1)                                  # draw 0 was x_T
+            self.kdraw.fill_(1)                                 # known-draw 0 feeds the standalone overwrite below
+        nk = self.knoise_buf[0] if self.replay else torch.randn(self.shape, dtype=torch.float, device=self.x.device)
+        ops.masked_overwrite(self.x, self.known, nk, self.mask, self.t, self.tb["sqrt_alphas_cumprod"],
+                             self.tb["sqrt_one_minus_alphas_cumprod"])
+        for _ in range(total_steps - 1):
+            self.graph.replay()
+        self.final.replay()
+        out = self.x.clone()
+        self.t.fill_(0)                         # a valid row for a replay too many (see _StepGraph.run)
+        return out
+
+
+def _masked_replay_check(noise_fn, shape, n_main, n_known, what):
+    if noise_fn.partial_buffer is None or noise_fn.buffer.shape[0] < n_main or noise_fn.partial_buffer.shape[0] < n_known \
+            or tuple(noise_fn.partial_buffer.shape[1:]) != tuple(shape) or tuple(noise_fn.buffer.shape[1:]) != tuple(shape):
+        raise ValueError("%s replays %d main draws and %d known-draws, all of shape %s" % (what, n_main, n_known, tuple(shape)))
+
+
+def graph_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps, noise_fn=torch.randn,
+                      known=None, mask=None):
+    """p_sample_loop_masked as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order, the
+    same generator state afterwards).  ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 (ops.known_mask) are copied into the graph's
+    own buffers: the cache key holds the shape, not the mask."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay:
+            _masked_replay_check(noise_fn, shape, total_steps + 1, total_steps, "the masked loop")
+        key = ("masked", id(model), tuple(shape), str(device), bool(clip_denoised), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
+               None if condition_cross is None else tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _MaskedGraph(diff, model, tuple(shape), device, condition, condition_cross, clip_denoised, replay)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], total_steps, known, mask, noise_fn.buffer[:total_steps + 1],
+                        noise_fn.partial_buffer[:total_steps])
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, total_steps, known, mask)
+        from ._lib import check_indices
+        check_indices("graph_masked_loop")
+        return out
+
+
+class _DDIMMaskedGraph:
+    """The captured strided masked loop (ddim_masked_loop): _DDIMCompleteGraph with the fused masked step.  ``graph`` (only when
+    S > 1): plan run, main draw k, the known-draw of pair k + 1, the fused update (dsc_ddim_masked_step_f32) and the advance kernel,
+    replayed S - 1 times; ``final``: plan run and the draw-free fused step of the last pair (x_start on the free elements, ``known`` on
+    the given ones), replayed once from ``graph``'s pool.  The first overwrite, at times[0], is one standalone draw and launch in
+    ``run``.  The tables, the step counter, ``known`` and ``mask`` live in buffers of this object, captured by pointer and refreshed in
+    place: one graph serves every eta and every mask."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False):
+        B, N, C = shape
+        self.shape, self.S = shape, S
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        self.tb = tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        ra, rm = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
+        sa, sb = tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"]
+        mean_type = _MEAN[diff.model_mean_type]
+        self.x = torch.empty(shape, device=device, dtype=torch.float32)
+        self.t = torch.zeros((B,), device=device, dtype=torch.int64)
+        self.step = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.times = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.times_next = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.coef = torch.zeros((3, S), device=device, dtype=torch.float32)
+        self.known = torch.zeros(shape, device=device, dtype=torch.float32)
+        self.mask = torch.zeros(shape, device=device, dtype=torch.uint8)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.kdraw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((S,) + tuple(shape), device=device) if replay else None      # x_T, then S - 1 main draws
+        self.knoise_buf = torch.zeros((S,) + tuple(shape), device=device) if replay else None     # one known-draw per pair
+        xv = self.x.view(B * N, C)
+
+        def draw(buf, counter):
+            if not self.replay:
+                return torch.randn(shape, dtype=torch.float, device=device)
+            n = buf.index_select(0, counter)[0]
+            ops.add_scalar_i64(counter, 1)
+            return n
+
+        def step(final):
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            noise = self.x if final else draw(self.noise_buf, self.draw)             # neither is read on the last pair
+            nk = self.known if final else draw(self.knoise_buf, self.kdraw)
+            ops.ddim_masked_step(self.x, plan.out.view(B, N, C), noise, self.known, nk, self.mask, self.step, self.times,
+                                 self.times_next, self.coef, ca, cb, ra, rm, sa, sb, mean_type, out=self.x)
+            if not final:
+                ops.ddim_advance(self.step, self.times, self.t)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  Tables, mask and the step
+        # counter are all zero: every index of the warm-up is in range (see _DDIMCompleteGraph).
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x.normal_()
+        kinds = ([False] if S > 1 else []) + [True]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in kinds:
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = None
+        if S > 1:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                step(False)
+        self.final = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.final, pool=self.graph.pool() if self.graph is not None else None):
+            step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+        self.step.zero_()
+
+    def run(self, x_T, dtab, known, mask, noise_buffer=None, known_noise=None):
+        pairs, times, times_next, coef = dtab
+        assert len(pairs) == self.S
+        self.check_current()
+        self.times.copy_(times)                 # in place: the graphs hold these pointers
+        self.times_next.copy_(times_next)
+        self.coef.copy_(coef)
+        self.x.copy_(x_T)
+        self.step.zero_()
+        self.t.fill_(pairs[0][0])
+        self.known.copy_(known)
+        self.mask.copy_(mask)
+        if self.replay:
+            self.noise_buf.copy_(noise_buffer[:self.S])
+            self.knoise_buf.copy_(known_noise[:self.S])
+            self.draw.fill_(1)                                  # draw 0 was x_T
+            self.kdraw.fill_(1)                                 # known-draw 0 feeds the standalone overwrite below
+        nk = self.knoise_buf[0] if self.replay else torch.randn(self.shape, dtype=torch.float, device=self.x.device)
+        ops.masked_overwrite(self.x, self.known, nk, self.mask, self.t, self.tb["sqrt_alphas_cumprod"],
+                             self.tb["sqrt_one_minus_alphas_cumprod"])
+        for _ in range(self.S - 1):
+            self.graph.replay()
+        self.final.replay()
+        return self.x.clone()
+
+
+def graph_ddim_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta, noise_fn=torch.randn,
+                           known=None, mask=None):
+    """ddim_masked_loop as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order, the same
+    generator state afterwards).  The cache key holds the shape and S; it holds neither eta nor the mask."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    S = int(sampling_timesteps)
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay:
+            _masked_replay_check(noise_fn, shape, S, S, "the strided masked loop")
+        dtab = diff.ddim_tables(S, eta, device)
+        key = (("ddim_masked", S), id(model), tuple(shape), str(device), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
+               None if condition_cross is None else tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _DDIMMaskedGraph(diff, model, tuple(shape), device, condition, condition_cross, S, replay)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], dtab, known, mask, noise_fn.buffer, noise_fn.partial_buffer)
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, dtab, known, mask)
+        from ._lib import check_indices
+        check_indices("graph_ddim_masked_loop")
         return out
 
 

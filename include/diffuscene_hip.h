@@ -360,6 +360,39 @@ int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_out, const fl
                               int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_steps, int32_t num_timesteps,
                               dsc_stream_t stream);
 
+/* Element-wise in-painting: the given elements of a scene are marked by a byte mask (b, n, c) -- any non-zero byte = given -- instead
+ * of a row prefix.  known / noise / mask have the shape of x (b scenes of `inner` elements).  Where mask[i] != 0:
+ *   x[i] = sqrt_ac[t] * known[i] + sqrt_1mac[t] * noise[i]      (t per scene, clamped and counted as everywhere)
+ * the other elements of x are neither read nor written, and known / noise are not read there. */
+int dsc_masked_overwrite_f32(float* x, const float* known, const float* noise, const uint8_t* mask, const int64_t* t,
+                             const float* sqrt_ac, const float* sqrt_1mac, int32_t b, int64_t inner, int32_t num_timesteps,
+                             dsc_stream_t stream);
+
+/* Fused step of the masked T-step loop, one launch after the model call.  Free elements (mask[i] == 0): dsc_p_sample_f32.  Given ones:
+ *   t >  0: out = sqrt_ac[t-1] * known + sqrt_1mac[t-1] * noise_k   (the overwrite that precedes the next model call)
+ *   t == 0: out = known                                             (the final select; noise_k is not read)
+ * A given element reads mask, known and noise_k only; a free one mask, x_t, model_out and noise only.  All operands (b, inner).
+ * Bit-identical to dsc_p_sample_f32 followed by dsc_masked_overwrite_f32 at t - 1 (or by the select).  out may alias x_t. */
+int dsc_p_sample_masked_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
+                            const float* noise_k, const uint8_t* mask, const int64_t* t, const float* ca, const float* cb,
+                            const float* coef1, const float* coef2, const float* sigma, const float* sqrt_ac,
+                            const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip, int32_t b, int64_t inner,
+                            int32_t num_timesteps, dsc_stream_t stream);
+
+/* Fused step of the strided (DDIM) masked loop.  k, t = times[k], t_next = times_next[k] as dsc_ddim_step_f32.  Free elements:
+ * dsc_ddim_step_f32.  Given ones:
+ *   t_next >= 0: out = sqrt_ac[t_next] * known + sqrt_1mac[t_next] * noise_k
+ *   t_next <  0: out = known                                        (the final select; noise and noise_k are not read)
+ * Reads per element as dsc_p_sample_masked_f32; the step index, times[k] and times_next[k] (where non-negative) are clamped into
+ * range and counted by dsc_device_error_count, as in dsc_ddim_inpaint_step_f32.  Bit-identical to dsc_ddim_step_f32 followed by
+ * dsc_masked_overwrite_f32 at t_next (or by the select).  out may alias x_t. */
+int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
+                             const float* noise_k, const uint8_t* mask, const int64_t* step, const int64_t* times,
+                             const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise, const float* sigma,
+                             const float* ca, const float* cb, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
+                             const float* sqrt_ac, const float* sqrt_1mac, float* out, int32_t mean_type,
+                             int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: hand-written backward of the denoiser (the reference relies on torch autograd through
  * denoise_net.py; train_on_batch, diffusion_scene_layout_ddpm.py:456-473).  Input gradients
