@@ -110,6 +110,21 @@ class ActFn(Function):
         return ops.activation_bwd(x, dy.contiguous(), ctx.act), None
 
 
+class SceneGateFn(Function):
+    """y[b] = keep[b] ? x[b] : 0 per scene (dsc_scene_gate_f32), the same select on the incoming gradient: a dropped scene neither
+    reads nor propagates -- its gradient is exactly zero whatever arrives."""
+
+    @staticmethod
+    def forward(ctx, x, keep):
+        ctx.save_for_backward(keep)
+        return ops.scene_gate(x.contiguous(), keep)
+
+    @staticmethod
+    def backward(ctx, dy):
+        keep, = ctx.saved_tensors
+        return ops.scene_gate(dy.contiguous(), keep), None
+
+
 class WeightStandardizeAllFn(Function):
     """All weight-standardised conv weights of the network in one batched launch (forward and backward)."""
 

@@ -355,6 +355,115 @@ __global__ __launch_bounds__(256) void ddim_masked_step_kernel(const float* xt, 
     }
 }
 
+// Classifier-free guidance (p_sample_loop_guided / ddim_guided_loop).  model_out holds 2 b scenes: rows [0, b) are the denoiser on the
+// text features (c), rows [b, 2 b) the denoiser on the null condition (u), both on the same x_t.  Scene i is guided with its own
+// scale w = scale[i], read through a pointer:  m = u + w * (c - u), the difference, the product and the sum each rounded on its own.
+// w == 0 gives u + 0 * (c - u) = u, w == 1 the conditional output up to rounding.
+__device__ __forceinline__ float cfg_mix(float c, float u, float w) {
+    const float d = c - u;
+    const float p = w * d;
+    return u + p;
+}
+
+// The unfused form: m (b, inner) from model_out (2 b, inner) and scale (b,).
+__global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restrict__ mo, const float* __restrict__ scale,
+                                                         float* __restrict__ out, int64_t inner) {
+    const int b = blockIdx.y;
+    const float w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x)
+        out[base + i] = cfg_mix(mo[base + i], mo[half + base + i], w);
+}
+
+// p_sample_kernel with m computed in registers from the two halves of mo.  x_dup (may be NULL): a second copy of the new x, so that a
+// captured loop can keep x as one (2 b, inner) buffer with both halves current.  At t == 0 the noise is not read (p_sample_kernel
+// adds 0 * noise there).  Same expressions, same rounding as cfg_combine_kernel followed by p_sample_kernel: equal to their composition
+// on finite noise (torch.equal; the sign of a zero result may differ at t == 0).
+__global__ __launch_bounds__(256) void p_sample_cfg_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ scale,
+                                                          const float* __restrict__ noise, const int64_t* __restrict__ t,
+                                                          const float* __restrict__ ca, const float* __restrict__ cb,
+                                                          const float* __restrict__ c1, const float* __restrict__ c2,
+                                                          const float* __restrict__ sigma, float* out,   // out may alias xt
+                                                          float* __restrict__ x_dup, float* __restrict__ x0_out, int mean_type, int clip,
+                                                          int64_t inner, int T) {
+    const int b = blockIdx.y;
+    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float k1 = c1[tv], k2 = c2[tv];
+    const float sg = sigma[tv];
+    const float w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float m0 = k1 * x0, m1 = k2 * x;
+        const float mean = m0 + m1;
+        float y = mean;                           // t == 0: sigma is forced to 0 and the noise is not read
+        if (tv != 0) { const float nz = sg * noise[base + i]; y = mean + nz; }
+        out[base + i] = y;
+        if (x_dup) x_dup[base + i] = y;
+        if (x0_out) x0_out[base + i] = x0;
+    }
+}
+
+// ddim_step_kernel with m computed in registers from the two halves of mo; x_dup as in p_sample_cfg_kernel.  On the last pair the
+// noise is not read.  Bit-identical to cfg_combine_kernel followed by ddim_step_kernel.
+__global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ scale,
+                                                           const float* __restrict__ noise, const int64_t* __restrict__ step,
+                                                           const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
+                                                           const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
+                                                           const float* __restrict__ sigma, const float* __restrict__ ca,
+                                                           const float* __restrict__ cb, const float* __restrict__ ra,
+                                                           const float* __restrict__ rm, float* out,   // out may alias xt
+                                                           float* __restrict__ x_dup, float* __restrict__ x0_out, int mean_type,
+                                                           int64_t inner, int S, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;               // one count per launch
+    const int64_t k = dsc_checked_index(step[0], S, first);
+    const int64_t tv = dsc_checked_index(times[k], T, first);
+    const bool last = times_next[k] < 0;
+    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    const float R = ra[tv], M = rm[tv];
+    const float an = sqrt_an[k], c = cnoise[k], sg = sigma[k];
+    const float w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
+        float x0;
+        if (mean_type == DSC_MEAN_X0) x0 = m;
+        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        if (x0_out) x0_out[base + i] = x0;
+        float y = x0;
+        if (!last) {
+            float pn;
+            if (mean_type == DSC_MEAN_EPS) pn = m;
+            else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
+            const float u0 = x0 * an, u1 = c * pn;
+            const float u = u0 + u1;
+            const float nz = sg * noise[base + i];
+            y = u + nz;
+        }
+        out[base + i] = y;
+        if (x_dup) x_dup[base + i] = y;
+    }
+}
+
+// Per-scene gate of the text-condition dropout (text_drop_prob): y[b, :] = keep[b] ? x[b, :] : 0 -- a select, a dropped scene's x is
+// not read.  Forward on the text features, backward on their incoming gradient.  y may alias x.
+__global__ __launch_bounds__(256) void scene_gate_kernel(const float* x, const uint8_t* __restrict__ keep, float* y, int64_t inner) {
+    const int b = blockIdx.y;
+    const bool k = keep[b] != 0;
+    const int64_t base = (int64_t)b * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x)
+        y[base + i] = k ? x[base + i] : 0.0f;
+}
+
 // Post-filter of generated scenes (reference delete_empty_from_network_samples, diffusion_scene_layout_ddpm.py:351-406): slot i
 // of a scene is dropped when its 'empty' logit (column empty_col) is >= 0.  The reference takes that decision from BATCH ROW 0
 // for every scene of the batch (:379, mode 0, kept as the drop-in default); mode 1 decides per scene, which is what batched
@@ -590,6 +699,63 @@ extern "C" int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out
     hipLaunchKernelGGL(ddim_masked_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x_t, model_out, noise, known, noise_k, mask, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
                        cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, inner, num_steps, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_cfg_combine_f32(const float* model_out, const float* scale, float* out, int32_t b, int64_t inner,
+                                   dsc_stream_t stream) {
+    if (!model_out || !scale || !out || b < 1 || inner < 1) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(cfg_combine_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream), model_out, scale,
+                       out, inner);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_p_sample_cfg_f32(const float* x_t, const float* model_out, const float* scale, const float* noise, const int64_t* t,
+                                    const float* ca, const float* cb, const float* coef1, const float* coef2, const float* sigma,
+                                    float* out, float* x_dup, float* x0_out, int32_t mean_type, int32_t clip, int32_t b,
+                                    int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !scale || !noise || !t || !coef1 || !coef2 || !sigma || !out || b < 1 || inner < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(p_sample_cfg_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, scale, noise, t, ca, cb, coef1, coef2, sigma, out, x_dup, x0_out, mean_type, clip, inner,
+                       num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
+                                     const int64_t* step, const int64_t* times, const int64_t* times_next,
+                                     const float* sqrt_alpha_next, const float* c_noise, const float* sigma, const float* ca,
+                                     const float* cb, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float* out,
+                                     float* x_dup, float* x0_out, int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps,
+                                     int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !scale || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
+        !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
+    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, scale, noise, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca, cb,
+                       sqrt_recip_ac, sqrt_recipm1_ac, out, x_dup, x0_out, mean_type, inner, num_steps, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y, int32_t b, int64_t inner, dsc_stream_t stream) {
+    if (!x || !keep || !y || b < 1 || inner < 1) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(scene_gate_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream), x, keep, y, inner);
     DSC_LAUNCH_CHECK();
     return 0;
 }

@@ -408,6 +408,86 @@ class GaussianDiffusion:
         assert img.shape == tuple(shape)
         return imgs if return_all_timesteps else img
 
+    # ------------------------------------------------------------------ classifier-free guidance
+    def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
+        """(condition at 2 B, condition_cross at 2 B = cat([cross, zeros]), scale (B,) f32 on the device) of a guided loop."""
+        B = shape[0]
+        if condition_cross is None or not isinstance(condition_cross, torch.Tensor) or condition_cross.dim() != 3 \
+                or condition_cross.shape[0] != B:
+            raise ValueError("%s needs condition_cross (B, L, text_embed_dim): guidance contrasts the text features with the null "
+                             "condition (all zeros)" % what)
+        scale = ops.guidance_scales(guidance_scale, B, device)
+        cross2 = torch.cat([condition_cross, torch.zeros_like(condition_cross)], dim=0).contiguous()
+        cond2 = condition
+        if condition is not None:
+            # a stride-0 (per-slot) condition stays per-slot at 2 B; any other is repeated for the null half
+            cond2 = condition[:1].expand(2 * B, -1, -1) if condition.stride(0) == 0 else torch.cat([condition, condition], dim=0).contiguous()
+        return cond2, cross2, scale
+
+    @torch.no_grad()
+    def p_sample_loop_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
+                             clip_denoised=True, keep_running=False, graph=None):
+        """Classifier-free guidance in T steps.  Scene b is the reference's p_sample_loop (:355-371) with
+        m = u + w[b] * (c - u) in place of the model output inside p_mean_variance: c the denoiser on (x, t, condition, condition_cross),
+        u the denoiser on (x, t, condition, 0) -- the null condition is condition_cross == 0, the features AFTER fc_text_f --, the
+        difference, the product and the sum each rounded on its own.  eps, x0 and v are linear in each other given x_t, so guiding the
+        raw output is the same guidance under all three mean types.  ``guidance_scale``: a float or B per-scene values
+        (ops.guidance_scales); 1 is the conditional model up to rounding, 0 the null-conditioned one.  Draws: exactly those of
+        p_sample_loop at batch B, in its order; both halves of the 2 B model call see the same x_t.  This eager loop is built from the
+        unfused pieces -- the denoiser at 2 B, cfg_combine, p_sample; the graph path (the default, by the rules of p_sample_loop)
+        replays one captured step whose update is the fused dsc_p_sample_cfg_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B = shape[0]
+        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "p_sample_loop_guided")
+        total_steps = self._total_steps(keep_running)
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_guided_loop
+            return graph_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, clip_denoised, total_steps, noise_fn)
+        tb = self.tables(device)
+        ca, cb = self._coeffs(tb)
+        img_t = noise_fn(size=shape, dtype=torch.float, device=device)
+        for t in reversed(range(0, total_steps)):
+            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
+            model_output = denoise_fn(torch.cat([img_t, img_t], dim=0), torch.cat([t_, t_]), cond2, cross2)
+            m = ops.cfg_combine(model_output.contiguous(), scale)
+            noise = noise_fn(size=shape, dtype=torch.float, device=device)
+            img_t = ops.p_sample(img_t.contiguous(), m, noise.contiguous(), t_, ca, cb, tb["posterior_mean_coef1"],
+                                 tb["posterior_mean_coef2"], self._sigma(tb), _MEAN[self.model_mean_type], clip_denoised)
+        assert img_t.shape == tuple(shape)
+        return img_t
+
+    @torch.no_grad()
+    def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
+                         sampling_timesteps=50, ddim_sampling_eta=0., graph=None):
+        """Classifier-free guidance in S strided (DDIM) steps: scene b is the reference's ddim_sample_loop (:402-444) with the guided
+        output m of p_sample_loop_guided in place of the model output inside model_predictions.  x_start is always clamped to [-1, 1].
+        Draws: exactly those of ddim_sample_loop at batch B (x_T, then one per pair except the last).  The eager loop is built from the
+        unfused pieces (the denoiser at 2 B, cfg_combine, ddim_step); the graph path replays one captured step whose update is the fused
+        dsc_ddim_cfg_step_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        B = shape[0]
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "ddim_guided_loop")
+        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_ddim_guided_loop
+            return graph_ddim_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, S, eta, noise_fn)
+        dtab = self.ddim_tables(S, eta, device)
+        pairs = dtab[0]
+        step = torch.zeros((1,), dtype=torch.int64, device=device)
+        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
+        img = noise_fn(size=shape, dtype=torch.float, device=device)
+        for time, time_next in pairs:
+            model_output = denoise_fn(torch.cat([img, img], dim=0), torch.cat([t_, t_]), cond2, cross2)
+            m = ops.cfg_combine(model_output.contiguous(), scale)
+            last = time_next < 0
+            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
+            img = self.ddim_step(img.contiguous(), m, noise.contiguous(), step, dtab)
+            if not last:
+                ops.ddim_advance(step, dtab[1], t_)
+        assert img.shape == tuple(shape)
+        return img
+
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
@@ -835,6 +915,20 @@ class DiffusionPoint(nn.Module):
                                                condition_cross=condition_cross, noise_fn=noise_fn, clip_denoised=clip_denoised,
                                                sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
                                                return_all_timesteps=return_all_timesteps, graph=graph)
+
+    def gen_samples_guided(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
+                           clip_denoised=True, keep_running=False, graph=None):
+        """gen_samples under classifier-free guidance (p_sample_loop_guided)."""
+        return self.diffusion.p_sample_loop_guided(self._denoise, shape=shape, device=device, condition=condition,
+                                                   condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
+                                                   clip_denoised=clip_denoised, keep_running=keep_running, graph=graph)
+
+    def gen_samples_guided_ddim(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
+                                sampling_timesteps=50, ddim_sampling_eta=0., graph=None):
+        """gen_samples_guided in S strided steps (ddim_guided_loop)."""
+        return self.diffusion.ddim_guided_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                               condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
+                                               sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph)
 
     def complete_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                          clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):

@@ -94,6 +94,11 @@ class DiffusionSceneLayout_DDPM(Module):
         else:
             raise NotImplementedError()
         self.diffusion = DiffusionPoint(denoise_net=denoise_net, config=config, **config["diffusion_kwargs"])
+        # ``text_drop_prob`` (new key, default 0.0 = reference behaviour): in training mode every scene's text features are replaced by
+        # the null condition (zeros after fc_text_f) with this probability -- what classifier-free guidance (``guidance_scale``) needs
+        self.text_drop_prob = float(config.get("text_drop_prob", 0.0))
+        if not 0.0 <= self.text_drop_prob <= 1.0:
+            raise ValueError("text_drop_prob must lie in [0, 1], got %r" % (config.get("text_drop_prob"),))
         self.n_classes = n_classes
         self.config = config
 
@@ -236,18 +241,48 @@ class DiffusionSceneLayout_DDPM(Module):
             target = torch.cat([target[:, :, 0:tr], target[:, :, tr + sz:bb]], dim=-1).contiguous()
         condition_cross = self._text_condition(sample_params.get("description"), sample_params.get("desc_emb"), device,
                                                desc_bert=sample_params.get("desc_bert"))
+        keep = self._text_keep(sample_params, batch_size, device) if condition_cross is not None else None
+        if keep is not None:
+            condition_cross = self._gate_text(condition_cross, keep)
         return target, condition, condition_cross
+
+    def _text_keep(self, sample_params, batch_size, device):
+        """The (B,) bool keep mask of the text-condition dropout, or None when nothing is dropped.  ``sample_params["_cond_keep"]``
+        overrides the draw (goldens); otherwise, with text_drop_prob = p > 0 in training mode, ONE draw u = torch.rand((B,)) is made --
+        after the text features, before the t and noise draws of the loss -- and keep = u >= p.  p == 0 or eval mode: no draw."""
+        keep = sample_params.get("_cond_keep")
+        if keep is not None:
+            keep = torch.as_tensor(keep)
+            if keep.dtype != torch.bool or tuple(keep.shape) != (batch_size,):
+                raise ValueError("_cond_keep must be a (%d,) bool tensor, got %s %s" % (batch_size, tuple(keep.shape), keep.dtype))
+            return keep.to(device)
+        p = getattr(self, "text_drop_prob", 0.0)
+        if p > 0.0 and self.training:
+            return torch.rand((batch_size,), device=device) >= p
+        return None
+
+    def _gate_text(self, condition_cross, keep):
+        """Rows of the dropped scenes replaced by zeros -- a select (dsc_scene_gate_f32), forward and on the gradient: a dropped scene
+        neither reads nor propagates its features."""
+        from ..autograd_ops import SceneGateFn
+        return SceneGateFn.apply(condition_cross, keep)
 
     # ------------------------------------------------------------------------------------ sampling
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
                input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
-               sampling_timesteps=None, ddim_sampling_eta=0.0):
+               sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
         defines no strided completion or re-arrangement, so this drop-in method refuses the combination; strided inpainting lives on
         the scene-level entry points (``complete_scene_batched``, ``arrange_scene_batched``, ``complete_scene``, ``arrange_scene`` with
-        ``sampling_timesteps``), over ``complete_samples_ragged_ddim`` / ``arrange_samples_ddim``."""
+        ``sampling_timesteps``), over ``complete_samples_ragged_ddim`` / ``arrange_samples_ddim``.
+        ``guidance_scale`` (None: the plain conditional model, this method as it was): a float or ``batch_size`` per-scene values w, the
+        classifier-free guidance scale of a text-conditioned model -- every step uses u + w (c - u), c the denoiser on the text features
+        and u the denoiser on the null condition (condition_cross == 0) (``gen_samples_guided`` / ``gen_samples_guided_ddim`` with
+        ``sampling_timesteps``).  Generation only; needs ``text``."""
+        if guidance_scale is not None:
+            self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
                                       "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
@@ -273,6 +308,19 @@ class DiffusionSceneLayout_DDPM(Module):
                                                    condition_cross=condition_cross, clip_denoised=clip_denoised,
                                                    partial_boxes=partial_boxes)
         print('unconditional / conditional generation sampling')
+        if guidance_scale is not None:
+            if condition_cross is None or condition_cross.dim() != 3:
+                raise ValueError("guidance_scale: the text encoder must give (B, L, text_embed_dim) features, got %s (the null "
+                                 "condition is defined on the cross-attention features)"
+                                 % (None if condition_cross is None else tuple(condition_cross.shape),))
+            from .. import ops
+            scale = ops.guidance_scales(guidance_scale, batch_size, "cpu")     # checked on the host; the loop uploads it
+            if sampling_timesteps is not None:
+                return self.diffusion.gen_samples_guided_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
+                                                              guidance_scale=scale, sampling_timesteps=sampling_timesteps,
+                                                              ddim_sampling_eta=ddim_sampling_eta)
+            return self.diffusion.gen_samples_guided(noise.shape, device, condition=condition, condition_cross=condition_cross,
+                                                     guidance_scale=scale, clip_denoised=clip_denoised)
         if sampling_timesteps is not None:
             return self.diffusion.gen_samples_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                    clip_denoised=clip_denoised, sampling_timesteps=sampling_timesteps,
@@ -283,18 +331,38 @@ class DiffusionSceneLayout_DDPM(Module):
         return self.diffusion.gen_samples(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                           clip_denoised=clip_denoised)
 
+    def _check_guidance(self, text, partial_boxes=None, input_boxes=None, ret_traj=False):
+        """The refusals of ``guidance_scale``, before anything is computed or drawn."""
+        if not self.text_condition:
+            raise ValueError("guidance_scale needs a text-conditioned model (text_condition: true): guidance contrasts the text "
+                             "condition with the null condition")
+        if text is None:
+            raise ValueError("guidance_scale needs text=...: there is nothing to guide towards without a prompt")
+        if partial_boxes is not None or input_boxes is not None:
+            raise ValueError("guidance_scale is defined for generation only, not for completion or re-arrangement")
+        if ret_traj:
+            raise ValueError("guidance_scale: the guided loops return the final scenes only (ret_traj is not supported)")
+
     @torch.no_grad()
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
                         clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                        ddim_sampling_eta=0.0):
+                        ddim_sampling_eta=0.0, guidance_scale=None):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
-                              clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta))
+                              clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
+                              **_guidance_kwargs(guidance_scale))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def generate_layout_progressive(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False,
                                     ddim=False, clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False,
-                                    num_step=100):
+                                    num_step=100, guidance_scale=None):
+        """``guidance_scale``: the guided loops keep no trajectory, so the guided call returns the final scenes under the key of the
+        last step, ``{0: dict}``."""
+        if guidance_scale is not None:
+            self._check_guidance(text)
+            samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ddim=ddim, clip_denoised=clip_denoised,
+                                  batch_seeds=batch_seeds, guidance_scale=guidance_scale)
+            return {0: self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)}
         traj = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
                            clip_denoised=clip_denoised, batch_seeds=batch_seeds, freq=num_step)[1:]
         return {num_step * i: self.delete_empty_from_network_samples(s, device=device, keep_empty=keep_empty)
@@ -414,10 +482,13 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
-                                batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
-        """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own."""
+                                batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
+                                guidance_scale=None):
+        """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own.
+        ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``)."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
-                              batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta))
+                              batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
+                              **_guidance_kwargs(guidance_scale))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
@@ -642,6 +713,11 @@ def _ddim_kwargs(sampling_timesteps, ddim_sampling_eta):
     if sampling_timesteps is None:
         return {}
     return dict(sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+
+
+def _guidance_kwargs(guidance_scale):
+    """The guidance keyword ``sample`` receives: none at all without guidance, so that call stays what it was."""
+    return {} if guidance_scale is None else dict(guidance_scale=guidance_scale)
 
 
 def train_on_batch(model, optimizer, sample_params, config):

@@ -5,6 +5,7 @@ passes raw device pointers + the current torch stream to libdiffuscene_hip.so an
 tensor.  There is no CPU path: a CPU tensor raises.
 """
 import ctypes as C
+import numbers
 
 import torch
 
@@ -627,6 +628,138 @@ def ddim_masked_step(x_t, model_out, noise, known, noise_k, mask, step, times, t
                                                    out.data_ptr(), mean_type, b, inner, S,
                                                    _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac),
                                                    stream_ptr()), "dsc_ddim_masked_step_f32")
+    return out
+
+
+# ---------------------------------------------------------------------------------- classifier-free guidance
+
+def guidance_scales(scale, b, device):
+    """The per-scene guidance scales of the guided kernels as a contiguous (b,) f32 tensor on ``device``.  ``scale``: a float (every
+    scene), or a length-b sequence / 1-d tensor (one scale per scene).  ValueError on NaN / inf, on a wrong length and on anything that
+    is not a number."""
+    b = int(b)
+    bad = "guidance_scale must be a number or a sequence of %d numbers, got %r" % (b, scale)
+    if isinstance(scale, torch.Tensor):
+        if scale.dim() > 1 or scale.dtype == torch.bool:
+            raise ValueError("guidance_scale: a tensor must be a scalar or (%d,) of numbers, got %s %s" % (b, tuple(scale.shape), scale.dtype))
+        scale = scale.tolist()
+    if isinstance(scale, (bool, str, bytes)) or scale is None:
+        raise ValueError(bad)
+    if isinstance(scale, numbers.Real):
+        host = [float(scale)] * b
+    else:
+        try:
+            host = [float(v) for v in scale]
+        except (TypeError, ValueError):
+            raise ValueError(bad) from None
+    if len(host) != b:
+        raise ValueError("guidance_scale has %d entries for a batch of %d scenes" % (len(host), b))
+    for i, v in enumerate(host):
+        if v != v or v in (float("inf"), float("-inf")):
+            raise ValueError("guidance_scale: scene %d: %r is not finite" % (i, v))
+    return torch.tensor(host, dtype=torch.float32).to(device).contiguous()
+
+
+def _cfg_args(x_t, model_out, scale):
+    """(b, inner) of a guided launch: model_out is (2 b, ...) with the conditional half first, scale a contiguous (b,) f32 device tensor."""
+    _c(model_out, "model_out"); _c(scale, "scale")
+    b = x_t.shape[0]
+    if model_out.dim() != x_t.dim() or model_out.shape[0] != 2 * b or tuple(model_out.shape[1:]) != tuple(x_t.shape[1:]):
+        raise RuntimeError("diffuscene_amd: model_out must be (2 * %d,) + %s (conditional half first), got %s"
+                           % (b, tuple(x_t.shape[1:]), tuple(model_out.shape)))
+    if tuple(scale.shape) != (b,):
+        raise RuntimeError("diffuscene_amd: scale must be a (%d,) f32 tensor (ops.guidance_scales), got %s" % (b, tuple(scale.shape)))
+    return b, x_t.numel() // b
+
+
+def _cfg_dup(x_dup, x_t, out):
+    if x_dup is None:
+        return None
+    _c(x_dup, "x_dup")
+    if x_dup.shape != x_t.shape:
+        raise RuntimeError("diffuscene_amd: x_dup must have the shape of x_t %s, got %s" % (tuple(x_t.shape), tuple(x_dup.shape)))
+    n = x_t.numel() * 4
+    for other in (x_t, out):
+        if x_dup.data_ptr() < other.data_ptr() + n and other.data_ptr() < x_dup.data_ptr() + n:
+            raise RuntimeError("diffuscene_amd: x_dup must not overlap x_t / out")
+    return x_dup.data_ptr()
+
+
+def cfg_combine(model_out, scale, out=None):
+    """m = u + scale[b] * (c - u) from model_out (2 B, ...) = [c; u] -> (B, ...).  See the C header."""
+    _c(model_out, "model_out")
+    if model_out.shape[0] % 2 or model_out.shape[0] < 2:
+        raise RuntimeError("diffuscene_amd: model_out must hold 2 B scenes, got %s" % (tuple(model_out.shape),))
+    b = model_out.shape[0] // 2
+    if out is None:
+        out = torch.empty((b,) + tuple(model_out.shape[1:]), device=model_out.device, dtype=torch.float32)
+    _c(out, "out")
+    b, inner = _cfg_args(out, model_out, scale)
+    _lib.check(_lib.fn("dsc_cfg_combine_f32")(model_out.data_ptr(), scale.data_ptr(), out.data_ptr(), b, inner, stream_ptr()),
+               "dsc_cfg_combine_f32")
+    return out
+
+
+def p_sample_cfg(x_t, model_out, scale, noise, t, ca, cb, coef1, coef2, sigma, mean_type, clip, out=None, x_dup=None, x0_out=None):
+    """p_sample on the guided model output, one launch: model_out (2 B, N, C) = [c; u], scale (B,) f32 (ops.guidance_scales); ``x_dup``
+    receives a second copy of the result.  Bit-identical to cfg_combine followed by p_sample.  See the C header."""
+    _c(x_t, "x_t"); _c(noise, "noise")
+    b, inner = _cfg_args(x_t, model_out, scale)
+    _scene_t(t, b)
+    if out is None:
+        out = torch.empty_like(x_t)
+    if noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous() or (x0_out is not None and x0_out.shape != x_t.shape):
+        raise RuntimeError("diffuscene_amd: p_sample_cfg operands of different shapes")
+    _lib.check(_lib.fn("dsc_p_sample_cfg_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(), t.data_ptr(),
+                                               ca.data_ptr() if ca is not None else None,
+                                               cb.data_ptr() if cb is not None else None,
+                                               coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), out.data_ptr(),
+                                               _cfg_dup(x_dup, x_t, out), _c(x0_out, "x0_out").data_ptr() if x0_out is not None else None,
+                                               mean_type, 1 if clip else 0, b, inner, _table_rows(ca, cb, coef1, coef2, sigma),
+                                               stream_ptr()), "dsc_p_sample_cfg_f32")
+    return out
+
+
+def ddim_cfg_step(x_t, model_out, scale, noise, step, times, times_next, coef, ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, mean_type,
+                  out=None, x_dup=None, x0_out=None):
+    """ddim_step on the guided model output, one launch; operands as p_sample_cfg, tables as ddim_step (``noise`` is not read on the
+    final pair).  Bit-identical to cfg_combine followed by ddim_step.  See the C header."""
+    _c(x_t, "x_t"); _c(noise, "noise")
+    b, inner = _cfg_args(x_t, model_out, scale)
+    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
+    S = times.numel()
+    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
+    if out is None:
+        out = torch.empty_like(x_t)
+    if noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous() or (x0_out is not None and x0_out.shape != x_t.shape):
+        raise RuntimeError("diffuscene_amd: ddim_cfg_step operands of different shapes")
+    _lib.check(_lib.fn("dsc_ddim_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
+                                                step.data_ptr(), times.data_ptr(), times_next.data_ptr(), coef[0].data_ptr(),
+                                                coef[1].data_ptr(), coef[2].data_ptr(), ca.data_ptr() if ca is not None else None,
+                                                cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
+                                                sqrt_recipm1_ac.data_ptr(), out.data_ptr(), _cfg_dup(x_dup, x_t, out),
+                                                _c(x0_out, "x0_out").data_ptr() if x0_out is not None else None, mean_type, b, inner, S,
+                                                _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), stream_ptr()),
+               "dsc_ddim_cfg_step_f32")
+    return out
+
+
+def scene_gate(x, keep, out=None):
+    """y[b] = keep[b] ? x[b] : 0 for a (B, ...) f32 tensor and a (B,) bool / uint8 device tensor; a dropped scene is not read.  See the C
+    header."""
+    _c(x, "x")
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8):
+        raise RuntimeError("diffuscene_amd: keep must be a bool / uint8 tensor on the HIP device")
+    b = x.shape[0]
+    if tuple(keep.shape) != (b,):
+        raise RuntimeError("diffuscene_amd: keep must be (%d,), got %s" % (b, tuple(keep.shape)))
+    keep = keep.contiguous()
+    kb = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(_lib.fn("dsc_scene_gate_f32")(x.data_ptr(), kb.data_ptr(), _c(out, "out").data_ptr(), b, x.numel() // b, stream_ptr()),
+               "dsc_scene_gate_f32")
     return out
 
 

@@ -15,6 +15,8 @@ _DDIMGraph on the sub-shape.
 Element-wise in-painting (_MaskedGraph, _DDIMMaskedGraph: p_sample_loop_masked / ddim_masked_loop) is the two completion graphs with
 the row prefix replaced by a (B, N, C) byte mask and full-shape known-draws: the same draw shift, the fused dsc_p_sample_masked_f32 /
 dsc_ddim_masked_step_f32, one graph per shape for every mask.
+Classifier-free guidance (_GuidedStepGraph, _DDIMGuidedGraph: p_sample_loop_guided / ddim_guided_loop) is _StepGraph / _DDIMGraph on a plan
+at 2 B (text features | zeros) with the fused dsc_p_sample_cfg_f32 / dsc_ddim_cfg_step_f32; the per-scene scales live in a device buffer.
 """
 import torch
 
@@ -972,6 +974,261 @@ def graph_ddim_masked_loop(diff, denoise_fn, shape, device, condition, condition
             out = g.run(x_T, dtab, known, mask)
         from ._lib import check_indices
         check_indices("graph_ddim_masked_loop")
+        return out
+
+
+class _GuidedStepGraph:
+    """The captured guided T-step loop (p_sample_loop_guided): _StepGraph with a plan prepared at 2 B -- rows [0, B) fed the text
+    features, rows [B, 2 B) zeros --, the timestep vector filled for 2 B rows and the fused update dsc_p_sample_cfg_f32, which reads
+    both halves of the plan's output and writes the new x to BOTH halves of ``x`` (2 B, N, C) (its x_dup pointer), so the copy into
+    the plan's input stays one node.  The (B,) scale vector is a buffer of this object, captured by pointer and refreshed in place by
+    ``run``: one graph serves every per-scene mix of scales.  ``fused=False`` captures the same step from the unfused kernels
+    (cfg_combine, p_sample, a copy into the null half) -- the comparison of tools/bench_cfg.py."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
+        B, N, C = shape
+        self.shape, self.fused = shape, fused
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(2 * B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        sigma = diff._sigma(tb)
+        mean_type = _MEAN[diff.model_mean_type]
+        k1, k2 = tb["posterior_mean_coef1"], tb["posterior_mean_coef2"]
+        self.x2 = torch.empty((2 * B, N, C), device=device, dtype=torch.float32)
+        self.x, self.x_null = self.x2[:B], self.x2[B:]
+        self.t = torch.zeros((2 * B,), device=device, dtype=torch.int64)
+        self.scale = torch.ones((B,), device=device, dtype=torch.float32)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((diff.num_timesteps + 1,) + tuple(shape), device=device) if replay else None
+        self.m = None if fused else torch.empty(shape, device=device, dtype=torch.float32)
+        xv = self.x2.view(2 * B * N, C)
+        tB = self.t[:B]
+
+        def step():
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            if self.replay:
+                noise = self.noise_buf.index_select(0, self.draw)[0]
+                ops.add_scalar_i64(self.draw, 1)
+            else:
+                noise = torch.randn(shape, dtype=torch.float, device=device)
+            mo = plan.out.view(2 * B, N, C)
+            if fused:
+                ops.p_sample_cfg(self.x, mo, self.scale, noise, tB, ca, cb, k1, k2, sigma, mean_type, clip_denoised, out=self.x,
+                                 x_dup=self.x_null)
+            else:
+                ops.cfg_combine(mo, self.scale, out=self.m)
+                ops.p_sample(self.x, self.m, noise, tB, ca, cb, k1, k2, sigma, mean_type, clip_denoised, out=self.x)
+                self.x_null.copy_(self.x)
+            ops.add_scalar_i64(self.t, -1)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph)
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x2.normal_()
+        self.t.fill_(1)
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            step()
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            step()
+        torch.cuda.set_rng_state(rng_state, device)
+        self.t.fill_(0)
+
+    def replay_steps(self, n=1):
+        self.check_current()
+        for _ in range(n):
+            self.graph.replay()
+
+    def run(self, x_T, total_steps, scale, noise_buffer=None):
+        self.check_current()
+        self.x.copy_(x_T)
+        self.x_null.copy_(x_T)
+        self.t.fill_(total_steps - 1)
+        self.scale.copy_(scale)                 # in place: the graph holds this pointer
+        if self.replay:
+            self.noise_buf[:noise_buffer.shape[0]].copy_(noise_buffer)
+            self.draw.fill_(1)                                  # draw 0 was x_T
+        for _ in range(total_steps):
+            self.graph.replay()
+        out = self.x.clone()
+        self.t.fill_(0)                         # a valid row for a replay too many (see _StepGraph.run)
+        return out
+
+
+def graph_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, clip_denoised, total_steps,
+                      noise_fn=torch.randn, fused=True):
+    """p_sample_loop_guided as a replayed hipGraph; bit-identical to the eager loop (same expressions, same draws in the same order, the
+    same generator state afterwards).  ``condition`` / ``condition_cross`` arrive at 2 B (GaussianDiffusion._guided_inputs), ``scale`` is
+    the (B,) f32 device vector of ops.guidance_scales: the cache key holds the shape, not the scales."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay and (noise_fn.buffer.shape[0] < total_steps + 1 or tuple(noise_fn.buffer.shape[1:]) != tuple(shape)):
+            raise ValueError("the guided loop replays %d draws of shape %s" % (total_steps + 1, tuple(shape)))
+        key = (("guided", bool(fused)), id(model), tuple(shape), str(device), bool(clip_denoised), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0), tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _GuidedStepGraph(diff, model, tuple(shape), device, condition, condition_cross, clip_denoised, replay, fused)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(2 * B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], total_steps, scale, noise_fn.buffer[:total_steps + 1])
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, total_steps, scale)
+        from ._lib import check_indices
+        check_indices("graph_guided_loop")
+        return out
+
+
+class _DDIMGuidedGraph:
+    """The captured guided strided loop (ddim_guided_loop): _DDIMGraph with the 2 B plan, the 2 B timestep vector and the fused update
+    dsc_ddim_cfg_step_f32 of _GuidedStepGraph.  Tables, step counter and the scale vector live in buffers of this object, captured by
+    pointer and refreshed in place: one graph serves every eta and every mix of scales.  ``fused=False``: the unfused kernels."""
+
+    check_current = _StepGraph.check_current
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False, fused=True):
+        B, N, C = shape
+        self.shape, self.S, self.fused = shape, S, fused
+        eng = model.engine(device)
+        use_table = diff.num_timesteps <= eng.time_table.shape[0]
+        self.plans = [eng.prepare(2 * B, N, condition, condition_cross, time_table=use_table)]
+        self.plan = plan = self.plans[0]
+        tb = diff.tables(device)
+        ca, cb = diff._coeffs(tb)
+        ra, rm = tb["sqrt_recip_alphas_cumprod"], tb["sqrt_recipm1_alphas_cumprod"]
+        mean_type = _MEAN[diff.model_mean_type]
+        self.x2 = torch.empty((2 * B, N, C), device=device, dtype=torch.float32)
+        self.x, self.x_null = self.x2[:B], self.x2[B:]
+        self.t = torch.zeros((2 * B,), device=device, dtype=torch.int64)
+        self.scale = torch.ones((B,), device=device, dtype=torch.float32)
+        self.step = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.times = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.times_next = torch.zeros((S,), device=device, dtype=torch.int64)
+        self.coef = torch.zeros((3, S), device=device, dtype=torch.float32)
+        self.replay = replay
+        self.draw = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.noise_buf = torch.zeros((S,) + tuple(shape), device=device) if replay else None    # x_T, then S - 1 step draws
+        self.m = None if fused else torch.empty(shape, device=device, dtype=torch.float32)
+        xv = self.x2.view(2 * B * N, C)
+
+        def step(final):
+            plan.x_in.copy_(xv)
+            plan.t_in.copy_(self.t)
+            plan.run()
+            if final:
+                noise = self.x                                   # not read on the last pair
+            elif self.replay:
+                noise = self.noise_buf.index_select(0, self.draw)[0]
+                ops.add_scalar_i64(self.draw, 1)
+            else:
+                noise = torch.randn(shape, dtype=torch.float, device=device)
+            mo = plan.out.view(2 * B, N, C)
+            if fused:
+                ops.ddim_cfg_step(self.x, mo, self.scale, noise, self.step, self.times, self.times_next, self.coef, ca, cb, ra, rm,
+                                  mean_type, out=self.x, x_dup=self.x_null)
+            else:
+                ops.cfg_combine(mo, self.scale, out=self.m)
+                ops.ddim_step(self.x, self.m, noise, self.step, self.times, self.times_next, self.coef, ca, cb, ra, rm, mean_type,
+                              out=self.x)
+                self.x_null.copy_(self.x)
+            if not final:
+                ops.ddim_advance(self.step, self.times, self.t)
+
+        # warm-up on a side stream, then capture; the caller's device RNG state is put back (see _StepGraph).  With all-zero tables
+        # every index of the warm-up is in range (see _DDIMGraph).
+        rng_state = torch.cuda.get_rng_state(device)
+        self.x2.normal_()
+        kinds = ([False] if S > 1 else []) + [True]
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            for final in kinds:
+                step(final)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = None
+        if S > 1:
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                step(False)
+        self.final = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.final, pool=self.graph.pool() if self.graph is not None else None):
+            step(True)
+        torch.cuda.set_rng_state(rng_state, device)
+        self.step.zero_()
+
+    def run(self, x_T, dtab, scale, noise_buffer=None):
+        pairs, times, times_next, coef = dtab
+        assert len(pairs) == self.S
+        self.check_current()
+        self.times.copy_(times)                 # in place: the graphs hold these pointers
+        self.times_next.copy_(times_next)
+        self.coef.copy_(coef)
+        self.scale.copy_(scale)
+        self.x.copy_(x_T)
+        self.x_null.copy_(x_T)
+        self.step.zero_()
+        self.t.fill_(pairs[0][0])
+        if self.replay:
+            self.noise_buf.copy_(noise_buffer[:self.S])
+            self.draw.fill_(1)                                  # draw 0 was x_T
+        for _ in range(self.S - 1):
+            self.graph.replay()
+        self.final.replay()
+        return self.x.clone()
+
+
+def graph_ddim_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, sampling_timesteps, eta,
+                           noise_fn=torch.randn, fused=True):
+    """ddim_guided_loop as replayed hipGraphs; bit-identical to the eager loop.  The cache key holds the shape and S; it holds neither
+    eta nor the scales."""
+    model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
+    if not isinstance(model, Unet1D):
+        raise RuntimeError("graph sampling needs DiffusionPoint._denoise over a diffuscene_amd Unet1D")
+    device = torch.device(device)
+    B, N, C = shape
+    S = int(sampling_timesteps)
+    with torch.no_grad():
+        replay = isinstance(noise_fn, NoiseReplay)
+        if replay and (noise_fn.buffer.shape[0] < S or tuple(noise_fn.buffer.shape[1:]) != tuple(shape)):
+            raise ValueError("the guided strided loop replays %d draws of shape %s" % (S, tuple(shape)))
+        dtab = diff.ddim_tables(S, eta, device)
+        key = (("ddim_guided", S, bool(fused)), id(model), tuple(shape), str(device), diff.model_mean_type, replay,
+               None if condition is None else (tuple(condition.shape), condition.stride(0) == 0), tuple(condition_cross.shape))
+        g = diff._graphs.get(key)
+        eng = model.engine(device)
+        eng.params_moved()
+        if g is None or g.plan is not eng.plans.get(_plan_key(g)):
+            g = _DDIMGuidedGraph(diff, model, tuple(shape), device, condition, condition_cross, S, replay, fused)
+            diff._graphs = {key: g}           # one live graph per diffusion object
+        else:
+            eng.prepare(2 * B, N, condition, condition_cross, time_table=g.plan.time_table)
+        if replay:
+            out = g.run(noise_fn.buffer[0], dtab, scale, noise_fn.buffer)
+        else:
+            x_T = torch.randn(shape, dtype=torch.float, device=device)
+            out = g.run(x_T, dtab, scale)
+        from ._lib import check_indices
+        check_indices("graph_ddim_guided_loop")
         return out
 
 

@@ -393,6 +393,38 @@ int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out, const flo
                              const float* sqrt_ac, const float* sqrt_1mac, float* out, int32_t mean_type,
                              int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream);
 
+/* Classifier-free guidance on the text path.  model_out is (2 b, inner): scenes [0, b) are the denoiser on the text features (c),
+ * scenes [b, 2 b) the denoiser on the null condition (condition_cross == 0) (u), both on the same x_t.  scale is a (b,) f32 DEVICE
+ * vector, read through the pointer by every launch (one captured graph serves every per-scene mix of scales):
+ *   m = u + scale[i] * (c - u)        difference, product and sum each rounded on its own
+ * eps, x0 and v are linear in each other given x_t, so guiding the raw model output is the same guidance under all three mean types.
+ * dsc_cfg_combine_f32 writes m to out (b, inner): the unfused form. */
+int dsc_cfg_combine_f32(const float* model_out, const float* scale, float* out, int32_t b, int64_t inner, dsc_stream_t stream);
+
+/* dsc_p_sample_f32 with m computed in registers from the two halves of model_out (2 b, inner); x_t / noise / out / x0_out are
+ * (b, inner).  x_dup (may be NULL): the new x is written there too, so a captured loop keeps x as one (2 b, inner) buffer with both
+ * halves current.  At t == 0 the noise is not read.  Equal to dsc_cfg_combine_f32 followed by dsc_p_sample_f32 on finite noise (same
+ * expressions, same rounding; at t == 0 that kernel adds 0 * noise, which can only change the sign of a zero).  out may alias x_t;
+ * x_dup must not. */
+int dsc_p_sample_cfg_f32(const float* x_t, const float* model_out, const float* scale, const float* noise, const int64_t* t,
+                         const float* ca, const float* cb, const float* coef1, const float* coef2, const float* sigma,
+                         float* out, float* x_dup /* may be NULL */, float* x0_out /* may be NULL */, int32_t mean_type,
+                         int32_t clip, int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream);
+
+/* dsc_ddim_step_f32 with the same change (tables, step counter and clamping as there; noise is not read on the last pair).
+ * Bit-identical to dsc_cfg_combine_f32 followed by dsc_ddim_step_f32.  out may alias x_t; x_dup must not. */
+int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise, const int64_t* step,
+                          const int64_t* times, const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise,
+                          const float* sigma, const float* ca, const float* cb, const float* sqrt_recip_ac,
+                          const float* sqrt_recipm1_ac, float* out, float* x_dup /* may be NULL */, float* x0_out /* may be NULL */,
+                          int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
+                          dsc_stream_t stream);
+
+/* Per-scene gate of the text-condition dropout (text_drop_prob): y[i, :] = keep[i] ? x[i, :] : 0 for b scenes of `inner` elements;
+ * keep holds one byte per scene.  A select: the elements of a dropped scene are not read (NaN there does not propagate).  Used forward
+ * on the text features and backward on their incoming gradient.  y may alias x. */
+int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y, int32_t b, int64_t inner, dsc_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: hand-written backward of the denoiser (the reference relies on torch autograd through
  * denoise_net.py; train_on_batch, diffusion_scene_layout_ddpm.py:456-473).  Input gradients
