@@ -7,6 +7,92 @@
 
 namespace {
 
+// The step arithmetic, stated once.  Every product, sum and difference is a statement of its own (one rounding each, operands in the
+// reference's order); the kernels below differ only in which elements they update, what they read and which indices they count.
+
+// q_sample: a * v + s * n.  Also what a given element (completion, in-painting) gets for the next model call.
+__device__ __forceinline__ float renoise(float v, float n, float a, float s) {
+    const float p0 = a * v, p1 = s * n;
+    return p0 + p1;
+}
+
+// x_start from the model output: m itself (mean type x0), else A * x - Bc * m (eps, v: ca / cb are the matching table pair).
+__device__ __forceinline__ float predict_x0(float x, float m, float A, float Bc, int mean_type, bool clip) {
+    float x0;
+    if (mean_type == DSC_MEAN_X0) x0 = m;
+    else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
+    return clip ? fminf(fmaxf(x0, -1.0f), 1.0f) : x0;
+}
+
+// Per-scene coefficients of the posterior step at row tv.  sg is sigma[tv]; with zero_at_0 it is forced to 0 at tv == 0 (the caller
+// still adds 0 * noise there), without it the caller does not read the noise at tv == 0.
+struct PosteriorCoef { float A, Bc, k1, k2, sg; };
+
+__device__ __forceinline__ PosteriorCoef posterior_coef(int64_t tv, const float* __restrict__ ca, const float* __restrict__ cb,
+                                                        const float* __restrict__ c1, const float* __restrict__ c2,
+                                                        const float* __restrict__ sigma, int mean_type, bool zero_at_0) {
+    PosteriorCoef p;
+    p.A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    p.Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    p.k1 = c1[tv], p.k2 = c2[tv];
+    p.sg = (!zero_at_0 || tv != 0) ? sigma[tv] : 0.f;
+    return p;
+}
+
+__device__ __forceinline__ float posterior_mean(float x0, float x, const PosteriorCoef& p) {
+    const float m0 = p.k1 * x0, m1 = p.k2 * x;
+    return m0 + m1;
+}
+
+// The last term of both updates: u + sigma * n.
+__device__ __forceinline__ float add_noise(float u, float n, float sg) {
+    const float nz = sg * n;
+    return u + nz;
+}
+
+// Coefficients of one DDIM pair.  Every scene is at the same step: k comes from a device counter, the per-step scalars from device
+// tables of S rows, so the launch can be captured once and replayed.  step[0] and times[k] are clamped and counted once per launch
+// (``first``: one thread of the grid).  times_next[k] < 0 marks the last pair; a kernel that re-noises at t_next asks for it as a row
+// (``want_tn``: clamped and counted like the others, 0 on the last pair), the others never index with it.
+struct DdimCoef { int64_t tn; bool last; float A, Bc, R, M, an, cn, sg; };
+
+__device__ __forceinline__ DdimCoef ddim_coef(const int64_t* __restrict__ step, const int64_t* __restrict__ times,
+                                              const int64_t* __restrict__ times_next, const float* __restrict__ sqrt_an,
+                                              const float* __restrict__ cnoise, const float* __restrict__ sigma,
+                                              const float* __restrict__ ca, const float* __restrict__ cb, const float* __restrict__ ra,
+                                              const float* __restrict__ rm, int mean_type, int S, int T, bool first, bool want_tn) {
+    DdimCoef d;
+    const int64_t k = dsc_checked_index(step[0], S, first);
+    const int64_t tv = dsc_checked_index(times[k], T, first);
+    const int64_t tn_raw = times_next[k];
+    d.last = tn_raw < 0;
+    d.tn = (d.last || !want_tn) ? 0 : dsc_checked_index(tn_raw, T, first);
+    d.A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
+    d.Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
+    d.R = ra[tv], d.M = rm[tv];
+    d.an = sqrt_an[k], d.cn = cnoise[k], d.sg = sigma[k];
+    return d;
+}
+
+// x0 * sqrt(alpha_next) + c * pred_noise, pred_noise = m (eps) or (R * x - x0) / M; the division is IEEE.
+__device__ __forceinline__ float ddim_mean(float x0, float x, float m, const DdimCoef& d, int mean_type) {
+    float pn;
+    if (mean_type == DSC_MEAN_EPS) pn = m;
+    else { const float q0 = d.R * x; const float q1 = q0 - x0; pn = q1 / d.M; }
+    const float u0 = x0 * d.an, u1 = d.cn * pn;
+    return u0 + u1;
+}
+
+// The (a, s) of the re-noising that follows a step: row tv - 1 of the schedule, or times_next[k]; off after the last step.
+struct Renoise { bool on; float a, s; };
+
+__device__ __forceinline__ Renoise renoise_coef(bool on, int64_t row, const float* __restrict__ sa, const float* __restrict__ sb) {
+    Renoise r;
+    r.on = on;
+    r.a = on ? sa[row] : 0.f, r.s = on ? sb[row] : 0.f;
+    return r;
+}
+
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                                       const int64_t* __restrict__ t, const float* __restrict__ sa,
                                                       const float* __restrict__ sb, float* __restrict__ xt,
@@ -17,8 +103,7 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = x0[base + i], n = noise[base + i];
-        const float p0 = a * x, p1 = s * n;
-        xt[base + i] = p0 + p1;
+        xt[base + i] = renoise(x, n, a, s);
         if (vout) {
             const float q0 = a * n, q1 = s * x;
             vout[base + i] = q0 - q1;
@@ -34,21 +119,12 @@ __global__ __launch_bounds__(256) void p_sample_kernel(const float* xt, const fl
                                                       float* __restrict__ x0_out, int mean_type, int clip, int64_t inner, int T) {
     const int b = blockIdx.y;
     const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float k1 = c1[tv], k2 = c2[tv];
-    const float sg = (tv != 0) ? sigma[tv] : 0.f;
+    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float m0 = k1 * x0, m1 = k2 * x;
-        const float mean = m0 + m1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = mean + nz;
+        const float x0 = predict_x0(x, m, p.A, p.Bc, mean_type, clip);
+        out[base + i] = add_noise(posterior_mean(x0, x, p), noise[base + i], p.sg);
         if (x0_out) x0_out[base + i] = x0;
     }
 }
@@ -73,30 +149,15 @@ __global__ __launch_bounds__(256) void ddim_step_kernel(const float* xt, const f
                                                        float* out,   // out may alias xt (in-place step)
                                                        float* __restrict__ x0_out, int mean_type, int64_t inner, int S, int T) {
     const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
-    const int64_t k = dsc_checked_index(step[0], S, first);
-    const int64_t tv = dsc_checked_index(times[k], T, first);
-    const bool last = times_next[k] < 0;
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float R = ra[tv], M = rm[tv];
-    const float an = sqrt_an[k], c = cnoise[k], sg = sigma[k];
+    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;               // one count per launch
+    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first, false);
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
         if (x0_out) x0_out[base + i] = x0;
-        if (last) { out[base + i] = x0; continue; }
-        float pn;
-        if (mean_type == DSC_MEAN_EPS) pn = m;
-        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
-        const float u0 = x0 * an, u1 = c * pn;
-        const float u = u0 + u1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = u + nz;
+        if (d.last) { out[base + i] = x0; continue; }
+        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
     }
 }
 
@@ -120,8 +181,7 @@ __global__ __launch_bounds__(256) void complete_overwrite_kernel(float* __restri
     const float a = sa[tv], s = sb[tv];
     const int64_t cnt = (int64_t)p * c;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        const float p0 = a * partial[(int64_t)b * cnt + i], p1 = s * noise[(int64_t)b * cnt + i];
-        x[(int64_t)b * n * c + i] = p0 + p1;   // rows [0,p) of scene b are the first p*c elements
+        x[(int64_t)b * n * c + i] = renoise(partial[(int64_t)b * cnt + i], noise[(int64_t)b * cnt + i], a, s);   // rows [0,p) of scene b are the first p*c elements
     }
 }
 
@@ -140,8 +200,7 @@ __global__ __launch_bounds__(256) void complete_overwrite_ragged_kernel(float* _
     const float a = sa[tv], s = sb[tv];
     const int64_t pbase = (int64_t)b * pmax * c;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        const float p0 = a * partial[pbase + i], p1 = s * noise[pbase + i];
-        x[(int64_t)b * n * c + i] = p0 + p1;   // rows [0,count) of scene b are its first count*c elements
+        x[(int64_t)b * n * c + i] = renoise(partial[pbase + i], noise[pbase + i], a, s);   // rows [0,count) of scene b are its first count*c elements
     }
 }
 
@@ -162,30 +221,18 @@ __global__ __launch_bounds__(256) void p_sample_inpaint_kernel(const float* xt, 
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     const int64_t tv = dsc_checked_index(t[b], T, first);
     const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float k1 = c1[tv], k2 = c2[tv];
-    const float sg = (tv != 0) ? sigma[tv] : 0.f;
-    const bool renoise = tv > 0;
-    const float a = renoise ? sa[tv - 1] : 0.f, s = renoise ? sb[tv - 1] : 0.f;
+    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
+    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
     const int64_t inner = (int64_t)n * c;
     const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         if (i < cnt) {
             const float pv = partial[pbase + i];
-            if (renoise) { const float p0 = a * pv, p1 = s * noise_p[pbase + i]; out[base + i] = p0 + p1; }
-            else out[base + i] = pv;
+            out[base + i] = r.on ? renoise(pv, noise_p[pbase + i], r.a, r.s) : pv;
             continue;
         }
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float m0 = k1 * x0, m1 = k2 * x;
-        const float mean = m0 + m1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = mean + nz;
+        out[base + i] = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
     }
 }
 
@@ -208,39 +255,21 @@ __global__ __launch_bounds__(256) void ddim_inpaint_step_kernel(const float* xt,
     const int b = blockIdx.y;
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;                                  // one count per out-of-range scene
     const bool first_all = first && blockIdx.y == 0;                                         // one count per launch
-    const int64_t k = dsc_checked_index(step[0], S, first_all);
-    const int64_t tv = dsc_checked_index(times[k], T, first_all);
-    const int64_t tn_raw = times_next[k];
-    const bool last = tn_raw < 0;
-    const int64_t tn = last ? 0 : dsc_checked_index(tn_raw, T, first_all);
+    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
+    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
     const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float R = ra[tv], M = rm[tv];
-    const float an = sqrt_an[k], cn = cnoise[k], sg = sigma[k];
-    const float a = last ? 0.f : sa[tn], s = last ? 0.f : sb[tn];
     const int64_t inner = (int64_t)n * c;
     const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         if (i < cnt) {
             const float pv = partial[pbase + i];
-            if (!last) { const float p0 = a * pv, p1 = s * noise_p[pbase + i]; out[base + i] = p0 + p1; }
-            else out[base + i] = pv;
+            out[base + i] = r.on ? renoise(pv, noise_p[pbase + i], r.a, r.s) : pv;
             continue;
         }
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        if (last) { out[base + i] = x0; continue; }
-        float pn;
-        if (mean_type == DSC_MEAN_EPS) pn = m;
-        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
-        const float u0 = x0 * an, u1 = cn * pn;
-        const float u = u0 + u1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = u + nz;
+        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
+        if (d.last) { out[base + i] = x0; continue; }
+        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
     }
 }
 
@@ -257,8 +286,7 @@ __global__ __launch_bounds__(256) void masked_overwrite_kernel(float* __restrict
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         if (!mask[base + i]) continue;
-        const float p0 = a * known[base + i], p1 = s * noise[base + i];
-        x[base + i] = p0 + p1;
+        x[base + i] = renoise(known[base + i], noise[base + i], a, s);
     }
 }
 
@@ -278,29 +306,17 @@ __global__ __launch_bounds__(256) void p_sample_masked_kernel(const float* xt, c
                                                              int mean_type, int clip, int64_t inner, int T) {
     const int b = blockIdx.y;
     const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float k1 = c1[tv], k2 = c2[tv];
-    const float sg = (tv != 0) ? sigma[tv] : 0.f;
-    const bool renoise = tv > 0;
-    const float a = renoise ? sa[tv - 1] : 0.f, s = renoise ? sb[tv - 1] : 0.f;
+    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
+    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         if (mask[base + i]) {
             const float kv = known[base + i];
-            if (renoise) { const float p0 = a * kv, p1 = s * noise_k[base + i]; out[base + i] = p0 + p1; }
-            else out[base + i] = kv;
+            out[base + i] = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
             continue;
         }
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float m0 = k1 * x0, m1 = k2 * x;
-        const float mean = m0 + m1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = mean + nz;
+        out[base + i] = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
     }
 }
 
@@ -321,37 +337,19 @@ __global__ __launch_bounds__(256) void ddim_masked_step_kernel(const float* xt, 
                                                               int mean_type, int64_t inner, int S, int T) {
     const int b = blockIdx.y;
     const bool first_all = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;           // one count per launch
-    const int64_t k = dsc_checked_index(step[0], S, first_all);
-    const int64_t tv = dsc_checked_index(times[k], T, first_all);
-    const int64_t tn_raw = times_next[k];
-    const bool last = tn_raw < 0;
-    const int64_t tn = last ? 0 : dsc_checked_index(tn_raw, T, first_all);
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float R = ra[tv], M = rm[tv];
-    const float an = sqrt_an[k], cn = cnoise[k], sg = sigma[k];
-    const float a = last ? 0.f : sa[tn], s = last ? 0.f : sb[tn];
+    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
+    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
     const int64_t base = (int64_t)b * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         if (mask[base + i]) {
             const float kv = known[base + i];
-            if (!last) { const float p0 = a * kv, p1 = s * noise_k[base + i]; out[base + i] = p0 + p1; }
-            else out[base + i] = kv;
+            out[base + i] = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
             continue;
         }
         const float x = xt[base + i], m = mo[base + i];
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        if (last) { out[base + i] = x0; continue; }
-        float pn;
-        if (mean_type == DSC_MEAN_EPS) pn = m;
-        else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
-        const float u0 = x0 * an, u1 = cn * pn;
-        const float u = u0 + u1;
-        const float nz = sg * noise[base + i];
-        out[base + i] = u + nz;
+        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
+        if (d.last) { out[base + i] = x0; continue; }
+        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
     }
 }
 
@@ -388,22 +386,14 @@ __global__ __launch_bounds__(256) void p_sample_cfg_kernel(const float* xt, cons
                                                           int64_t inner, int T) {
     const int b = blockIdx.y;
     const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float k1 = c1[tv], k2 = c2[tv];
-    const float sg = sigma[tv];
+    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, false);
     const float w = scale[b];
     const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        if (clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-        const float m0 = k1 * x0, m1 = k2 * x;
-        const float mean = m0 + m1;
-        float y = mean;                           // t == 0: sigma is forced to 0 and the noise is not read
-        if (tv != 0) { const float nz = sg * noise[base + i]; y = mean + nz; }
+        const float x0 = predict_x0(x, m, p.A, p.Bc, mean_type, clip);
+        float y = posterior_mean(x0, x, p);       // t == 0: sigma is forced to 0 and the noise is not read
+        if (tv != 0) y = add_noise(y, noise[base + i], p.sg);
         out[base + i] = y;
         if (x_dup) x_dup[base + i] = y;
         if (x0_out) x0_out[base + i] = x0;
@@ -423,32 +413,15 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const float* xt, con
                                                            int64_t inner, int S, int T) {
     const int b = blockIdx.y;
     const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;               // one count per launch
-    const int64_t k = dsc_checked_index(step[0], S, first);
-    const int64_t tv = dsc_checked_index(times[k], T, first);
-    const bool last = times_next[k] < 0;
-    const float A = (mean_type == DSC_MEAN_X0) ? 0.f : ca[tv];
-    const float Bc = (mean_type == DSC_MEAN_X0) ? 0.f : cb[tv];
-    const float R = ra[tv], M = rm[tv];
-    const float an = sqrt_an[k], c = cnoise[k], sg = sigma[k];
+    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first, false);
     const float w = scale[b];
     const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
         const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-        float x0;
-        if (mean_type == DSC_MEAN_X0) x0 = m;
-        else { const float p0 = A * x, p1 = Bc * m; x0 = p0 - p1; }
-        x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
         if (x0_out) x0_out[base + i] = x0;
         float y = x0;
-        if (!last) {
-            float pn;
-            if (mean_type == DSC_MEAN_EPS) pn = m;
-            else { const float q0 = R * x; const float q1 = q0 - x0; pn = q1 / M; }
-            const float u0 = x0 * an, u1 = c * pn;
-            const float u = u0 + u1;
-            const float nz = sg * noise[base + i];
-            y = u + nz;
-        }
+        if (!d.last) y = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
         out[base + i] = y;
         if (x_dup) x_dup[base + i] = y;
     }
@@ -498,6 +471,11 @@ __global__ __launch_bounds__(192) void postfilter_compact_kernel(const float* __
     if (tid == 0) counts[b] = total;
 }
 
+// ca / cb are read for every mean type but x0.
+inline bool bad_mean_args(int32_t mean_type, const float* ca, const float* cb) {
+    return mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V || (mean_type != DSC_MEAN_X0 && (!ca || !cb));
+}
+
 inline unsigned grid_x(int64_t inner) {
     int64_t g = (inner + 255) / 256;
     return (unsigned)(g > 64 ? 64 : g);
@@ -522,8 +500,7 @@ extern "C" int dsc_p_sample_f32(const float* x_t, const float* model_out, const 
                                 int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
     if (!x_t || !model_out || !noise || !t || !coef1 || !coef2 || !sigma || !out || b < 1 || inner < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(p_sample_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x_t, model_out, noise, t, ca, cb, coef1, coef2, sigma, out, x0_out, mean_type, clip, inner, num_timesteps);
@@ -549,8 +526,7 @@ extern "C" int dsc_ddim_step_f32(const float* x_t, const float* model_out, const
     if (!x_t || !model_out || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
         !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -617,8 +593,7 @@ extern "C" int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out
     if (!x_t || !model_out || !noise || !partial || !noise_p || !counts || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
         !out || b < 1 || n < 1 || pmax < 1 || pmax > n || c < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -639,8 +614,7 @@ extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_ou
         !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || n < 1 || pmax < 1 ||
         pmax > n || c < 1 || num_steps < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(ddim_inpaint_step_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -670,8 +644,7 @@ extern "C" int dsc_p_sample_masked_f32(const float* x_t, const float* model_out,
     if (!x_t || !model_out || !noise || !known || !noise_k || !mask || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
         !out || b < 1 || inner < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(p_sample_masked_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -692,8 +665,7 @@ extern "C" int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out
         !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || inner < 1 ||
         num_steps < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(ddim_masked_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -720,8 +692,7 @@ extern "C" int dsc_p_sample_cfg_f32(const float* x_t, const float* model_out, co
                                     int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
     if (!x_t || !model_out || !scale || !noise || !t || !coef1 || !coef2 || !sigma || !out || b < 1 || inner < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(p_sample_cfg_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -740,8 +711,7 @@ extern "C" int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, c
     if (!x_t || !model_out || !scale || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
         !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
         return DSC_EINVAL;
-    if (mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V) return DSC_EINVAL;
-    if (mean_type != DSC_MEAN_X0 && (!ca || !cb)) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
     if (b > 65535) return DSC_ERANGE;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
