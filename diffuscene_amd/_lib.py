@@ -18,6 +18,8 @@ SS_NONE, SS_PER_TOKEN, SS_PER_SCENE, SS_PER_SLOT, SS_BY_INDEX = 0, 1, 2, 3, 4
 MEAN_EPS, MEAN_X0, MEAN_V = 0, 1, 2
 TILE_GN_80_W8, TILE_GN_80_W4, TILE_160x256, TILE_160x128_W4 = 1, 2, 5, 8      # DSC_TILE_* (dsc_gemm_split_tile)
 TILE_WAVE_GN, TILE_WAVE_DENSE, TILE_WAVE_GN_64 = 10, 11, 12
+F32_TILE_160x256, F32_TILE_160x128, F32_TILE_128x128, F32_TILE_96x128, F32_TILE_64x64 = 0, 1, 2, 3, 4      # DSC_F32_TILE_* (dsc_gemm_f32_tile)
+DSC_PLANES_NONE = -100          # dsc_gemm_planes_layout's "stays on the exact-f32 kernel" (ops.planes_layout turns it into -1)
 GEMM_ROW_INVARIANT = 1          # dsc_gemm_args.flags (include/diffuscene_hip.h)
 WS_MAX = 64
 MAX_TOKENS_PER_SCENE = 160
@@ -108,6 +110,7 @@ SIGNATURES = {
     "dsc_split_bf16x3_f32": (C.c_int, [C.POINTER(SplitItem), C.c_int32, C.c_void_p]),
     "dsc_gemm_arithmetic": (C.c_int, [C.POINTER(GemmArgs), C.c_int32]),
     "dsc_gemm_split_tile": (C.c_int, [C.POINTER(GemmArgs), C.c_int32]),
+    "dsc_gemm_f32_tile": (C.c_int, [C.POINTER(GemmArgs)]),
     "dsc_gemm_planes_layout": (C.c_int, [C.POINTER(GemmArgs), C.c_int32]),
     "dsc_get_split_wave": (C.c_int, []),
     "dsc_set_split_wave": (C.c_int, [C.c_int32]),

@@ -167,6 +167,33 @@ static long tile_cost(long m_rows, int rows_per_blk, int n, int bm, int bn) {
     return ((nblk + 255) / 256) * (long)bm * bn;
 }
 
+// The exact-f32 tile of a dense launch (DSC_F32_TILE_* of the header), by the cost rule above over the launch's shape alone.
+// DSC_GEMM_ROW_INVARIANT pins the 64 x 64 tile: the tiles do not give a row the same bits -- the 64 x 64 kernel (classic main loop) adds the
+// bias to the finished K sum, the interleaved kernels of the four larger tiles start their accumulators from it -- and 64 x 64 is what
+// the m = T table launch of the time MLP and every batch of <= 64 scenes took before the pin, so no stored result moves.
+static int select_f32_tile(const dsc_gemm_args* a) {
+    if (a->flags & DSC_GEMM_ROW_INVARIANT) return DSC_F32_TILE_64x64;
+    const bool wide = (a->n % 256) == 0;
+    struct Cand { int bm, bn, id; };
+    // ties go to the earlier candidate: 160 x 128 (2 blocks per CU) measured 1 % ahead of 160 x 256 at M = 20480
+    const Cand cands[5] = {{160, 128, DSC_F32_TILE_160x128}, {160, 256, DSC_F32_TILE_160x256}, {128, 128, DSC_F32_TILE_128x128},
+                           {96, 128, DSC_F32_TILE_96x128}, {64, 64, DSC_F32_TILE_64x64}};
+    int best = -1;
+    long best_cost = 0;
+    for (int i = 0; i < 5; ++i) {
+        if (cands[i].id == DSC_F32_TILE_160x256 && !wide) continue;
+        const long c = tile_cost(a->m, cands[i].bm, a->n, cands[i].bm, cands[i].bn) * a->batch;
+        if (best < 0 || c < best_cost) { best = cands[i].id; best_cost = c; }
+    }
+    return best;
+}
+
+// The tile dsc_gemm_f32 runs the launch on when neither the split-bf16 family nor the K-parallel kernel takes it (host only, launches nothing)
+extern "C" int dsc_gemm_f32_tile(const dsc_gemm_args* a) {
+    const int rc = check_common(a);
+    return rc ? rc : select_f32_tile(a);
+}
+
 extern "C" int dsc_gemm_f32(const dsc_gemm_args* a, dsc_stream_t stream) {
     int rc = check_common(a);
     if (rc) return rc;
@@ -178,24 +205,13 @@ extern "C" int dsc_gemm_f32(const dsc_gemm_args* a, dsc_stream_t stream) {
         SkinnyPlan sp;
         if (skinny_plan(a, false, &sp)) return launch_skinny<false>(a, sp, s);
     }
-    const bool wide = (a->n % 256) == 0;
-    struct Cand { int bm, bn, id; };
-    // ties go to the earlier candidate: 160 x 128 (2 blocks per CU) measured 1 % ahead of 160 x 256 at M = 20480
-    const Cand cands[5] = {{160, 128, 1}, {160, 256, 0}, {128, 128, 2}, {96, 128, 3}, {64, 64, 4}};
-    int best = -1;
-    long best_cost = 0;
-    for (int i = 0; i < 5; ++i) {
-        if (cands[i].id == 0 && !wide) continue;
-        const long c = tile_cost(a->m, cands[i].bm, a->n, cands[i].bm, cands[i].bn) * a->batch;
-        if (best < 0 || c < best_cost) { best = cands[i].id; best_cost = c; }
-    }
-    switch (best) {
+    switch (select_f32_tile(a)) {
         // 8 waves x (5x1 tiles): 160 x 256 block tile, one block per CU (fewer LDS-staged bytes per MFMA, shortest
         // epilogue); needs full 256-column tiles
-        case 0: return launch<5, 1, 1, 8, false>(a, 160, s);
-        case 1: return launch<5, 1, 1, 4, false>(a, 160, s);
-        case 2: return launch<2, 2, 2, 2, false>(a, 128, s);
-        case 3: return launch<3, 1, 1, 4, false>(a, 96, s);
+        case DSC_F32_TILE_160x256: return launch<5, 1, 1, 8, false>(a, 160, s);
+        case DSC_F32_TILE_160x128: return launch<5, 1, 1, 4, false>(a, 160, s);
+        case DSC_F32_TILE_128x128: return launch<2, 2, 2, 2, false>(a, 128, s);
+        case DSC_F32_TILE_96x128: return launch<3, 1, 1, 4, false>(a, 96, s);
         default: return launch<1, 1, 2, 2, false, 0>(a, 64, s);
     }
 }

@@ -588,6 +588,10 @@ static int select_block_tile(const dsc_gemm_args* a, bool gn);
 // have_planes: the planes question is asked for a launch as it is (dispatch) or for a launch whose planes do not exist yet
 static int select_tile(const dsc_gemm_args* a, bool gn, bool assume_planes = false) {
     if (dsc_get_gemm_arithmetic() != 1 || (!assume_planes && !a->w_planes)) return -1;
+    // DSC_GEMM_ROW_INVARIANT: every tile below is chosen by m, and a row of the split arithmetic is not the row of the exact-f32 kernel
+    // that builds the m = T table -- a flagged launch ignores its planes (dispatch, dsc_gemm_arithmetic, dsc_gemm_split_tile and
+    // dsc_gemm_planes_layout all ask here)
+    if (a->flags & DSC_GEMM_ROW_INVARIANT) return -1;
     const int w = select_wave(a, gn);
     return w >= 0 ? w : select_block_tile(a, gn);
 }
@@ -692,7 +696,7 @@ extern "C" int dsc_gemm_split_tile(const dsc_gemm_args* a, int32_t gn) {
 extern "C" int dsc_gemm_planes_layout(const dsc_gemm_args* a, int32_t gn) {
     if (!a || a->m <= 0 || a->n <= 0 || a->k1 <= 0) return DSC_EINVAL;
     const int tile = select_tile(a, gn != 0, true);
-    return tile < 0 ? -1 : (tile == T_WAVE_GN || tile == T_WAVE_DENSE || tile == T_WAVE_GN_64) ? DSC_PLANES_FRAGMENT : DSC_PLANES_ROWMAJOR;
+    return tile < 0 ? DSC_PLANES_NONE : (tile == T_WAVE_GN || tile == T_WAVE_DENSE || tile == T_WAVE_GN_64) ? DSC_PLANES_FRAGMENT : DSC_PLANES_ROWMAJOR;
 }
 
 extern "C" int dsc_split_bf16x3_f32(const dsc_split_item* items, int32_t count, dsc_stream_t stream) {

@@ -285,7 +285,8 @@ class Plan:
             temb = pool.get(B, D)
             self.call("dsc_time_embedding_f32", self.t_in.data_ptr(), B, D, e.time_table.data_ptr(),
                       e.time_table.shape[0], e.time_freq.data_ptr(), temb.data_ptr(), keep=(temb,))
-            # row_invariant: ss_table() below builds the same rows with m = T for the captured loops -- both must take the same kernel
+            # row_invariant: ss_table() below builds the same rows with m = T for the captured loops -- a row must not depend on the number
+            # of rows, so these three stay on the exact-f32 tile kernels at every B (the library wants no planes for them)
             t1 = self.gemm(temb, net.time_mlp[1].weight, pool.get(B, 4 * D), net.time_mlp[1].bias, act_out=ACT_GELU, row_invariant=True)
             # every consumer applies SiLU first (ResnetBlock.mlp) -> fold it into this epilogue
             t2 = self.gemm(t1, net.time_mlp[3].weight, pool.get(B, 4 * D), net.time_mlp[3].bias, act_out=ACT_SILU, row_invariant=True)

@@ -109,9 +109,11 @@ PLANES_ROWMAJOR, PLANES_FRAGMENT = 0, 1
 def planes_layout(g, gn=False):
     """Which layout of the weight's bf16 planes this launch wants (dsc_gemm_planes_layout): PLANES_ROWMAJOR (the block-staged split
     kernel), PLANES_FRAGMENT (the wave-autonomous kernel reads MFMA fragments straight from memory), or -1: the launch stays on the
-    exact-f32 kernel whatever it is given.  Asked BEFORE planes are made."""
+    exact-f32 kernel whatever it is given (always so for a row_invariant launch).  Asked BEFORE planes are made; invalid arguments raise."""
     r = _lib.fn("dsc_gemm_planes_layout")(C.byref(g), 1 if gn else 0)
-    if r < -1:
+    if r == _lib.DSC_PLANES_NONE:          # the library's own value for it: -1 is DSC_EINVAL there
+        return -1
+    if r < 0:
         _lib.check(r, "dsc_gemm_planes_layout")
     return r
 
@@ -162,6 +164,7 @@ def split_planes(items, stream=None):
         elif tuple(planes.shape) != shape or planes.dtype != torch.int16 or not planes.is_contiguous():
             raise RuntimeError("split_planes: planes must be contiguous int16 %s" % (shape,))
         planes._dsc_layout = PLANES_FRAGMENT if frag else PLANES_ROWMAJOR
+        planes._dsc_fragment = None        # attach_planes' converted copy: the kernel writes through a raw pointer, planes._version does not move
         out.append(planes)
         batch.append((ptr, ldw, r, c, planes.data_ptr(), (1 if tr else 0) | frag, w2, planes))
     for i in range(0, len(batch), _lib.WS_MAX):

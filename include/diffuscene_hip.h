@@ -113,13 +113,22 @@ typedef struct dsc_gemm_args {
     float* gnb_dss; int64_t ld_gnb_dss;
     /* DSC_GEMM_ROW_INVARIANT: every output row must come out exactly as in a launch of the same product with any other number of rows --
      * a table built once with m = T rows stands in for per-step launches with m = B rows (the tabulated time MLP of the reverse loops,
-     * engine.ss_table), and a captured loop must reproduce the eager loop bit for bit.  The launch then stays on the exact-f32 tile
-     * kernels, whose K order does not depend on m (the K-parallel kernel for small launches associates the K sum differently). */
+     * engine.ss_table), and a captured loop must reproduce the eager loop bit for bit.  Every kernel family whose choice or K association
+     * depends on m refuses a flagged launch: the split-bf16 family (its tiles are chosen by m; w_planes is ignored, dsc_gemm_split_tile
+     * answers -1, dsc_gemm_arithmetic 0 and dsc_gemm_planes_layout DSC_PLANES_NONE, so callers make no planes for it) and the K-parallel
+     * kernel for small launches (it associates the K sum as eight slice sums; dsc_gemm_skinny answers 0).  The launch runs on ONE exact-f32
+     * tile kernel whatever m is, the 64 x 64 tile (dsc_gemm_f32_tile answers DSC_F32_TILE_64x64): the five exact-f32 tiles share the K
+     * order, but the 64 x 64 kernel adds the bias to the finished K sum while the four larger ones start their accumulators from the
+     * bias, so a row with a bias differs between them in the last bit (measured: t_pack rows at m = 80, 330, 390, 420, 720 against the
+     * m = 1000 launch, before the pin).  64 x 64 is the tile the m = T table launch and every batch of <= 64 scenes took before, so the pin
+     * moves no result at those sizes.  A flagged launch larger than the table's pays for it with the smallest tile; it is meant for
+     * products of a few hundred rows.  tests/test_gpu_row_invariant.py holds all of this at one m inside every dispatch class. */
     int32_t flags;
 } dsc_gemm_args;
 #define DSC_GEMM_ROW_INVARIANT 1
 #define DSC_PLANES_ROWMAJOR 0
 #define DSC_PLANES_FRAGMENT 1
+#define DSC_PLANES_NONE (-100)   /* answer of dsc_gemm_planes_layout only: no planes wanted (never a value of w_planes_layout, never an error code) */
 
 int dsc_gemm_f32(const dsc_gemm_args* args, dsc_stream_t stream);
 
@@ -148,8 +157,19 @@ int dsc_gemm_arithmetic(const dsc_gemm_args* args, int32_t gn);
 #define DSC_TILE_WAVE_GN_64  12  /* half-size GroupNorm launches: one scene of 65..80 tokens x 64 channels per wave */
 int dsc_gemm_split_tile(const dsc_gemm_args* args, int32_t gn);
 
-/* The planes layout the launch wants: DSC_PLANES_ROWMAJOR / DSC_PLANES_FRAGMENT, or -1 when it stays on the exact-f32 kernel whatever
- * planes it is given (w_planes / w_planes_layout of `args` are not read). */
+/* Which TILE of the exact-f32 MFMA kernel dsc_gemm_f32 picks for the launch's shape: the kernel that runs when neither the split-bf16
+ * family (dsc_gemm_split_tile) nor the K-parallel kernel (dsc_gemm_skinny) takes the launch.  Host only, launches nothing; a negative
+ * DSC_E* code for arguments dsc_gemm_f32 would reject.  Tests use it to say which tiles a bit-for-bit comparison went through. */
+#define DSC_F32_TILE_160x256 0   /* 8 waves */
+#define DSC_F32_TILE_160x128 1
+#define DSC_F32_TILE_128x128 2
+#define DSC_F32_TILE_96x128  3
+#define DSC_F32_TILE_64x64   4
+int dsc_gemm_f32_tile(const dsc_gemm_args* args);
+
+/* The planes layout the launch wants: DSC_PLANES_ROWMAJOR / DSC_PLANES_FRAGMENT, or DSC_PLANES_NONE when it stays on the exact-f32 kernel
+ * whatever planes it is given (w_planes / w_planes_layout of `args` are not read; a DSC_GEMM_ROW_INVARIANT launch always does).  Invalid
+ * arguments (null, m / n / k1 <= 0) answer DSC_EINVAL, which is none of the three. */
 int dsc_gemm_planes_layout(const dsc_gemm_args* args, int32_t gn);
 
 /* The wave-autonomous kernel family of the split arithmetic: 1 = used wherever a launch qualifies (default), 0 = never (every split
