@@ -9,6 +9,20 @@ Same names, signatures, assertion behaviour and RNG draw order as the reference 
   kernels (csrc/diffusion.hip), bit-identical to the reference's fp32 expressions;
 * the reverse loops run as a replayed hipGraph (default since round 6; ``graph=False`` or env DSC_GRAPH=0 for the eager loop): one captured step
   with a device-resident timestep, replayed T times -- no Python, no launches on the critical path.
+
+The eager loops -- what the captured loops of sampler.py are tested against, built from the unfused kernels on purpose -- are two cores,
+each a generator of states (x_T, then the state after every step), and two independent variations handed to a core as small objects:
+  GaussianDiffusion._t_states        T steps: fill t_, model call, one draw (also at t == 0), ops.p_sample
+  GaussianDiffusion._strided_states  S strided (DDIM) pairs: device step counter, model call, a draw except on the last pair, ddim_step,
+                                     ddim_advance
+  the given part   _FREE (nothing), _GivenRows / _GivenRagged (a dense / ragged row prefix), _GivenMask (a byte mask): drawn for and
+                   written over the state in place BEFORE every model call, restored in the last state; x_T is cloned only if it is
+                   written
+  the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine)
+The twelve public loops validate, hand over to the captured loop under _use_graph, build the two objects and run a core: nothing given --
+p_sample_loop, _trajectory, _arrange / ddim_sample_loop, ddim_arrange_loop (both arrange loops on the sub-shape); guided --
+p_sample_loop_guided / ddim_guided_loop; rows -- p_sample_loop_complete, _complete_ragged / ddim_complete_ragged_loop; mask --
+p_sample_loop_masked / ddim_masked_loop.
 """
 import json
 import os
@@ -54,6 +68,101 @@ def get_betas(schedule_type, b_start, b_end, time_num):
         # the reference's 'cosine' branch never assigns betas (diffusion_ddpm.py:84-87, UnboundLocalError)
         raise NotImplementedError(schedule_type)
     return betas
+
+
+# ---------------------------------------------------------------------- the variations of an eager loop (module docstring)
+class _Free:
+    """The given part of a loop that is given nothing.  ``before(x, t_)``: draw noise and write q_sample(given, t, noise) over the state
+    in place, in front of the model call; ``finish(x)``: the clean values into the last state; ``inplace``: does ``before`` write."""
+    inplace = False
+
+    def before(self, x, t_):
+        pass
+
+    def finish(self, x):
+        return x
+
+
+_FREE = _Free()
+
+
+class _Given:
+    """A given part that writes: the q_sample tables and one draw of ``size`` per step."""
+    inplace = True
+
+    def __init__(self, diff, device, noise_fn, size):
+        tb = diff.tables(device)
+        self.q = (tb["sqrt_alphas_cumprod"], tb["sqrt_one_minus_alphas_cumprod"])
+        self.draw = lambda: noise_fn(size=size, dtype=torch.float, device=device).contiguous()
+
+
+class _GivenRows(_Given):
+    """The first P rows of every scene are given by ``boxes`` (B, P, C): p_sample_loop_complete, reference :461-473."""
+
+    def __init__(self, diff, device, noise_fn, boxes):
+        super().__init__(diff, device, noise_fn, boxes.shape)
+        self.boxes = boxes
+
+    def before(self, x, t_):
+        ops.complete_overwrite(x, self.boxes, self.draw(), t_, *self.q)
+
+    def finish(self, x):
+        x[:, :self.boxes.shape[1], :] = self.boxes
+        return x
+
+
+class _GivenRagged(_GivenRows):
+    """Rows [0, counts[b]) of scene b are given by ``boxes`` (B, Pmax, C); ``counts``: (B,) int64 on the device (ops.ragged_counts)."""
+
+    def __init__(self, diff, device, noise_fn, boxes, counts):
+        super().__init__(diff, device, noise_fn, boxes)
+        self.counts = counts
+
+    def before(self, x, t_):
+        ops.complete_overwrite_ragged(x, self.boxes, self.draw(), self.counts, t_, *self.q)
+
+    def finish(self, x):
+        return restore_given_rows(x, self.boxes, self.counts)
+
+
+class _GivenMask(_Given):
+    """The elements marked by ``mask`` (B, N, C) uint8 (ops.known_mask) are given by ``known``.  One draw of the full shape per step."""
+
+    def __init__(self, diff, device, noise_fn, shape, known, mask):
+        super().__init__(diff, device, noise_fn, shape)
+        self.known, self.mask = known, mask
+
+    def before(self, x, t_):
+        ops.masked_overwrite(x, self.known, self.draw(), self.mask, t_, *self.q)
+
+    def finish(self, x):
+        return torch.where(self.mask != 0, self.known, x)
+
+
+def restore_given_rows(x, boxes, counts):
+    """x[b, :counts[b]] = boxes[b, :counts[b]], in place: the restore of the ragged completion loops, eager and captured unfused."""
+    pmax = boxes.shape[1]
+    given = torch.arange(pmax, device=x.device)[None, :, None] < counts[:, None, None]
+    x[:, :pmax, :] = torch.where(given, boxes, x[:, :pmax, :])
+    return x
+
+
+def _model(denoise_fn, condition, condition_cross):
+    """The model call of a loop: (x, t_) -> model output."""
+    return lambda x, t_: denoise_fn(x, t_, condition, condition_cross)
+
+
+def _guided_model(denoise_fn, cond2, cross2, scale):
+    """The guided model call: the denoiser at 2 B on the same x and t in both halves (conditions of _guided_inputs), then
+    m = u + scale[b] * (c - u) (dsc_cfg_combine_f32)."""
+    return lambda x, t_: ops.cfg_combine(denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), cond2, cross2).contiguous(), scale)
+
+
+def _last(states, shape):
+    for x in states:
+        pass
+    assert x.shape == tuple(shape)
+    return x
 
 
 class GaussianDiffusion:
@@ -275,24 +384,66 @@ class GaussianDiffusion:
         return model_mean, model_variance, model_log_variance
 
     # ------------------------------------------------------------------ sampling
-    def p_sample(self, denoise_fn, data, t, condition, condition_cross, noise_fn, clip_denoised=False,
-                 return_pred_xstart=False):
-        """One reverse step, reference :339-352: model call, then ONE noise draw (also at t == 0), then the fused
-        x0-from-output / clamp / posterior-mean / masked noise-add kernel."""
-        model_output = denoise_fn(data, t, condition, condition_cross)
-        noise = noise_fn(size=data.shape, dtype=data.dtype, device=data.device)
+    def _posterior_step(self, data, model_output, t, noise_fn, clip_denoised, x0_out=None, draw=None):
+        """The update of one reverse step, reference :344-352: ONE noise draw (also at t == 0), then the fused x0-from-output / clamp /
+        posterior-mean / masked noise-add kernel.  ``draw``: the keywords of the draw where they are not the reference's."""
+        noise = noise_fn(**(draw or dict(size=data.shape, dtype=data.dtype, device=data.device)))
         assert noise.shape == data.shape
         tb = self.tables(data.device)
         ca, cb = self._coeffs(tb)
-        pred_xstart = torch.empty_like(data) if return_pred_xstart else None
         sample = ops.p_sample(data.contiguous(), model_output.contiguous(), noise.contiguous(), t, ca, cb,
                               tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], self._sigma(tb),
-                              _MEAN[self.model_mean_type], clip_denoised, x0_out=pred_xstart)
+                              _MEAN[self.model_mean_type], clip_denoised, x0_out=x0_out)
         assert sample.shape == data.shape
+        return sample
+
+    def p_sample(self, denoise_fn, data, t, condition, condition_cross, noise_fn, clip_denoised=False,
+                 return_pred_xstart=False):
+        """One reverse step, reference :339-352: model call, then _posterior_step."""
+        model_output = denoise_fn(data, t, condition, condition_cross)
+        pred_xstart = torch.empty_like(data) if return_pred_xstart else None
+        sample = self._posterior_step(data, model_output, t, noise_fn, clip_denoised, pred_xstart)
         return (sample, pred_xstart) if return_pred_xstart else sample
 
     def _total_steps(self, keep_running):
         return self.num_timesteps if not keep_running else len(self.betas)
+
+    def _say_last(self):
+        print('last:', 0, self.num_timesteps, len(self.betas))          # the reference's print at t == 0 (:469, :497)
+
+    # the two eager loops (module docstring); a state that a given part overwrites in place stays the same tensor until the update
+    def _t_states(self, model, shape, device, noise_fn, clip_denoised, total_steps, given=_FREE, draw=None):
+        """The T-step loop, reference :355-371: fill t_, [overwrite the given part], model call, one draw, ops.p_sample -- at t == 0 too."""
+        x = noise_fn(size=shape, dtype=torch.float, device=device)
+        if given.inplace:
+            x = x.clone()                       # a caller's tensor (a row of a NoiseReplay buffer) is not written
+        yield x
+        for t in reversed(range(0, total_steps)):
+            t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
+            given.before(x, t_)
+            x = self._posterior_step(x, model(x, t_), t_, noise_fn, clip_denoised, draw=draw)
+            yield given.finish(x) if t == 0 else x      # not a copy: ``given.before`` of the next step writes into it (keep a clone)
+
+    def _strided_states(self, model, shape, device, noise_fn, S, eta, given=_FREE):
+        """The strided (DDIM) loop, reference :402-444: a device step counter, [overwrite the given part], model call, a draw except on
+        the last pair ((t, -1) takes x_start), ddim_step, ddim_advance."""
+        dtab = self.ddim_tables(S, eta, device)
+        pairs = dtab[0]
+        step = torch.zeros((1,), dtype=torch.int64, device=device)
+        t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(pairs[0][0])
+        x = noise_fn(size=shape, dtype=torch.float, device=device)
+        if given.inplace:
+            x = x.clone()
+        yield x
+        for time, time_next in pairs:
+            given.before(x, t_)
+            model_output = model(x, t_)
+            last = time_next < 0
+            noise = x if last else noise_fn(size=shape, dtype=torch.float, device=device)      # not read on the last pair
+            x = self.ddim_step(x.contiguous(), model_output.contiguous(), noise.contiguous(), step, dtab)
+            if not last:
+                ops.ddim_advance(step, dtab[1], t_)
+            yield given.finish(x) if last else x        # not a copy, as in _t_states
 
     def p_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                       clip_denoised=True, keep_running=False, graph=None):
@@ -302,12 +453,8 @@ class GaussianDiffusion:
             from ..sampler import graph_sample_loop
             return graph_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross,
                                      clip_denoised, self._total_steps(keep_running), noise_fn)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device)
-        for t in reversed(range(0, self._total_steps(keep_running))):
-            t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
+        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised,
+                                     self._total_steps(keep_running)), shape)
         assert img_t.shape == shape
         return img_t
 
@@ -316,13 +463,9 @@ class GaussianDiffusion:
         """reference :373-398"""
         assert isinstance(shape, (tuple, list))
         total_steps = self._total_steps(keep_running)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device)
-        imgs = [img_t]
-        for t in reversed(range(0, total_steps)):
-            t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
+        states = self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised, total_steps)
+        imgs = [next(states)]
+        for t, img_t in zip(reversed(range(0, total_steps)), states):
             if t % freq == 0 or t == total_steps - 1:
                 imgs.append(img_t)
         assert imgs[-1].shape == shape
@@ -391,22 +534,9 @@ class GaussianDiffusion:
         if not return_all_timesteps and _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_ddim_sample_loop
             return graph_ddim_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn)
-        dtab = self.ddim_tables(S, eta, device)
-        pairs = dtab[0]
-        step = torch.zeros((1,), dtype=torch.int64, device=device)
-        t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(pairs[0][0])
-        img = noise_fn(size=shape, dtype=torch.float, device=device)
-        imgs = [img]
-        for time, time_next in pairs:
-            model_output = denoise_fn(img, t_, condition, condition_cross)
-            last = time_next < 0
-            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
-            img = self.ddim_step(img.contiguous(), model_output.contiguous(), noise.contiguous(), step, dtab)
-            imgs.append(img)
-            if not last:
-                ops.ddim_advance(step, dtab[1], t_)
-        assert img.shape == tuple(shape)
-        return imgs if return_all_timesteps else img
+        imgs = list(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta))
+        assert imgs[-1].shape == tuple(shape)
+        return imgs if return_all_timesteps else imgs[-1]
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
@@ -437,24 +567,14 @@ class GaussianDiffusion:
         unfused pieces -- the denoiser at 2 B, cfg_combine, p_sample; the graph path (the default, by the rules of p_sample_loop)
         replays one captured step whose update is the fused dsc_p_sample_cfg_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B = shape[0]
         cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "p_sample_loop_guided")
         total_steps = self._total_steps(keep_running)
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_guided_loop
             return graph_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, clip_denoised, total_steps, noise_fn)
-        tb = self.tables(device)
-        ca, cb = self._coeffs(tb)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device)
-        for t in reversed(range(0, total_steps)):
-            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
-            model_output = denoise_fn(torch.cat([img_t, img_t], dim=0), torch.cat([t_, t_]), cond2, cross2)
-            m = ops.cfg_combine(model_output.contiguous(), scale)
-            noise = noise_fn(size=shape, dtype=torch.float, device=device)
-            img_t = ops.p_sample(img_t.contiguous(), m, noise.contiguous(), t_, ca, cb, tb["posterior_mean_coef1"],
-                                 tb["posterior_mean_coef2"], self._sigma(tb), _MEAN[self.model_mean_type], clip_denoised)
-        assert img_t.shape == tuple(shape)
-        return img_t
+        self.tables(device)                     # the device check, before the first draw
+        return _last(self._t_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, clip_denoised, total_steps,
+                                    draw=dict(size=shape, dtype=torch.float, device=device)), shape)
 
     @torch.no_grad()
     def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
@@ -465,54 +585,30 @@ class GaussianDiffusion:
         unfused pieces (the denoiser at 2 B, cfg_combine, ddim_step); the graph path replays one captured step whose update is the fused
         dsc_ddim_cfg_step_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B = shape[0]
         S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
         cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "ddim_guided_loop")
         self.ddim_sampling_eta, self.sampling_timesteps = eta, S
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_ddim_guided_loop
             return graph_ddim_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, S, eta, noise_fn)
-        dtab = self.ddim_tables(S, eta, device)
-        pairs = dtab[0]
-        step = torch.zeros((1,), dtype=torch.int64, device=device)
-        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
-        img = noise_fn(size=shape, dtype=torch.float, device=device)
-        for time, time_next in pairs:
-            model_output = denoise_fn(torch.cat([img, img], dim=0), torch.cat([t_, t_]), cond2, cross2)
-            m = ops.cfg_combine(model_output.contiguous(), scale)
-            last = time_next < 0
-            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
-            img = self.ddim_step(img.contiguous(), m, noise.contiguous(), step, dtab)
-            if not last:
-                ops.ddim_advance(step, dtab[1], t_)
-        assert img.shape == tuple(shape)
-        return img
+        return _last(self._strided_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, S, eta), shape)
 
+    # ------------------------------------------------------------------ completion, in-painting, re-arrangement
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
         model call) and overwrites the first P rows of x_t in place; at t == 0 the clean objects are restored."""
         assert isinstance(shape, (tuple, list))
+        partial_boxes = partial_boxes.contiguous()
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_sample_loop
-            print('last:', 0, self.num_timesteps, len(self.betas))
+            self._say_last()
             return graph_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised,
-                                     self._total_steps(keep_running), noise_fn, partial_boxes=partial_boxes.contiguous())
-        tb = self.tables(device)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device).clone()   # overwritten in place below
-        partial_boxes = partial_boxes.contiguous()
-        num_partial = partial_boxes.shape[1]
-        for t in reversed(range(0, self._total_steps(keep_running))):
-            t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
-            noise = noise_fn(size=partial_boxes.shape, dtype=torch.float, device=device)
-            ops.complete_overwrite(img_t, partial_boxes, noise.contiguous(), t_, tb["sqrt_alphas_cumprod"],
-                                   tb["sqrt_one_minus_alphas_cumprod"])
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
-            if t == 0:
-                print('last:', t, self.num_timesteps, len(self.betas))
-                img_t[:, :num_partial, :] = partial_boxes
+                                     self._total_steps(keep_running), noise_fn, partial_boxes=partial_boxes)
+        given = _GivenRows(self, device, noise_fn, partial_boxes)
+        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised,
+                                     self._total_steps(keep_running), given), shape)
+        self._say_last()
         assert img_t.shape == shape
         return img_t
 
@@ -527,35 +623,17 @@ class GaussianDiffusion:
         This eager loop is built from the unfused pieces -- ragged overwrite, p_sample, restore; the graph path (the default, by the
         rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B, N, C = shape
-        if partial_boxes is None or num_partial is None:
-            raise ValueError("p_sample_loop_complete_ragged needs partial_boxes (B, Pmax, C) and num_partial (B,)")
-        if partial_boxes.dim() != 3 or partial_boxes.shape[0] != B or partial_boxes.shape[2] != C or not 1 <= partial_boxes.shape[1] <= N:
-            raise ValueError("partial_boxes must be (%d, 1 <= Pmax <= %d, %d), got %s" % (B, N, C, tuple(partial_boxes.shape)))
-        partial_boxes = partial_boxes.contiguous()
-        pmax = partial_boxes.shape[1]
-        counts = ops.ragged_counts(num_partial, B, pmax, device)
+        partial_boxes, counts = self._ragged_inputs(shape, device, partial_boxes, num_partial, "p_sample_loop_complete_ragged")
         total_steps = self._total_steps(keep_running)
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_complete_ragged_loop
-            print('last:', 0, self.num_timesteps, len(self.betas))
+            self._say_last()
             return graph_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised,
                                               total_steps, noise_fn, partial_boxes, counts)
-        tb = self.tables(device)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device).clone()   # overwritten in place below
-        for t in reversed(range(0, total_steps)):
-            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
-            noise = noise_fn(size=partial_boxes.shape, dtype=torch.float, device=device)
-            ops.complete_overwrite_ragged(img_t, partial_boxes, noise.contiguous(), counts, t_, tb["sqrt_alphas_cumprod"],
-                                          tb["sqrt_one_minus_alphas_cumprod"])
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
-            if t == 0:
-                print('last:', t, self.num_timesteps, len(self.betas))
-                given = torch.arange(pmax, device=device)[None, :, None] < counts[:, None, None]
-                img_t[:, :pmax, :] = torch.where(given, partial_boxes, img_t[:, :pmax, :])
-        assert img_t.shape == tuple(shape)
+        given = _GivenRagged(self, device, noise_fn, partial_boxes, counts)
+        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised, total_steps,
+                                     given), shape)
+        self._say_last()
         return img_t
 
     @torch.no_grad()
@@ -575,40 +653,25 @@ class GaussianDiffusion:
         restore; the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
         dsc_ddim_inpaint_step_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B, N, C = shape
         S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        if partial_boxes is None or num_partial is None:
-            raise ValueError("ddim_complete_ragged_loop needs partial_boxes (B, Pmax, C) and num_partial (B,)")
-        if partial_boxes.dim() != 3 or partial_boxes.shape[0] != B or partial_boxes.shape[2] != C or not 1 <= partial_boxes.shape[1] <= N:
-            raise ValueError("partial_boxes must be (%d, 1 <= Pmax <= %d, %d), got %s" % (B, N, C, tuple(partial_boxes.shape)))
-        partial_boxes = partial_boxes.contiguous()
-        pmax = partial_boxes.shape[1]
-        counts = ops.ragged_counts(num_partial, B, pmax, device)
+        partial_boxes, counts = self._ragged_inputs(shape, device, partial_boxes, num_partial, "ddim_complete_ragged_loop")
         self.ddim_sampling_eta, self.sampling_timesteps = eta, S
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_ddim_complete_ragged_loop
             return graph_ddim_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn,
                                                    partial_boxes, counts)
-        tb = self.tables(device)
-        dtab = self.ddim_tables(S, eta, device)
-        pairs = dtab[0]
-        step = torch.zeros((1,), dtype=torch.int64, device=device)
-        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
-        img = noise_fn(size=shape, dtype=torch.float, device=device).clone()     # overwritten in place below
-        for time, time_next in pairs:
-            noise_p = noise_fn(size=partial_boxes.shape, dtype=torch.float, device=device)
-            ops.complete_overwrite_ragged(img, partial_boxes, noise_p.contiguous(), counts, t_, tb["sqrt_alphas_cumprod"],
-                                          tb["sqrt_one_minus_alphas_cumprod"])
-            model_output = denoise_fn(img, t_, condition, condition_cross)
-            last = time_next < 0
-            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
-            img = self.ddim_step(img, model_output.contiguous(), noise.contiguous(), step, dtab)
-            if not last:
-                ops.ddim_advance(step, dtab[1], t_)
-        given = torch.arange(pmax, device=device)[None, :, None] < counts[:, None, None]
-        img[:, :pmax, :] = torch.where(given, partial_boxes, img[:, :pmax, :])
-        assert img.shape == tuple(shape)
-        return img
+        return _last(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta,
+                                          _GivenRagged(self, device, noise_fn, partial_boxes, counts)), shape)
+
+    def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
+        """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
+        B, N, C = shape
+        if partial_boxes is None or num_partial is None:
+            raise ValueError("%s needs partial_boxes (B, Pmax, C) and num_partial (B,)" % what)
+        if partial_boxes.dim() != 3 or partial_boxes.shape[0] != B or partial_boxes.shape[2] != C or not 1 <= partial_boxes.shape[1] <= N:
+            raise ValueError("partial_boxes must be (%d, 1 <= Pmax <= %d, %d), got %s" % (B, N, C, tuple(partial_boxes.shape)))
+        partial_boxes = partial_boxes.contiguous()
+        return partial_boxes, ops.ragged_counts(num_partial, B, partial_boxes.shape[1], device)
 
     def _masked_inputs(self, shape, device, known, mask, what):
         B, N, C = shape
@@ -631,26 +694,15 @@ class GaussianDiffusion:
         ``known``.  This eager loop is built from the unfused pieces -- masked overwrite, p_sample, select; the graph path (the default,
         by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B, N, C = shape
         known, mask = self._masked_inputs(shape, device, known, mask, "p_sample_loop_masked")
         total_steps = self._total_steps(keep_running)
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_masked_loop
             return graph_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised, total_steps,
                                      noise_fn, known, mask)
-        tb = self.tables(device)
-        img_t = noise_fn(size=shape, dtype=torch.float, device=device).clone()   # overwritten in place below
-        for t in reversed(range(0, total_steps)):
-            t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(t)
-            noise_k = noise_fn(size=shape, dtype=torch.float, device=device)
-            ops.masked_overwrite(img_t, known, noise_k.contiguous(), mask, t_, tb["sqrt_alphas_cumprod"],
-                                 tb["sqrt_one_minus_alphas_cumprod"])
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
-        img_t = torch.where(mask != 0, known, img_t)
-        assert img_t.shape == tuple(shape)
-        return img_t
+        given = _GivenMask(self, device, noise_fn, shape, known, mask)
+        return _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised, total_steps,
+                                    given), shape)
 
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
@@ -663,32 +715,14 @@ class GaussianDiffusion:
         whole rows [0, counts[b]) returns what that loop returns, bit for bit.  The eager loop is built from the unfused pieces; the
         graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
         assert isinstance(shape, (tuple, list))
-        B, N, C = shape
         S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
         known, mask = self._masked_inputs(shape, device, known, mask, "ddim_masked_loop")
         self.ddim_sampling_eta, self.sampling_timesteps = eta, S
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_ddim_masked_loop
             return graph_ddim_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn, known, mask)
-        tb = self.tables(device)
-        dtab = self.ddim_tables(S, eta, device)
-        pairs = dtab[0]
-        step = torch.zeros((1,), dtype=torch.int64, device=device)
-        t_ = torch.empty(B, dtype=torch.int64, device=device).fill_(pairs[0][0])
-        img = noise_fn(size=shape, dtype=torch.float, device=device).clone()     # overwritten in place below
-        for time, time_next in pairs:
-            noise_k = noise_fn(size=shape, dtype=torch.float, device=device)
-            ops.masked_overwrite(img, known, noise_k.contiguous(), mask, t_, tb["sqrt_alphas_cumprod"],
-                                 tb["sqrt_one_minus_alphas_cumprod"])
-            model_output = denoise_fn(img, t_, condition, condition_cross)
-            last = time_next < 0
-            noise = img if last else noise_fn(size=shape, dtype=torch.float, device=device)     # not read on the last pair
-            img = self.ddim_step(img, model_output.contiguous(), noise.contiguous(), step, dtab)
-            if not last:
-                ops.ddim_advance(step, dtab[1], t_)
-        img = torch.where(mask != 0, known, img)
-        assert img.shape == tuple(shape)
-        return img
+        given = _GivenMask(self, device, noise_fn, shape, known, mask)
+        return _last(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta, given), shape)
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
@@ -703,38 +737,29 @@ class GaussianDiffusion:
         sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
         img = self.ddim_sample_loop(denoise_fn, sub, device, condition, condition_cross, noise_fn=noise_fn,
                                     sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph)
-        tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
-        img = torch.cat([img[:, :, 0:tr], input_boxes[:, :, tr:tr + sz], img[:, :, tr:], input_boxes[:, :, bb:]], dim=-1).contiguous()
+        img = self._arranged(img, input_boxes)
         assert img.shape == tuple(shape)
         return img
+
+    def _arranged(self, img, input_boxes):
+        """The re-assembly of a re-arrangement, reference :496-503: the diffused [translation | angle] into the given rows."""
+        tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
+        return torch.cat([img[:, :, 0:tr], input_boxes[:, :, tr:tr + sz], img[:, :, tr:], input_boxes[:, :, bb:]], dim=-1).contiguous()
 
     def p_sample_loop_arrange(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                               clip_denoised=True, keep_running=False, input_boxes=None, graph=None):
         """Re-arrangement, reference :478-506: diffuse [translation | angle] only, re-assemble at t == 0."""
         assert isinstance(shape, (tuple, list))
+        sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
         if _use_graph(graph, noise_fn, denoise_fn):
             from ..sampler import graph_sample_loop
-            sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
             img_t = graph_sample_loop(self, denoise_fn, sub, device, condition, condition_cross, clip_denoised,
                                       self._total_steps(keep_running), noise_fn)
-            print('last:', 0, self.num_timesteps, len(self.betas))
-            tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
-            img_t = torch.cat([img_t[:, :, 0:tr], input_boxes[:, :, tr:tr + sz], img_t[:, :, tr:],
-                               input_boxes[:, :, bb:]], dim=-1).contiguous()
-            assert img_t.shape == shape
-            return img_t
-        img_t = noise_fn(size=(shape[0], shape[1], self.translation_dim + self.angle_dim), dtype=torch.float,
-                         device=device)
-        for t in reversed(range(0, self._total_steps(keep_running))):
-            t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
-            img_t = self.p_sample(denoise_fn=denoise_fn, data=img_t, t=t_, condition=condition,
-                                  condition_cross=condition_cross, noise_fn=noise_fn,
-                                  clip_denoised=clip_denoised, return_pred_xstart=False)
-            if t == 0:
-                print('last:', t, self.num_timesteps, len(self.betas))
-                tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
-                img_t = torch.cat([img_t[:, :, 0:tr], input_boxes[:, :, tr:tr + sz], img_t[:, :, tr:],
-                                   input_boxes[:, :, bb:]], dim=-1).contiguous()
+        else:
+            img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), sub, device, noise_fn, clip_denoised,
+                                         self._total_steps(keep_running)), sub)
+        self._say_last()
+        img_t = self._arranged(img_t, input_boxes)
         assert img_t.shape == shape
         return img_t
 

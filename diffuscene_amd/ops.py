@@ -359,6 +359,42 @@ def _table_rows(*tables):
     return rows.pop()
 
 
+def _opt(t, name=None):
+    """The pointer of an optional operand, None when it is absent; checked as ``name`` when given one."""
+    if t is None:
+        return None
+    return (t if name is None else _c(t, name)).data_ptr()
+
+
+def _table_run(ca, cb, *tables):
+    """(the pointer run ca, cb, tables... of a step kernel, the rows they share).  The posterior steps pass (coef1, coef2, sigma), the
+    strided ones (sqrt_recip_ac, sqrt_recipm1_ac), the in-painting ones append (sqrt_ac, sqrt_1mac); ca / cb are absent for mean type x0."""
+    return (_opt(ca), _opt(cb)) + tuple(tb.data_ptr() for tb in tables), _table_rows(ca, cb, *tables)
+
+
+def _strided_run(step, times, times_next, coef):
+    """(the pointer run step, times, times_next, coef rows 0..2 of a strided step kernel, S): the (1,) int64 device counter, the (S,)
+    int64 pairs and the (3, S) fp32 rows [sqrt(alpha_next), c, sigma]."""
+    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
+    S = times.numel()
+    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
+    return (step.data_ptr(), times.data_ptr(), times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr()), S
+
+
+def _same_shape(what, x_t, *operands, out=None):
+    if any(o is not None and o.shape != x_t.shape for o in operands + (out,)) or not (out is None or out.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: %s operands of different shapes" % what)
+
+
+def _out_like(what, x_t, out, *operands):
+    """``out`` of a fused step, allocated when absent: it and every operand have x_t's shape, and it is contiguous."""
+    if out is None:
+        out = torch.empty_like(x_t)
+    _same_shape(what, x_t, *operands, out=out)
+    return out
+
+
 def q_sample(x0, noise, t, sqrt_ac, sqrt_1mac, want_v=False):
     _c(x0, "x0"); _c(noise, "noise"); _dev(t, "t", torch.int64)
     xt = torch.empty_like(x0)
@@ -375,13 +411,9 @@ def p_sample(x_t, model_out, noise, t, ca, cb, coef1, coef2, sigma, mean_type, c
     if out is None:
         out = torch.empty_like(x_t)
     b = x_t.shape[0]
-    _lib.check(_lib.fn("dsc_p_sample_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), t.data_ptr(),
-                                           ca.data_ptr() if ca is not None else None,
-                                           cb.data_ptr() if cb is not None else None,
-                                           coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), out.data_ptr(),
-                                           x0_out.data_ptr() if x0_out is not None else None,
-                                           mean_type, 1 if clip else 0, b, x_t.numel() // b,
-                                           _table_rows(ca, cb, coef1, coef2, sigma), stream_ptr()),
+    post, rows = _table_run(ca, cb, coef1, coef2, sigma)
+    _lib.check(_lib.fn("dsc_p_sample_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), t.data_ptr(), *post, out.data_ptr(),
+                                           _opt(x0_out), mean_type, 1 if clip else 0, b, x_t.numel() // b, rows, stream_ptr()),
                "dsc_p_sample_f32")
     return out
 
@@ -397,23 +429,14 @@ def ddim_step(x_t, model_out, noise, step, times, times_next, coef, ca, cb, sqrt
     """One DDIM step (see the C header).  ``step`` is the (1,) int64 device counter, ``times`` / ``times_next`` the (S,) int64 pairs and
     ``coef`` the (3, S) fp32 rows [sqrt(alpha_next), c, sigma]; ``noise`` is not read on the final pair (pass any tensor of x_t's shape)."""
     _c(x_t, "x_t"); _c(model_out, "model_out"); _c(noise, "noise")
-    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
-    S = times.numel()
-    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
-        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
-    if model_out.shape != x_t.shape or noise.shape != x_t.shape:
-        raise RuntimeError("diffuscene_amd: ddim_step operands of different shapes")
+    strided, S = _strided_run(step, times, times_next, coef)
+    _same_shape("ddim_step", x_t, model_out, noise)
     if out is None:
         out = torch.empty_like(x_t)
     b = x_t.shape[0]
-    _lib.check(_lib.fn("dsc_ddim_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), step.data_ptr(),
-                                            times.data_ptr(), times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
-                                            coef[2].data_ptr(), ca.data_ptr() if ca is not None else None,
-                                            cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
-                                            sqrt_recipm1_ac.data_ptr(), out.data_ptr(),
-                                            x0_out.data_ptr() if x0_out is not None else None, mean_type, b,
-                                            x_t.numel() // b, S, _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac),
-                                            stream_ptr()), "dsc_ddim_step_f32")
+    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac)
+    _lib.check(_lib.fn("dsc_ddim_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), *strided, *tabs, out.data_ptr(),
+                                            _opt(x0_out), mean_type, b, x_t.numel() // b, S, rows, stream_ptr()), "dsc_ddim_step_f32")
     return out
 
 
@@ -503,18 +526,11 @@ def p_sample_inpaint(x_t, model_out, noise, partial, noise_p, counts, t, ca, cb,
     _c(model_out, "model_out"); _c(noise, "noise")
     b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
     _scene_t(t, b)
-    if out is None:
-        out = torch.empty_like(x_t)
-    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
-        raise RuntimeError("diffuscene_amd: p_sample_inpaint operands of different shapes")
+    out = _out_like("p_sample_inpaint", x_t, out, model_out, noise)
+    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
     _lib.check(_lib.fn("dsc_p_sample_inpaint_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
-                                                   noise_p.data_ptr(), cnt.data_ptr(), t.data_ptr(),
-                                                   ca.data_ptr() if ca is not None else None,
-                                                   cb.data_ptr() if cb is not None else None,
-                                                   coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), sqrt_ac.data_ptr(),
-                                                   sqrt_1mac.data_ptr(), out.data_ptr(), mean_type, 1 if clip else 0, b, n, pmax, c,
-                                                   _table_rows(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac), stream_ptr()),
-               "dsc_p_sample_inpaint_f32")
+                                                   noise_p.data_ptr(), cnt.data_ptr(), t.data_ptr(), *post, out.data_ptr(), mean_type,
+                                                   1 if clip else 0, b, n, pmax, c, rows, stream_ptr()), "dsc_p_sample_inpaint_f32")
     return out
 
 
@@ -525,23 +541,12 @@ def ddim_inpaint_step(x_t, model_out, noise, partial, noise_p, counts, step, tim
     counts / partial as p_sample_inpaint.  See the C header."""
     _c(model_out, "model_out"); _c(noise, "noise")
     b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
-    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
-    S = times.numel()
-    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
-        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
-    if out is None:
-        out = torch.empty_like(x_t)
-    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
-        raise RuntimeError("diffuscene_amd: ddim_inpaint_step operands of different shapes")
+    strided, S = _strided_run(step, times, times_next, coef)
+    out = _out_like("ddim_inpaint_step", x_t, out, model_out, noise)
+    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
     _lib.check(_lib.fn("dsc_ddim_inpaint_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
-                                                    noise_p.data_ptr(), cnt.data_ptr(), step.data_ptr(), times.data_ptr(),
-                                                    times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
-                                                    ca.data_ptr() if ca is not None else None,
-                                                    cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
-                                                    sqrt_recipm1_ac.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
-                                                    out.data_ptr(), mean_type, b, n, pmax, c, S,
-                                                    _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac),
-                                                    stream_ptr()), "dsc_ddim_inpaint_step_f32")
+                                                    noise_p.data_ptr(), cnt.data_ptr(), *strided, *tabs, out.data_ptr(), mean_type,
+                                                    b, n, pmax, c, S, rows, stream_ptr()), "dsc_ddim_inpaint_step_f32")
     return out
 
 
@@ -592,18 +597,11 @@ def p_sample_masked(x_t, model_out, noise, known, noise_k, mask, t, ca, cb, coef
     _c(model_out, "model_out"); _c(noise, "noise")
     b, inner = _masked_args(x_t, known, noise_k, mask)
     _scene_t(t, b)
-    if out is None:
-        out = torch.empty_like(x_t)
-    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
-        raise RuntimeError("diffuscene_amd: p_sample_masked operands of different shapes")
+    out = _out_like("p_sample_masked", x_t, out, model_out, noise)
+    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
     _lib.check(_lib.fn("dsc_p_sample_masked_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
-                                                  noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(),
-                                                  ca.data_ptr() if ca is not None else None,
-                                                  cb.data_ptr() if cb is not None else None,
-                                                  coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), sqrt_ac.data_ptr(),
-                                                  sqrt_1mac.data_ptr(), out.data_ptr(), mean_type, 1 if clip else 0, b, inner,
-                                                  _table_rows(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac), stream_ptr()),
-               "dsc_p_sample_masked_f32")
+                                                  noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(), *post, out.data_ptr(), mean_type,
+                                                  1 if clip else 0, b, inner, rows, stream_ptr()), "dsc_p_sample_masked_f32")
     return out
 
 
@@ -614,23 +612,12 @@ def ddim_masked_step(x_t, model_out, noise, known, noise_k, mask, step, times, t
     See the C header."""
     _c(model_out, "model_out"); _c(noise, "noise")
     b, inner = _masked_args(x_t, known, noise_k, mask)
-    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
-    S = times.numel()
-    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
-        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
-    if out is None:
-        out = torch.empty_like(x_t)
-    if model_out.shape != x_t.shape or noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous():
-        raise RuntimeError("diffuscene_amd: ddim_masked_step operands of different shapes")
+    strided, S = _strided_run(step, times, times_next, coef)
+    out = _out_like("ddim_masked_step", x_t, out, model_out, noise)
+    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
     _lib.check(_lib.fn("dsc_ddim_masked_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
-                                                   noise_k.data_ptr(), mask.data_ptr(), step.data_ptr(), times.data_ptr(),
-                                                   times_next.data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
-                                                   ca.data_ptr() if ca is not None else None,
-                                                   cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
-                                                   sqrt_recipm1_ac.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(),
-                                                   out.data_ptr(), mean_type, b, inner, S,
-                                                   _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac),
-                                                   stream_ptr()), "dsc_ddim_masked_step_f32")
+                                                   noise_k.data_ptr(), mask.data_ptr(), *strided, *tabs, out.data_ptr(), mean_type,
+                                                   b, inner, S, rows, stream_ptr()), "dsc_ddim_masked_step_f32")
     return out
 
 
@@ -709,17 +696,12 @@ def p_sample_cfg(x_t, model_out, scale, noise, t, ca, cb, coef1, coef2, sigma, m
     _c(x_t, "x_t"); _c(noise, "noise")
     b, inner = _cfg_args(x_t, model_out, scale)
     _scene_t(t, b)
-    if out is None:
-        out = torch.empty_like(x_t)
-    if noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous() or (x0_out is not None and x0_out.shape != x_t.shape):
-        raise RuntimeError("diffuscene_amd: p_sample_cfg operands of different shapes")
+    out = _out_like("p_sample_cfg", x_t, out, noise, x0_out)
+    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out), _opt(x0_out, "x0_out"))
+    post, rows = _table_run(ca, cb, coef1, coef2, sigma)
     _lib.check(_lib.fn("dsc_p_sample_cfg_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(), t.data_ptr(),
-                                               ca.data_ptr() if ca is not None else None,
-                                               cb.data_ptr() if cb is not None else None,
-                                               coef1.data_ptr(), coef2.data_ptr(), sigma.data_ptr(), out.data_ptr(),
-                                               _cfg_dup(x_dup, x_t, out), _c(x0_out, "x0_out").data_ptr() if x0_out is not None else None,
-                                               mean_type, 1 if clip else 0, b, inner, _table_rows(ca, cb, coef1, coef2, sigma),
-                                               stream_ptr()), "dsc_p_sample_cfg_f32")
+                                               *post, *extra, mean_type, 1 if clip else 0, b, inner, rows, stream_ptr()),
+               "dsc_p_sample_cfg_f32")
     return out
 
 
@@ -729,22 +711,12 @@ def ddim_cfg_step(x_t, model_out, scale, noise, step, times, times_next, coef, c
     final pair).  Bit-identical to cfg_combine followed by ddim_step.  See the C header."""
     _c(x_t, "x_t"); _c(noise, "noise")
     b, inner = _cfg_args(x_t, model_out, scale)
-    _dev(step, "step", torch.int64); _dev(times, "times", torch.int64); _dev(times_next, "times_next", torch.int64); _c(coef, "coef")
-    S = times.numel()
-    if times_next.numel() != S or tuple(coef.shape) != (3, S) or not (times.is_contiguous() and times_next.is_contiguous()):
-        raise RuntimeError("diffuscene_amd: DDIM tables must be (S,) int64 pairs and (3, S) coefficients")
-    if out is None:
-        out = torch.empty_like(x_t)
-    if noise.shape != x_t.shape or out.shape != x_t.shape or not out.is_contiguous() or (x0_out is not None and x0_out.shape != x_t.shape):
-        raise RuntimeError("diffuscene_amd: ddim_cfg_step operands of different shapes")
-    _lib.check(_lib.fn("dsc_ddim_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
-                                                step.data_ptr(), times.data_ptr(), times_next.data_ptr(), coef[0].data_ptr(),
-                                                coef[1].data_ptr(), coef[2].data_ptr(), ca.data_ptr() if ca is not None else None,
-                                                cb.data_ptr() if cb is not None else None, sqrt_recip_ac.data_ptr(),
-                                                sqrt_recipm1_ac.data_ptr(), out.data_ptr(), _cfg_dup(x_dup, x_t, out),
-                                                _c(x0_out, "x0_out").data_ptr() if x0_out is not None else None, mean_type, b, inner, S,
-                                                _table_rows(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), stream_ptr()),
-               "dsc_ddim_cfg_step_f32")
+    strided, S = _strided_run(step, times, times_next, coef)
+    out = _out_like("ddim_cfg_step", x_t, out, noise, x0_out)
+    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out), _opt(x0_out, "x0_out"))
+    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac)
+    _lib.check(_lib.fn("dsc_ddim_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(), *strided, *tabs,
+                                                *extra, mean_type, b, inner, S, rows, stream_ptr()), "dsc_ddim_cfg_step_f32")
     return out
 
 

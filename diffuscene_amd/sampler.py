@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from .networks.denoise_net import Unet1D
+from .networks.diffusion_ddpm import restore_given_rows
 
 _MEAN = {"eps": ops.MEAN_EPS, "x0": ops.MEAN_X0, "v": ops.MEAN_V}
 
@@ -314,10 +315,7 @@ class _Ragged:
             self._overwrite(self.pnoise.head())
 
     def _restore(self, out):
-        if not self.fused:
-            given = torch.arange(self.pmax, device=out.device)[None, :, None] < self.counts[:, None, None]
-            out[:, :self.pmax, :] = torch.where(given, self.partial, out[:, :self.pmax, :])
-        return out
+        return out if self.fused else restore_given_rows(out, self.partial, self.counts)
 
 
 class _Masked:
@@ -640,6 +638,21 @@ def _head(buffer, n):
     return None if buffer is None else buffer[:n]
 
 
+def _replay_check(what, n_main, shape=None, n_partial=None, pshape=None):
+    """check(noise_fn) of a front end: the NoiseReplay holds ``n_main`` main draws (of ``shape``, where the loop has always checked it)
+    and, for a loop with a given part, ``n_partial`` draws of ``pshape`` for it; ValueError otherwise."""
+    def check(nf):
+        ok = nf.buffer.shape[0] >= n_main and (shape is None or tuple(nf.buffer.shape[1:]) == tuple(shape))
+        if n_partial is not None:
+            ok = ok and nf.partial_buffer is not None and nf.partial_buffer.shape[0] >= n_partial \
+                and tuple(nf.partial_buffer.shape[1:]) == tuple(pshape)
+        if not ok:
+            raise ValueError("%s replays %d main draws%s%s" % (
+                what, n_main, "" if shape is None else " of shape %s" % (tuple(shape),),
+                "" if n_partial is None else " and %d draws of shape %s for the given part" % (n_partial, tuple(pshape))))
+    return check
+
+
 def graph_sample_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps,
                       noise_fn=torch.randn, partial_boxes=None):
     pshape = None if partial_boxes is None else tuple(partial_boxes.shape)
@@ -656,15 +669,10 @@ def graph_ddim_sample_loop(diff, denoise_fn, shape, device, condition, condition
                            noise_fn=torch.randn):
     """ddim_sample_loop as replayed hipGraphs; bit-identical to the eager loop (same kernels, same draws in the same order)."""
     S = int(sampling_timesteps)
-
-    def check(nf):
-        if nf.buffer.shape[0] < S:
-            raise ValueError("NoiseReplay holds %d draws, DDIM with S = %d makes %d" % (nf.buffer.shape[0], S, S))
-
     return _cached_loop(
         "graph_ddim_sample_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim", S),
         lambda model, dev, replay: _DDIMGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, buf), check=check, ddim=(S, eta))
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, buf), check=_replay_check("DDIM with S = %d" % S, S), ddim=(S, eta))
 
 
 def graph_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps,
@@ -674,20 +682,13 @@ def graph_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condi
     holds Pmax but not the counts."""
     B, N, C = shape
     pmax = partial_boxes.shape[1]
-
-    def check(nf):
-        if nf.partial_buffer is None or nf.buffer.shape[0] < total_steps + 1 or nf.partial_buffer.shape[0] < total_steps \
-                or tuple(nf.partial_buffer.shape[1:]) != (B, pmax, C):
-            raise ValueError("ragged completion replays %d main draws (B, N, C) and %d partial draws (B, Pmax, C)"
-                             % (total_steps + 1, total_steps))
-
     return _cached_loop(
         "graph_complete_ragged_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
         ("ragged", bool(fused), pmax, bool(clip_denoised)),
         lambda model, dev, replay: _RaggedCompleteGraph(diff, model, tuple(shape), pmax, dev, condition, condition_cross, clip_denoised,
                                                         replay, fused),
         lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, partial_boxes, counts, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
-        check=check)
+        check=_replay_check("ragged completion", total_steps + 1, None, total_steps, (B, pmax, C)))
 
 
 def graph_ddim_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta,
@@ -698,23 +699,12 @@ def graph_ddim_complete_ragged_loop(diff, denoise_fn, shape, device, condition, 
     B, N, C = shape
     S = int(sampling_timesteps)
     pmax = partial_boxes.shape[1]
-
-    def check(nf):
-        if nf.partial_buffer is None or nf.buffer.shape[0] < S or nf.partial_buffer.shape[0] < S \
-                or tuple(nf.partial_buffer.shape[1:]) != (B, pmax, C):
-            raise ValueError("strided ragged completion replays %d main draws (B, N, C) and %d partial draws (B, Pmax, C)" % (S, S))
-
     return _cached_loop(
         "graph_ddim_complete_ragged_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
         ("ddim_ragged", S, bool(fused), pmax),
         lambda model, dev, replay: _DDIMCompleteGraph(diff, model, tuple(shape), pmax, dev, condition, condition_cross, S, replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, partial_boxes, counts, buf, pbuf), check=check, ddim=(S, eta))
-
-
-def _masked_replay_check(noise_fn, shape, n_main, n_known, what):
-    if noise_fn.partial_buffer is None or noise_fn.buffer.shape[0] < n_main or noise_fn.partial_buffer.shape[0] < n_known \
-            or tuple(noise_fn.partial_buffer.shape[1:]) != tuple(shape) or tuple(noise_fn.buffer.shape[1:]) != tuple(shape):
-        raise ValueError("%s replays %d main draws and %d known-draws, all of shape %s" % (what, n_main, n_known, tuple(shape)))
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, partial_boxes, counts, buf, pbuf),
+        check=_replay_check("strided ragged completion", S, None, S, (B, pmax, C)), ddim=(S, eta))
 
 
 def graph_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps, noise_fn=torch.randn,
@@ -726,7 +716,7 @@ def graph_masked_loop(diff, denoise_fn, shape, device, condition, condition_cros
         "graph_masked_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("masked", bool(clip_denoised)),
         lambda model, dev, replay: _MaskedGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay),
         lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, known, mask, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
-        check=lambda nf: _masked_replay_check(nf, shape, total_steps + 1, total_steps, "the masked loop"))
+        check=_replay_check("the masked loop", total_steps + 1, shape, total_steps, shape))
 
 
 def graph_ddim_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta, noise_fn=torch.randn,
@@ -738,7 +728,7 @@ def graph_ddim_masked_loop(diff, denoise_fn, shape, device, condition, condition
         "graph_ddim_masked_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim_masked", S),
         lambda model, dev, replay: _DDIMMaskedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay),
         lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, known, mask, buf, pbuf),
-        check=lambda nf: _masked_replay_check(nf, shape, S, S, "the strided masked loop"), ddim=(S, eta))
+        check=_replay_check("the strided masked loop", S, shape, S, shape), ddim=(S, eta))
 
 
 def graph_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, clip_denoised, total_steps,
@@ -746,16 +736,13 @@ def graph_guided_loop(diff, denoise_fn, shape, device, condition, condition_cros
     """p_sample_loop_guided as a replayed hipGraph; bit-identical to the eager loop (same expressions, same draws in the same order, the
     same generator state afterwards).  ``condition`` / ``condition_cross`` arrive at 2 B (GaussianDiffusion._guided_inputs), ``scale`` is
     the (B,) f32 device vector of ops.guidance_scales: the cache key holds the shape, not the scales."""
-    def check(nf):
-        if nf.buffer.shape[0] < total_steps + 1 or tuple(nf.buffer.shape[1:]) != tuple(shape):
-            raise ValueError("the guided loop replays %d draws of shape %s" % (total_steps + 1, tuple(shape)))
-
     return _cached_loop(
         "graph_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
         ("guided", bool(fused), bool(clip_denoised)),
         lambda model, dev, replay: _GuidedStepGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay,
                                                     fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, scale, _head(buf, total_steps + 1)), mult=2, check=check)
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, scale, _head(buf, total_steps + 1)), mult=2,
+        check=_replay_check("the guided loop", total_steps + 1, shape))
 
 
 def graph_ddim_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, sampling_timesteps, eta,
@@ -763,15 +750,11 @@ def graph_ddim_guided_loop(diff, denoise_fn, shape, device, condition, condition
     """ddim_guided_loop as replayed hipGraphs; bit-identical to the eager loop.  The cache key holds the shape and S; it holds neither
     eta nor the scales."""
     S = int(sampling_timesteps)
-
-    def check(nf):
-        if nf.buffer.shape[0] < S or tuple(nf.buffer.shape[1:]) != tuple(shape):
-            raise ValueError("the guided strided loop replays %d draws of shape %s" % (S, tuple(shape)))
-
     return _cached_loop(
         "graph_ddim_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim_guided", S, bool(fused)),
         lambda model, dev, replay: _DDIMGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, buf), mult=2, check=check, ddim=(S, eta))
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, buf), mult=2, check=_replay_check("the guided strided loop", S, shape),
+        ddim=(S, eta))
 
 
 def _plan_key(g):
