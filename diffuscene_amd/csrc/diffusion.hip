@@ -4,6 +4,7 @@
 // results are bit-identical to the fp32 CPU path on the same inputs.
 #define DSC_BAD_INDEX_COUNTER
 #include "dsc_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -471,6 +472,101 @@ __global__ __launch_bounds__(192) void postfilter_compact_kernel(const float* __
     if (tid == 0) counts[b] = total;
 }
 
+// Per-scene counter-based noise (include/diffuscene_hip.h, diffuscene_amd/scene_noise.py): Philox4x32-10 on the counter
+// (q, stream, draw lo, draw hi) under the key (seed lo, seed hi), q the scene's own quad index -- nothing of the batch enters.
+struct Quad { uint32_t r[4]; };
+
+__device__ __forceinline__ Quad philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    return Quad{{c0, c1, c2, c3}};
+}
+
+// u = (r >> 8) * 2^-24 + 2^-25: the product is exact, the sum is rounded to nearest even above 1/2 (there u needs 25 bits), so u lies
+// in (0, 1] and u == 1 gives rho == 0, never an infinity.
+__device__ __forceinline__ float unit_open(uint32_t r) {
+    const float p = (float)(r >> 8) * 5.9604644775390625e-08f;
+    return p + 2.98023223876953125e-08f;
+}
+
+// Box-Muller on one pair of words, full-precision logf / sinf / cosf; every product a statement of its own.
+__device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& z0, float& z1) {
+    const float l = logf(unit_open(ra));
+    const float m = -2.0f * l;
+    const float rho = sqrtf(m);
+    const float theta = 6.2831853071795864769f * unit_open(rb);
+    const float c = cosf(theta), s = sinf(theta);
+    z0 = rho * c;
+    z1 = rho * s;
+}
+
+__device__ __forceinline__ void store_word(float* p, uint32_t r, float z) { *p = z; }
+__device__ __forceinline__ void store_word(uint32_t* p, uint32_t r, float z) { *p = r; }
+
+// One thread per Philox block = four consecutive elements of one scene; the grid is flat over B * quads (I: the index type, 32 bits
+// where the count fits).  VEC4 (per_scene % 4 == 0 and a 16-byte-aligned out): every scene base is 16-byte aligned and a lane stores its
+// quad as one dwordx4, lane i at base + 16 i -- the coalesced form.  Otherwise a scene's base is odd and a lane stores its live elements
+// as dwords: the four stores of a wave interleave inside the same 1 KiB span, so every cache line they touch is completed by that wave.
+// T = float: the normals; T = uint32_t: the raw words (the host-side probe).  *draw is read, never written.
+template <typename T, typename I, bool VEC4>
+__global__ __launch_bounds__(256) void scene_noise_kernel(T* __restrict__ out, const int64_t* __restrict__ seeds,
+                                                          const int64_t* __restrict__ draw, uint32_t stream, I total, I quads,
+                                                          int64_t per_scene) {
+    const I idx = (I)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const I b = idx / quads, q = idx - b * quads;
+    const uint64_t seed = (uint64_t)seeds[b], d = (uint64_t)draw[0];
+    const Quad w = philox4x32_10((uint32_t)q, stream, (uint32_t)d, (uint32_t)(d >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (std::is_same<T, float>::value) {
+        box_muller(w.r[0], w.r[1], z[0], z[1]);
+        box_muller(w.r[2], w.r[3], z[2], z[3]);
+    }
+    const int64_t e = (int64_t)q * 4;
+    T* o = out + (int64_t)b * per_scene + e;
+    if constexpr (VEC4) {
+        if constexpr (std::is_same<T, float>::value) *reinterpret_cast<float4*>(o) = make_float4(z[0], z[1], z[2], z[3]);
+        else *reinterpret_cast<uint4*>(o) = make_uint4(w.r[0], w.r[1], w.r[2], w.r[3]);
+    } else {
+        const int64_t left = per_scene - e;
+        const int live = left < 4 ? (int)left : 4;      // the last quad of a scene: per_scene & 3 live lanes
+#pragma unroll
+        for (int lane = 0; lane < 4; ++lane)
+            if (lane < live) store_word(o + lane, w.r[lane], z[lane]);
+    }
+}
+
+template <typename T>
+int launch_scene_noise(T* out, const int64_t* seeds, const int64_t* draw, int64_t stream, int64_t B, int64_t per_scene,
+                       dsc_stream_t hip_stream) {
+    if (!out || !seeds || !draw || stream < 0 || stream > 0xffffffffll || B < 0 || per_scene < 0) return DSC_EINVAL;
+    if (B == 0 || per_scene == 0) return 0;
+    if (per_scene > (1ll << 32)) return DSC_ERANGE;
+    const int64_t quads = (per_scene + 3) / 4;                          // <= 2^30
+    if (B > (((1ll << 31) - 1) * 256) / quads) return DSC_ERANGE;       // the flat grid: fewer than 2^31 blocks of 256
+    const int64_t total = B * quads;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    const hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const bool vec4 = per_scene % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const uint32_t st = (uint32_t)stream;
+    DSC_CLEAR_STALE_ERROR();
+    if (total <= 0xffffff00ll) {                                        // no 32-bit index of the last block wraps
+        const uint32_t t32 = (uint32_t)total, q32 = (uint32_t)quads;
+        if (vec4) hipLaunchKernelGGL((scene_noise_kernel<T, uint32_t, true>), grid, block, 0, s, out, seeds, draw, st, t32, q32, per_scene);
+        else hipLaunchKernelGGL((scene_noise_kernel<T, uint32_t, false>), grid, block, 0, s, out, seeds, draw, st, t32, q32, per_scene);
+    } else {
+        if (vec4) hipLaunchKernelGGL((scene_noise_kernel<T, int64_t, true>), grid, block, 0, s, out, seeds, draw, st, total, quads, per_scene);
+        else hipLaunchKernelGGL((scene_noise_kernel<T, int64_t, false>), grid, block, 0, s, out, seeds, draw, st, total, quads, per_scene);
+    }
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
 // ca / cb are read for every mean type but x0.
 inline bool bad_mean_args(int32_t mean_type, const float* ca, const float* cb) {
     return mean_type < DSC_MEAN_EPS || mean_type > DSC_MEAN_V || (mean_type != DSC_MEAN_X0 && (!ca || !cb));
@@ -728,6 +824,16 @@ extern "C" int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y,
     hipLaunchKernelGGL(scene_gate_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream), x, keep, y, inner);
     DSC_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int dsc_scene_randn_f32(float* out, const int64_t* seeds, const int64_t* draw, int64_t stream, int64_t b,
+                                   int64_t per_scene, dsc_stream_t hip_stream) {
+    return launch_scene_noise(out, seeds, draw, stream, b, per_scene, hip_stream);
+}
+
+extern "C" int dsc_scene_philox_u32(uint32_t* out, const int64_t* seeds, const int64_t* draw, int64_t stream, int64_t b,
+                                    int64_t per_scene, dsc_stream_t hip_stream) {
+    return launch_scene_noise(out, seeds, draw, stream, b, per_scene, hip_stream);
 }
 
 unsigned dsc_bad_index_diffusion(bool reset) { return dsc_read_bad_index_count(reset); }

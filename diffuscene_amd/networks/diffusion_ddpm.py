@@ -19,6 +19,8 @@ each a generator of states (x_T, then the state after every step), and two indep
                    written over the state in place BEFORE every model call, restored in the last state; x_T is cloned only if it is
                    written
   the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine)
+A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
+part -- and then numbers its own draws: main stream x_T = 0, 1, 2, ..., given stream 0, 1, 2, ... (scene_noise.py).
 The twelve public loops validate, hand over to the captured loop under _use_graph, build the two objects and run a core: nothing given --
 p_sample_loop, _trajectory, _arrange / ddim_sample_loop, ddim_arrange_loop (both arrange loops on the sub-shape); guided --
 p_sample_loop_guided / ddim_guided_loop; rows -- p_sample_loop_complete, _complete_ragged / ddim_complete_ragged_loop; mask --
@@ -33,6 +35,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..scene_noise import SceneNoise
 from .loss import axis_aligned_bbox_overlaps_3d  # noqa: F401  (re-exported: the reference module exposes it, :16)
 
 ModelPrediction = namedtuple('ModelPrediction', ['pred_noise', 'pred_x_start'])
@@ -156,6 +159,12 @@ def _guided_model(denoise_fn, cond2, cross2, scale):
     """The guided model call: the denoiser at 2 B on the same x and t in both halves (conditions of _guided_inputs), then
     m = u + scale[b] * (c - u) (dsc_cfg_combine_f32)."""
     return lambda x, t_: ops.cfg_combine(denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), cond2, cross2).contiguous(), scale)
+
+
+def _arm(noise_fn, given):
+    """A SceneNoise starts a new loop here: its draw numbers go back to 0 and it learns whether the loop draws for a given part."""
+    if isinstance(noise_fn, SceneNoise):
+        noise_fn.arm(given.inplace)
 
 
 def _last(states, shape):
@@ -414,6 +423,7 @@ class GaussianDiffusion:
     # the two eager loops (module docstring); a state that a given part overwrites in place stays the same tensor until the update
     def _t_states(self, model, shape, device, noise_fn, clip_denoised, total_steps, given=_FREE, draw=None):
         """The T-step loop, reference :355-371: fill t_, [overwrite the given part], model call, one draw, ops.p_sample -- at t == 0 too."""
+        _arm(noise_fn, given)
         x = noise_fn(size=shape, dtype=torch.float, device=device)
         if given.inplace:
             x = x.clone()                       # a caller's tensor (a row of a NoiseReplay buffer) is not written
@@ -431,6 +441,7 @@ class GaussianDiffusion:
         pairs = dtab[0]
         step = torch.zeros((1,), dtype=torch.int64, device=device)
         t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(pairs[0][0])
+        _arm(noise_fn, given)
         x = noise_fn(size=shape, dtype=torch.float, device=device)
         if given.inplace:
             x = x.clone()
@@ -870,10 +881,11 @@ def _check_ddim(num_timesteps, sampling_timesteps, ddim_sampling_eta):
 def _use_graph(graph, noise_fn, denoise_fn=None):
     """Does this reverse loop run as the replayed hipGraph step (sampler.py)?  ``graph=True`` / ``False`` decide; None (what the
     reference's call sites pass) = yes by default since round 6 -- the captured loop is bit-identical to the eager one and not
-    host-bound at small batches -- unless DSC_GRAPH=0, a custom ``noise_fn`` (its draws cannot be captured) or a ``denoise_fn`` that
-    is not DiffusionPoint._denoise over this package's Unet1D."""
+    host-bound at small batches -- unless DSC_GRAPH=0, a custom ``noise_fn`` (its draws cannot be captured; a NoiseReplay and a
+    SceneNoise can: the graph walks a buffer / counts the draws on the device) or a ``denoise_fn`` that is not DiffusionPoint._denoise
+    over this package's Unet1D."""
     from ..sampler import NoiseReplay
-    capturable = noise_fn is torch.randn or isinstance(noise_fn, NoiseReplay)
+    capturable = noise_fn is torch.randn or isinstance(noise_fn, (NoiseReplay, SceneNoise))
     if graph is None:
         if os.environ.get("DSC_GRAPH", "1") == "0" or not capturable:
             return False

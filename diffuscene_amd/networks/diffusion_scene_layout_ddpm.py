@@ -50,6 +50,10 @@ def _two_layer(n_in, n_out):
 
 
 class DiffusionSceneLayout_DDPM(Module):
+    # The reference's call sites pass ``batch_seeds=torch.arange(i, i + 1)`` for scene i and its sample() never reads it; this drop-in
+    # ignores it too (the seeded-parity contract rests on that) unless a caller opts in: True makes a non-None ``batch_seeds`` the
+    # ``scene_seeds`` of that call, so the unchanged scripts produce, scene by scene, what generate_layout_batched(scene_seeds=range(n)) does.
+    honour_batch_seeds = False
 
     def __init__(self, n_classes, feature_extractor, config):
         super().__init__()
@@ -268,9 +272,23 @@ class DiffusionSceneLayout_DDPM(Module):
         return SceneGateFn.apply(condition_cross, keep)
 
     # ------------------------------------------------------------------------------------ sampling
+    def _seeded(self, scene_seeds, batch_seeds, batch_size, device):
+        """The noise keyword of a loop call: none at all without seeds -- that call stays what it was --, else a SceneNoise over the
+        checked seeds (ops.scene_seeds: ValueError before anything is drawn).  ``scene_seeds``: one int in [0, 2**63) per scene; scene
+        b of the call is then a function of its seed, its own inputs, the model and the loop kind -- not of the batch size, its
+        position, the other scenes or earlier calls (up to the GEMM dispatch of that batch size) --, the device
+        generator is left untouched, and repeated seeds give identical scenes."""
+        if scene_seeds is None and self.honour_batch_seeds:
+            scene_seeds = batch_seeds
+        if scene_seeds is None:
+            return {}
+        from .. import ops
+        from ..scene_noise import SceneNoise
+        return dict(noise_fn=SceneNoise(ops.scene_seeds(scene_seeds, batch_size, device), device))
+
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
                input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
-               sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None):
+               sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
@@ -280,13 +298,16 @@ class DiffusionSceneLayout_DDPM(Module):
         ``guidance_scale`` (None: the plain conditional model, this method as it was): a float or ``batch_size`` per-scene values w, the
         classifier-free guidance scale of a text-conditioned model -- every step uses u + w (c - u), c the denoiser on the text features
         and u the denoiser on the null condition (condition_cross == 0) (``gen_samples_guided`` / ``gen_samples_guided_ddim`` with
-        ``sampling_timesteps``).  Generation only; needs ``text``."""
+        ``sampling_timesteps``).  Generation only; needs ``text``.
+        ``scene_seeds`` (None: the device generator, this method as it was): one seed per scene, see ``_seeded``; combines with every
+        other keyword.  ``batch_seeds`` stays accepted and ignored (``honour_batch_seeds``)."""
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
                                       "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
         device = room_mask.device
+        seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept: it advances the CPU RNG (:232)
         padded = None
         if self.room_partial_condition:
@@ -301,12 +322,12 @@ class DiffusionSceneLayout_DDPM(Module):
             print('scene arrangement sampling')
             return self.diffusion.arrange_samples(noise.shape, device, condition=condition,
                                                   condition_cross=condition_cross, clip_denoised=clip_denoised,
-                                                  input_boxes=input_boxes)
+                                                  input_boxes=input_boxes, **seeded)
         if partial_boxes is not None:
             print('scene completion sampling')
             return self.diffusion.complete_samples(noise.shape, device, condition=condition,
                                                    condition_cross=condition_cross, clip_denoised=clip_denoised,
-                                                   partial_boxes=partial_boxes)
+                                                   partial_boxes=partial_boxes, **seeded)
         print('unconditional / conditional generation sampling')
         if guidance_scale is not None:
             if condition_cross is None or condition_cross.dim() != 3:
@@ -318,18 +339,18 @@ class DiffusionSceneLayout_DDPM(Module):
             if sampling_timesteps is not None:
                 return self.diffusion.gen_samples_guided_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                               guidance_scale=scale, sampling_timesteps=sampling_timesteps,
-                                                              ddim_sampling_eta=ddim_sampling_eta)
+                                                              ddim_sampling_eta=ddim_sampling_eta, **seeded)
             return self.diffusion.gen_samples_guided(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                                     guidance_scale=scale, clip_denoised=clip_denoised)
+                                                     guidance_scale=scale, clip_denoised=clip_denoised, **seeded)
         if sampling_timesteps is not None:
             return self.diffusion.gen_samples_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                    clip_denoised=clip_denoised, sampling_timesteps=sampling_timesteps,
-                                                   ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj))
+                                                   ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj), **seeded)
         if ret_traj:
             return self.diffusion.gen_sample_traj(noise.shape, device, freq=freq, condition=condition,
-                                                  condition_cross=condition_cross, clip_denoised=clip_denoised)
+                                                  condition_cross=condition_cross, clip_denoised=clip_denoised, **seeded)
         return self.diffusion.gen_samples(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                          clip_denoised=clip_denoised)
+                                          clip_denoised=clip_denoised, **seeded)
 
     def _check_guidance(self, text, partial_boxes=None, input_boxes=None, ret_traj=False):
         """The refusals of ``guidance_scale``, before anything is computed or drawn."""
@@ -346,25 +367,25 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
                         clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                        ddim_sampling_eta=0.0, guidance_scale=None):
+                        ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
                               clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
-                              **_guidance_kwargs(guidance_scale))
+                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def generate_layout_progressive(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False,
                                     ddim=False, clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False,
-                                    num_step=100, guidance_scale=None):
+                                    num_step=100, guidance_scale=None, scene_seeds=None):
         """``guidance_scale``: the guided loops keep no trajectory, so the guided call returns the final scenes under the key of the
         last step, ``{0: dict}``."""
         if guidance_scale is not None:
             self._check_guidance(text)
             samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ddim=ddim, clip_denoised=clip_denoised,
-                                  batch_seeds=batch_seeds, guidance_scale=guidance_scale)
+                                  batch_seeds=batch_seeds, guidance_scale=guidance_scale, **_seed_kwargs(scene_seeds))
             return {0: self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)}
         traj = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
-                           clip_denoised=clip_denoised, batch_seeds=batch_seeds, freq=num_step)[1:]
+                           clip_denoised=clip_denoised, batch_seeds=batch_seeds, freq=num_step, **_seed_kwargs(scene_seeds))[1:]
         return {num_step * i: self.delete_empty_from_network_samples(s, device=device, keep_empty=keep_empty)
                 for i, s in enumerate(traj)}
 
@@ -373,7 +394,8 @@ class DiffusionSceneLayout_DDPM(Module):
         from .diffusion_ddpm import _check_ddim
         return _check_ddim(int(self.config["diffusion_kwargs"].get("time_num", 1000)), sampling_timesteps, ddim_sampling_eta)
 
-    def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta):
+    def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta,
+                          seeded={}):
         """The strided completion call behind complete_scene / complete_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``complete_samples_ragged_ddim``."""
         device = room_mask.device
@@ -384,9 +406,11 @@ class DiffusionSceneLayout_DDPM(Module):
         print('scene completion sampling')
         return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                            condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
-                                                           sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+                                                           sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                                           **seeded)
 
-    def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta):
+    def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta,
+                         seeded={}):
         """The strided re-arrangement call behind arrange_scene / arrange_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``arrange_samples_ddim``."""
         device = room_mask.device
@@ -397,35 +421,38 @@ class DiffusionSceneLayout_DDPM(Module):
         print('scene arrangement sampling')
         return self.diffusion.arrange_samples_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                    condition_cross=condition_cross, input_boxes=input_boxes,
-                                                   sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+                                                   sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, **seeded)
 
     @torch.no_grad()
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                       ddim_sampling_eta=0.0):
+                       ddim_sampling_eta=0.0, scene_seeds=None):
         """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
         every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
         x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part."""
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
-                              ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds)
+                              ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds,
+                              **_seed_kwargs(scene_seeds))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene(self, room_mask, num_points, point_dim, input_boxes, batch_size=1, ret_traj=False, ddim=False,
                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                      ddim_sampling_eta=0.0):
+                      ddim_sampling_eta=0.0, scene_seeds=None):
         """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop."""
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
-            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta)
+            seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, ret_traj=ret_traj,
-                              ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds)
+                              ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_seed_kwargs(scene_seeds))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     # ------------------------------------------------------------------------------------ post-filter
@@ -483,12 +510,13 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
                                 batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                                guidance_scale=None):
+                                guidance_scale=None, scene_seeds=None):
         """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own.
-        ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``)."""
+        ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``).  ``scene_seeds``: one seed per
+        scene (``_seeded``): scene b can then be regenerated alone, or the batch split over calls and devices."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
-                              **_guidance_kwargs(guidance_scale))
+                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
@@ -537,7 +565,7 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
                                clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
-                               ddim_sampling_eta=0.0):
+                               ddim_sampling_eta=0.0, scene_seeds=None):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
@@ -550,10 +578,11 @@ class DiffusionSceneLayout_DDPM(Module):
         device = room_mask.device
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
@@ -562,12 +591,12 @@ class DiffusionSceneLayout_DDPM(Module):
         condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
         print('scene completion sampling')
         samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts)
+                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
-                              batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
+                              batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0, scene_seeds=None):
         """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
         each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead."""
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
@@ -580,10 +609,11 @@ class DiffusionSceneLayout_DDPM(Module):
             raise ValueError("input_boxes: every scene must be (%d, %d), got %s" % (num_points, point_dim, tuple(input_boxes.shape[1:])))
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
-            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta)
+            seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, clip_denoised=clip_denoised,
-                              batch_seeds=batch_seeds)
+                              batch_seeds=batch_seeds, **_seed_kwargs(scene_seeds))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     # ------------------------------------------------------------------------------------ element-wise in-painting
@@ -646,7 +676,8 @@ class DiffusionSceneLayout_DDPM(Module):
 
     @torch.no_grad()
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
-                              clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0):
+                              clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
+                              scene_seeds=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -663,6 +694,7 @@ class DiffusionSceneLayout_DDPM(Module):
         if batch_size is None:
             batch_size = len(boxes) if isinstance(boxes, (list, tuple)) else int(boxes.shape[0])
         B, N, C = int(batch_size), int(num_points), int(point_dim)
+        seeded = self._seeded(scene_seeds, batch_seeds, B, device)
         if isinstance(boxes, (list, tuple)):
             if len(boxes) != B:
                 raise ValueError("boxes lists %d scenes for a batch of %d" % (len(boxes), B))
@@ -692,10 +724,10 @@ class DiffusionSceneLayout_DDPM(Module):
         print('scene in-painting sampling')
         if sampling_timesteps is not None:
             samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
-                                                          known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta)
+                                                          known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded)
         else:
             samples = self.diffusion.inpaint_samples((B, N, C), device, condition=condition, condition_cross=condition_cross,
-                                                     clip_denoised=clip_denoised, known=known, mask=mask)
+                                                     clip_denoised=clip_denoised, known=known, mask=mask, **seeded)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -713,6 +745,11 @@ def _ddim_kwargs(sampling_timesteps, ddim_sampling_eta):
     if sampling_timesteps is None:
         return {}
     return dict(sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta)
+
+
+def _seed_kwargs(scene_seeds):
+    """The seed keyword ``sample`` receives: none at all without seeds, so that call stays what it was."""
+    return {} if scene_seeds is None else dict(scene_seeds=scene_seeds)
 
 
 def _guidance_kwargs(guidance_scale):

@@ -650,6 +650,76 @@ def guidance_scales(scale, b, device):
     return torch.tensor(host, dtype=torch.float32).to(device).contiguous()
 
 
+def scene_seeds(value, batch_size, device):
+    """The per-scene seeds of the seeded loops as a contiguous (batch_size,) int64 tensor on ``device``.  ``value``: a sequence (list,
+    tuple, range, numpy array) or a 1-d integer tensor of exactly ``batch_size`` Python / numpy ints in [0, 2**63).  ValueError on
+    bools, floats, a wrong length and values that are negative or too large.  Repeated seeds are allowed: two scenes with the same seed
+    and the same inputs are the same scene."""
+    b = int(batch_size)
+    bad = "scene_seeds must be a sequence or 1-d integer tensor of %d ints in [0, 2**63), got %r" % (b, value)
+    if isinstance(value, torch.Tensor):
+        if value.dim() != 1 or value.dtype.is_floating_point or value.dtype.is_complex or value.dtype == torch.bool:
+            raise ValueError("scene_seeds: a tensor must be (%d,) of integers, got %s %s" % (b, tuple(value.shape), value.dtype))
+        host = value.tolist()
+    elif value is None or isinstance(value, (str, bytes, numbers.Number)):
+        raise ValueError(bad)
+    else:
+        try:
+            host = [v.item() if hasattr(v, "item") and getattr(v, "ndim", 0) == 0 else v for v in value]
+        except TypeError:
+            raise ValueError(bad) from None
+    if len(host) != b:
+        raise ValueError("scene_seeds has %d entries for a batch of %d scenes" % (len(host), b))
+    for i, v in enumerate(host):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+            raise ValueError("scene_seeds: scene %d: %r is not an integer" % (i, v))
+        if not 0 <= int(v) < 2 ** 63:
+            raise ValueError("scene_seeds: scene %d: %r outside [0, 2**63)" % (i, v))
+    return torch.tensor([int(v) for v in host], dtype=torch.int64).to(device).contiguous()
+
+
+def _scene_noise_args(seeds, draw, stream, shape):
+    _dev(seeds, "seeds", torch.int64); _dev(draw, "draw", torch.int64)
+    shape = tuple(int(s) for s in shape)
+    if len(shape) < 1 or seeds.dim() != 1 or seeds.shape[0] != shape[0] or not seeds.is_contiguous():
+        raise RuntimeError("diffuscene_amd: seeds must be a contiguous (%s,) int64 tensor (ops.scene_seeds), got %s"
+                           % (shape[0] if shape else "B", tuple(seeds.shape)))
+    if draw.numel() != 1:
+        raise RuntimeError("diffuscene_amd: draw must hold ONE int64 (the device draw counter), got %s" % (tuple(draw.shape),))
+    per_scene = 1
+    for s in shape[1:]:
+        per_scene *= s
+    return shape, per_scene, int(stream)
+
+
+def scene_randn(seeds, draw, stream, shape, out=None):
+    """Per-scene normals: out[b] = scene_normal(seeds[b], stream, draw[0], e) over the scene's own ``shape[1:]`` block (see the C
+    header, diffuscene_amd/scene_noise.py).  ``seeds``: (B,) int64 device tensor (ops.scene_seeds), ``draw``: the (1,) int64 DEVICE draw
+    counter, read by the launch -- capturable --, ``stream``: 0 the main draws, 1 the draws of the given part."""
+    shape, per_scene, stream = _scene_noise_args(seeds, draw, stream, shape)
+    if out is None:
+        out = torch.empty(shape, device=seeds.device, dtype=torch.float32)
+    _c(out, "out")
+    if tuple(out.shape) != shape:
+        raise RuntimeError("diffuscene_amd: scene_randn: out must be %s, got %s" % (shape, tuple(out.shape)))
+    if out.numel() == 0:
+        return out                             # nothing to draw (an empty tensor has no address to pass)
+    _lib.check(_lib.fn("dsc_scene_randn_f32")(out.data_ptr(), seeds.data_ptr(), draw.data_ptr(), stream, shape[0], per_scene,
+                                              stream_ptr()), "dsc_scene_randn_f32")
+    return out
+
+
+def scene_philox(seeds, draw, stream, shape):
+    """The raw Philox word of every element of scene_randn's draw, as int32 bit patterns (a probe for tests)."""
+    shape, per_scene, stream = _scene_noise_args(seeds, draw, stream, shape)
+    out = torch.empty(shape, device=seeds.device, dtype=torch.int32)
+    if out.numel() == 0:
+        return out
+    _lib.check(_lib.fn("dsc_scene_philox_u32")(out.data_ptr(), seeds.data_ptr(), draw.data_ptr(), stream, shape[0], per_scene,
+                                               stream_ptr()), "dsc_scene_philox_u32")
+    return out
+
+
 def _cfg_args(x_t, model_out, scale):
     """(b, inner) of a guided launch: model_out is (2 b, ...) with the conditional half first, scale a contiguous (b,) f32 device tensor."""
     _c(model_out, "model_out"); _c(scale, "scale")

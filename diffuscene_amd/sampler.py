@@ -6,7 +6,8 @@ is device-resident and replayed once per step; the timestep moves on inside the 
 in diffusion_ddpm.py: the same kernels, the same draws in the same order and shapes, the same generator state afterwards.
 
 Structure:
-  _Draws          one noise stream of a loop: torch.randn, or the rows of a replay buffer behind a device counter.
+  _Draws          one noise stream of a loop: torch.randn, the rows of a replay buffer behind a device counter, or -- seeded -- the
+                  per-scene noise kernel (scene_noise.py) on the graph's seed buffer behind a device draw counter.
   _LoopGraph      the core: launch plans, the state (x, t), the main noise stream, the model call, warm-up + capture that costs the
                   caller no random numbers (``graph``: a step that is followed by another, ``final``: the last one where it differs),
                   the stale-pointer check and the replays.
@@ -30,6 +31,9 @@ import torch
 from . import ops
 from .networks.denoise_net import Unet1D
 from .networks.diffusion_ddpm import restore_given_rows
+from .scene_noise import GIVEN, MAIN, SceneNoise
+
+RANDN, REPLAY, SEEDED = "randn", "replay", "seeded"            # the noise modes of a captured loop
 
 _MEAN = {"eps": ops.MEAN_EPS, "x0": ops.MEAN_X0, "v": ops.MEAN_V}
 
@@ -102,15 +106,23 @@ def _prepare_plans(eng, rows, N, condition, condition_cross, time_table, nch=1):
 
 
 class _Draws:
-    """One noise stream of a captured loop.  A call is one draw: torch.randn of the stream's shape, or -- when replaying -- row
-    ``counter`` of ``buf`` and a counter increment, both device-side, so the captured step walks the buffer as it is replayed."""
+    """One noise stream of a captured loop.  A call is one draw: torch.randn of the stream's shape; or -- when replaying -- row
+    ``counter`` of ``buf``; or -- seeded -- draw number ``counter`` of stream ``stream`` under the (B,) seed buffer ``seeds`` of the
+    graph (dsc_scene_randn_f32 reads the counter through its pointer).  The two counted modes end with a counter increment, device-side,
+    so the captured step walks the buffer / the draw numbers as it is replayed."""
 
-    def __init__(self, shape, device, rows=None):
+    def __init__(self, shape, device, rows=None, seeds=None, stream=MAIN):
         self.shape, self.device = tuple(shape), device
         self.buf = None if rows is None else torch.zeros((rows,) + self.shape, device=device)
+        self.seeds, self.stream = seeds, stream
         self.counter = torch.zeros((1,), device=device, dtype=torch.int64)
+        self.zero = torch.zeros((1,), device=device, dtype=torch.int64) if seeds is not None else None
 
     def __call__(self):
+        if self.seeds is not None:
+            n = ops.scene_randn(self.seeds, self.counter, self.stream, self.shape)
+            ops.add_scalar_i64(self.counter, 1)
+            return n
         if self.buf is None:
             return torch.randn(self.shape, dtype=torch.float, device=self.device)
         n = self.buf.index_select(0, self.counter)[0]
@@ -118,17 +130,25 @@ class _Draws:
         return n
 
     def head(self):
-        """Draw 0, taken outside the graph (the standalone first overwrite); a replaying loop then starts its counter at 1."""
+        """Draw 0, taken outside the graph (x_T of a seeded loop, the standalone first overwrite); a counted loop then starts its
+        counter at 1."""
+        if self.seeds is not None:
+            return ops.scene_randn(self.seeds, self.zero, self.stream, self.shape)
         return self() if self.buf is None else self.buf[0]
 
 
 class _LoopGraph:
     """The core of every captured loop; a subclass adds its buffers, ``_step(final)`` and ``run``.  ``mult``: scenes of the plan per
-    scene of the loop (2 for the guided loops), ``draws``: rows of the main replay buffer, ``nch``: sub-batch chains."""
+    scene of the loop (2 for the guided loops), ``draws``: rows of the main replay buffer, ``nch``: sub-batch chains.  ``replay``: the
+    noise mode -- False / RANDN, True / REPLAY, or SEEDED: the graph owns a (B,) seed buffer, refreshed in place by ``seeded_x_T``."""
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, replay, draws, mult=1, nch=1):
         B, N, C = shape
-        self.shape, self.device, self.replay = shape, device, replay
+        self.shape, self.device = shape, device
+        self.mode = {False: RANDN, True: REPLAY}.get(replay, replay)
+        assert self.mode in (RANDN, REPLAY, SEEDED), replay
+        self.replay = self.mode == REPLAY
+        self.seeds = torch.zeros((B,), device=device, dtype=torch.int64) if self.mode == SEEDED else None
         eng = model.engine(device)
         self.plans = _prepare_plans(eng, mult * B, N, condition, condition_cross, diff.num_timesteps <= eng.time_table.shape[0], nch)
         self.plan = self.plans[0]
@@ -143,8 +163,13 @@ class _LoopGraph:
         self.noise = self._stream(shape, draws)
         self.graph = self.final = None
 
-    def _stream(self, shape, rows):
-        return _Draws(shape, self.device, rows if self.replay else None)
+    def _stream(self, shape, rows, stream=MAIN):
+        return _Draws(shape, self.device, rows if self.replay else None, self.seeds, stream)
+
+    def seeded_x_T(self, seeds):
+        """The seeds of this run into the graph's own buffer, in place (the captured launches hold its pointer) -> x_T, main draw 0."""
+        self.seeds.copy_(seeds)
+        return self.noise.head()
 
     def _model_call(self):
         plan = self.plan
@@ -216,11 +241,13 @@ class _LoopGraph:
 
     def _upload(self, *loads):
         """(stream, buffer, first row) each: the replay buffers go into the graph's own, in place, then the counters are set --
-        main draw 0 was x_T, draw 0 of a shifted stream feeds the standalone overwrite (_Draws.head)."""
-        if not self.replay:
+        main draw 0 was x_T, draw 0 of a shifted stream feeds the standalone overwrite (_Draws.head).  A seeded loop has no buffers:
+        its counters start on the same numbers."""
+        if self.mode == RANDN:
             return
-        for d, buffer, _ in loads:
-            self._copy_rows(d.buf, buffer)
+        if self.replay:
+            for d, buffer, _ in loads:
+                self._copy_rows(d.buf, buffer)
         for d, _, first in loads:
             d.counter.fill_(first)
 
@@ -302,7 +329,7 @@ class _Ragged:
         self.pmax, self.fused = pmax, fused
         self.partial = torch.zeros((B, pmax, C), device=self.device, dtype=torch.float32)
         self.counts = torch.zeros((B,), device=self.device, dtype=torch.int64)
-        self.pnoise = self._stream((B, pmax, C), rows)
+        self.pnoise = self._stream((B, pmax, C), rows, GIVEN)
 
     def _overwrite(self, pn):
         ops.complete_overwrite_ragged(self.x, self.partial, pn, self.counts, self.t, *self.q)
@@ -325,7 +352,7 @@ class _Masked:
     def _init_given(self, rows):
         self.known = torch.zeros(self.shape, device=self.device, dtype=torch.float32)
         self.mask = torch.zeros(self.shape, device=self.device, dtype=torch.uint8)
-        self.knoise = self._stream(self.shape, rows)
+        self.knoise = self._stream(self.shape, rows, GIVEN)
 
     def _begin_given(self, known, mask, noise_buffer, known_noise):
         self.known.copy_(known)                 # in place: the graphs hold these pointers
@@ -346,7 +373,7 @@ class _StepGraph(_PosteriorLoop):
         self.side = [torch.cuda.Stream(device=device) for _ in range(nch - 1)]
         self.model_out = torch.empty(shape, device=device, dtype=torch.float32) if nch > 1 else None
         self.partial = torch.zeros(partial_shape, device=device) if partial_shape is not None else None
-        self.pnoise = self._stream(partial_shape, self.T) if partial_shape is not None else None
+        self.pnoise = self._stream(partial_shape, self.T, GIVEN) if partial_shape is not None else None
         self._capture([False])
 
     def _model_call(self):
@@ -601,8 +628,9 @@ def _cached_loop(name, diff, denoise_fn, shape, device, condition, condition_cro
                  ddim=None):
     """The front end of every graph_*_loop.  ``tag``: what of the loop's arguments shapes the graph (the loop, clip_denoised, S, Pmax,
     fused -- never eta, counts, mask or scales, which live in buffers); the key adds the model, the shape and the conditioning's
-    shapes.  ``check(noise_fn)`` validates a NoiseReplay, ``make(model, device, replay)`` builds the graph when there is none for the
-    key or its plan is stale, ``run(g, x_T, main buffer, partial buffer, dtab)`` runs it; ``ddim`` = (S, eta) of a strided loop, whose
+    shapes and the noise mode (randn / replay / seeded -- never the seeds, which live in a buffer).  ``check(noise_fn)`` validates a
+    NoiseReplay, ``make(model, device, replay)`` builds the graph (``replay``: the noise mode) when there is none for the key or its plan
+    is stale, ``run(g, x_T, main buffer, partial buffer, dtab)`` runs it; ``ddim`` = (S, eta) of a strided loop, whose
     device tables ``dtab`` are looked up here."""
     model = getattr(getattr(denoise_fn, "__self__", None), "model", None)
     if not isinstance(model, Unet1D):
@@ -611,22 +639,27 @@ def _cached_loop(name, diff, denoise_fn, shape, device, condition, condition_cro
     shape = tuple(shape)
     with torch.no_grad():
         replay = isinstance(noise_fn, NoiseReplay)
+        mode = SEEDED if isinstance(noise_fn, SceneNoise) else REPLAY if replay else RANDN
+        if mode == SEEDED and noise_fn.seeds.shape[0] != shape[0]:
+            raise ValueError("SceneNoise holds %d seeds, the loop samples %d scenes" % (noise_fn.seeds.shape[0], shape[0]))
         if replay and check is not None:
             check(noise_fn)
         dtab = None if ddim is None else diff.ddim_tables(ddim[0], ddim[1], device)
-        key = (tag, id(model), shape, str(device), diff.model_mean_type, replay,
+        key = (tag, id(model), shape, str(device), diff.model_mean_type, mode,
                None if condition is None else (tuple(condition.shape), condition.stride(0) == 0),
                None if condition_cross is None else tuple(condition_cross.shape))
         g = diff._graphs.get(key)
         eng = model.engine(device)
         eng.params_moved()              # parameters re-homed since the capture (first training step, .to()): the engine drops its plans
         if g is None or g.plan is not eng.plans.get(_plan_key(g)):
-            g = make(model, device, replay)
+            g = make(model, device, replay if mode != SEEDED else SEEDED)
             diff._graphs = {key: g}           # one live graph per diffusion object
         else:                                 # refresh weights + conditioning buffers
             _prepare_plans(eng, mult * shape[0], shape[1], condition, condition_cross, g.plan.time_table, len(g.plans))
         if replay:
             out = run(g, noise_fn.buffer[0], noise_fn.buffer, noise_fn.partial_buffer, dtab)
+        elif mode == SEEDED:                  # x_T is main draw 0; the device generator is not touched
+            out = run(g, g.seeded_x_T(noise_fn.seeds.to(device)), None, None, dtab)
         else:
             out = run(g, torch.randn(shape, dtype=torch.float, device=device), None, None, dtab)
         from ._lib import check_indices

@@ -445,6 +445,27 @@ int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, const float*
  * on the text features and backward on their incoming gradient.  y may alias x. */
 int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y, int32_t b, int64_t inner, dsc_stream_t stream);
 
+/* Per-scene noise: out (b, per_scene) contiguous, out[i, e] = scene_normal(seeds[i], stream, *draw, e), a pure function of its four
+ * arguments (diffuscene_amd/scene_noise.py evaluates the same definition on the host) -- nothing of b, of the scene's position or of
+ * earlier launches enters:
+ *   (r0, r1, r2, r3) = Philox4x32-10 on the counter (e >> 2, stream, draw & 0xffffffff, draw >> 32) under the key
+ *                      (seed & 0xffffffff, seed >> 32), the seed read as 64 bits; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants
+ *                      0x9E3779B9 / 0xBB67AE85, ten rounds, the key bumped after every round;
+ *   u_i = (float)(r_i >> 8) * 2^-24 + 2^-25   in float32 (rounded to nearest even above 1/2: u in (0, 1], and u == 1 gives rho == 0);
+ *   lanes e & 3 == 0, 1: rho = sqrtf(-2 * logf(u0)), theta = (float)(2 pi) * u1, z0 = rho * cosf(theta), z1 = rho * sinf(theta);
+ *   lanes 2, 3 the same on (u2, u3).  Full-precision logf / sinf / cosf, no fast-math.
+ * seeds: (b,) int64 on the device.  draw: ONE int64 on the device, read by the launch and never written, so a captured launch draws
+ * what the counter holds at replay time (dsc_add_scalar_i64 advances it inside the graph).  stream: a 32-bit id (0 the main draws of a
+ * loop, 1 the draws for the given part of a scene).  per_scene <= 2^32.  Null pointers, a negative count or a stream outside 32 bits:
+ * DSC_EINVAL; b == 0 or per_scene == 0: nothing is launched, 0; b * ceil(per_scene / 4) beyond 2^31 - 1 blocks of 256: DSC_ERANGE.
+ * One thread per Philox block; the last quad of a scene stores only its per_scene & 3 live lanes; dwordx4 stores when
+ * per_scene % 4 == 0 and out is 16-byte aligned, dword stores otherwise (no alignment is required of out). */
+int dsc_scene_randn_f32(float* out, const int64_t* seeds, const int64_t* draw, int64_t stream, int64_t b, int64_t per_scene,
+                        dsc_stream_t hip_stream);
+/* The raw word r_(e & 3) of every element instead of the normal: a probe for tests, so that the integer stream is pinned exactly. */
+int dsc_scene_philox_u32(uint32_t* out, const int64_t* seeds, const int64_t* draw, int64_t stream, int64_t b, int64_t per_scene,
+                         dsc_stream_t hip_stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Training: hand-written backward of the denoiser (the reference relies on torch autograd through
  * denoise_net.py; train_on_batch, diffusion_scene_layout_ddpm.py:456-473).  Input gradients
