@@ -149,19 +149,20 @@ __global__ __launch_bounds__(256) void gather_max_bwd_kernel(const float* __rest
 
 // ---- column statistics: partial[split][0..1][C] = sum (v - pivot), sum (v - pivot)^2 over the rows of the split, for
 // v = a (MODE 0) | sums of g and g * b with g = a masked by (mask > 0) (MODE 1: BatchNorm backward: a = dy, b = xhat,
-// mask = y of a ReLU layer or nullptr)
+// mask = y of a ReLU layer or nullptr).  With `only`, columns whose only[c] is not negative are left out (not read, not written).
 template <int MODE>
 __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ a, long lda, const float* __restrict__ b,
                                                        long ldb, const float* __restrict__ mask, long ldm,
-                                                       const float* __restrict__ pivot, long rows, int ch, int chunk,
-                                                       float* __restrict__ partial) {
+                                                       const float* __restrict__ pivot, const float* __restrict__ only, long rows,
+                                                       int ch, int chunk, float* __restrict__ partial) {
     __shared__ float red[2][4][64];
     const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
     const int c = blockIdx.x * 64 + cl;
     const long r0 = (long)blockIdx.y * chunk;
     const long r1 = (r0 + chunk < rows) ? r0 + chunk : rows;
+    const bool live = c < ch && (!only || only[c] < 0.f);
     float s0 = 0.f, s1 = 0.f;
-    if (c < ch) {
+    if (live) {
         const float pv = (MODE == 0 && pivot) ? pivot[c] : 0.f;
         for (long r = r0 + rl; r < r1; r += 4) {
             if (MODE == 0) {
@@ -176,24 +177,35 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
     }
     red[0][rl][cl] = s0; red[1][rl][cl] = s1;
     __syncthreads();
-    if (rl == 0 && c < ch) {
+    if (rl == 0 && live) {
         partial[((long)blockIdx.y * 2 + 0) * ch + c] = (red[0][0][cl] + red[0][1][cl]) + (red[0][2][cl] + red[0][3][cl]);
         partial[((long)blockIdx.y * 2 + 1) * ch + c] = (red[1][0][cl] + red[1][1][cl]) + (red[1][2][cl] + red[1][3][cl]);
     }
 }
 
-// BatchNorm finalize: mean / rstd from the partial sums (fp64 combine), running statistics (momentum, unbiased variance)
+// A column is summed a second time, about its mean, when the first pivot lies more than BN_RECENTRE_SIGMA standard deviations
+// from the mean: var = s1/rows - m^2 (m = mean - pivot) carries the rounding of s1 magnified by 1 + m^2/var.
+constexpr double BN_RECENTRE_SIGMA = 4.0;
+
+// BatchNorm finalize: mean / rstd from the partial sums about the pivot (fp64 combine; mean = pivot + s0 / rows,
+// var = s1 / rows - (s0 / rows)^2), running statistics (momentum, unbiased variance).
+// FIRST pass (pivot = a row of x): a column whose pivot is too far out gets mean[c] = its mean, rstd[c] = -1 and nothing else: the
+// mark of the second pass.  SECOND pass (pivot == nullptr): only the marked columns, their pivot is mean[c].
+template <bool FIRST>
 __global__ void bn_finalize_kernel(const float* __restrict__ partial, int splits, const float* __restrict__ pivot, long rows,
-                                   int ch, float eps, float momentum, float* __restrict__ mean, float* __restrict__ rstd,
-                                   float* __restrict__ run_mean, float* __restrict__ run_var) {
+                                   int ch, float eps, float momentum, float* mean, float* rstd, float* __restrict__ run_mean,
+                                   float* __restrict__ run_var) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= ch) return;
+    if (!FIRST && !(rstd[c] < 0.f)) return;
+    const double pv = FIRST ? (double)pivot[c] : (double)mean[c];
     double s0 = 0.0, s1 = 0.0;
     for (int s = 0; s < splits; ++s) { s0 += partial[((long)s * 2) * ch + c]; s1 += partial[((long)s * 2 + 1) * ch + c]; }
     const double m = s0 / (double)rows;
     double var = s1 / (double)rows - m * m;
     if (var < 0.0) var = 0.0;
-    mean[c] = (float)(m + (double)pivot[c]);
+    mean[c] = (float)(m + pv);
+    if (FIRST && m * m > BN_RECENTRE_SIGMA * BN_RECENTRE_SIGMA * var) { rstd[c] = -1.0f; return; }
     rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
     if (run_mean) {
         const double unb = rows > 1 ? var * (double)rows / (double)(rows - 1) : var;
@@ -447,11 +459,19 @@ extern "C" int dsc_batchnorm_fwd_f32(const float* x, int64_t ldx, const float* g
     if (workspace_floats < (int64_t)splits * 4 * ch) return DSC_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DSC_CLEAR_STALE_ERROR();
-    // pivot = first row (shifted sums: no cancellation in the variance)
+    // First pass: sums of v - x[0] and (v - x[0])^2, shifted by the first row so that a common offset of the column costs no digits.
+    // That is exact enough while the first row is an ordinary sample of its column.  Where it is not (bn_finalize_kernel<true>
+    // marks the column), a second pass sums the column about its own mean: the squares are then of the size of the variance whatever
+    // the first row holds, and s0 is only the fp32 rounding residue of the mean.  Columns with an ordinary first row are not
+    // read again and get the statistics of the first pass.  Assumes finite input.
     hipLaunchKernelGGL(colstats_kernel<0>, dim3((ch + 63) / 64, splits), dim3(256), 0, s, x, (long)ldx, nullptr, 0L, nullptr, 0L,
-                       x, (long)rows, ch, chunk, workspace);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((ch + 255) / 256), dim3(256), 0, s, workspace, splits, x, (long)rows, ch, eps,
+                       x, nullptr, (long)rows, ch, chunk, workspace);
+    hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((ch + 255) / 256), dim3(256), 0, s, workspace, splits, x, (long)rows, ch, eps,
                        momentum, mean, rstd, running_mean, running_var);
+    hipLaunchKernelGGL(colstats_kernel<0>, dim3((ch + 63) / 64, splits), dim3(256), 0, s, x, (long)ldx, nullptr, 0L, nullptr, 0L,
+                       mean, rstd, (long)rows, ch, chunk, workspace);
+    hipLaunchKernelGGL(bn_finalize_kernel<false>, dim3((ch + 255) / 256), dim3(256), 0, s, workspace, splits, nullptr, (long)rows, ch,
+                       eps, momentum, mean, rstd, running_mean, running_var);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(rows * ch)), dim3(256), 0, s, x, (long)ldx, mean, rstd, gamma, beta,
                        (long)rows, ch, relu, xhat, y);
     DSC_LAUNCH_CHECK();
@@ -480,7 +500,7 @@ extern "C" int dsc_batchnorm_bwd_f32(const float* dy, const float* xhat, const f
     float* sums = workspace + (int64_t)splits * 2 * ch;          // [2][C] behind the partials
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(colstats_kernel<1>, dim3((ch + 63) / 64, splits), dim3(256), 0, s, dy, (long)ch, xhat, (long)ch,
-                       relu ? y : nullptr, (long)ch, nullptr, (long)rows, ch, chunk, workspace);
+                       relu ? y : nullptr, (long)ch, nullptr, nullptr, (long)rows, ch, chunk, workspace);
     hipLaunchKernelGGL(colstats_reduce_kernel, dim3((2 * ch + 255) / 256), dim3(256), 0, s, workspace, splits, ch, sums);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(rows * ch)), dim3(256), 0, s, dy, xhat, y, gamma, rstd, sums, (long)rows,
                        ch, relu, dx);

@@ -10,7 +10,8 @@ token-major ``[cloud * N + point][channel]`` device tensors and every layer is a
 * ``knn`` (:59-76): xyz -> distances in-kernel; features -> per-cloud Gram matrices by ONE batched GEMM, then a top-16
   selection kernel (one wave per point).  Neighbour order is nearest-first with ties to the lowest index; everything
   downstream (max pooling, covariance) is order-invariant.
-* Conv1d(k=1) + BatchNorm1d(+ReLU): GEMM, then column statistics over all points of the batch (shifted sums, fp64 combine),
+* Conv1d(k=1) + BatchNorm1d(+ReLU): GEMM, then column statistics over all points of the batch (sums shifted by the first row, fp64 combine;
+  a column whose first row lies far outside it is summed again about its mean),
   apply; running statistics are updated like ``nn.BatchNorm1d`` (momentum 0.1, unbiased variance) so ``eval()`` works.
 * GraphLayer max pooling over 16 neighbours, global max pooling over points: arg-max kept for the backward.
 * FoldingLayer first convolution on ``cat([grid | codeword])`` (:247-251): the codeword columns are the same for all 2025 grid
