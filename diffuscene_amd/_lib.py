@@ -230,6 +230,10 @@ SIGNATURES = {
     "dsc_p_sample_cfg_f32": (C.c_int, [c_f32p] * 4 + [c_i64p] + [c_f32p] * 8 + [C.c_int32] * 3 + [C.c_int64, C.c_int32, C.c_void_p]),
     "dsc_ddim_cfg_step_f32": (C.c_int, [c_f32p] * 4 + [c_i64p] * 3 + [c_f32p] * 10 + [C.c_int32] * 2 +
                               [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "dsc_p_sample_masked_cfg_f32": (C.c_int, [c_f32p] * 6 + [C.c_void_p, c_i64p] + [c_f32p] * 9 + [C.c_int32] * 3 +
+                                    [C.c_int64, C.c_int32, C.c_void_p]),
+    "dsc_ddim_masked_cfg_step_f32": (C.c_int, [c_f32p] * 6 + [C.c_void_p] + [c_i64p] * 3 + [c_f32p] * 11 + [C.c_int32] * 2 +
+                                     [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
     "dsc_scene_gate_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int32, C.c_int64, C.c_void_p]),
 }
 

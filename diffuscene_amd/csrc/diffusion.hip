@@ -428,6 +428,76 @@ __global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const float* xt, con
     }
 }
 
+// Guided in-painting (p_sample_loop_masked_guided): p_sample_masked_kernel with m computed in registers from the two halves of mo
+// (2 b, inner); known / noise_k / mask stay (b, inner).  x_dup as in p_sample_cfg_kernel: every written element, given or free, goes
+// there too.  A given element reads mask, known and noise_k only (no noise_k at t == 0); a free one mask, xt, both halves of mo and
+// noise only.  Bit-identical to cfg_combine_kernel followed by p_sample_masked_kernel.
+__global__ __launch_bounds__(256) void p_sample_masked_cfg_kernel(const float* xt, const float* __restrict__ mo,
+                                                                 const float* __restrict__ scale, const float* __restrict__ noise,
+                                                                 const float* __restrict__ known, const float* __restrict__ noise_k,
+                                                                 const uint8_t* __restrict__ mask, const int64_t* __restrict__ t,
+                                                                 const float* __restrict__ ca, const float* __restrict__ cb,
+                                                                 const float* __restrict__ c1, const float* __restrict__ c2,
+                                                                 const float* __restrict__ sigma, const float* __restrict__ sa,
+                                                                 const float* __restrict__ sb, float* out,   // out may alias xt
+                                                                 float* __restrict__ x_dup, int mean_type, int clip, int64_t inner,
+                                                                 int T) {
+    const int b = blockIdx.y;
+    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
+    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
+    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
+    const float w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        float y;
+        if (mask[base + i]) {
+            const float kv = known[base + i];
+            y = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
+        } else {
+            const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
+            y = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
+        }
+        out[base + i] = y;
+        if (x_dup) x_dup[base + i] = y;
+    }
+}
+
+// The strided twin (ddim_masked_guided_loop): ddim_masked_step_kernel with the same change and the same x_dup; index checks as there.
+// On the last pair neither noise nor noise_k is read.  Bit-identical to cfg_combine_kernel followed by ddim_masked_step_kernel.
+__global__ __launch_bounds__(256) void ddim_masked_cfg_step_kernel(const float* xt, const float* __restrict__ mo,
+                                                                  const float* __restrict__ scale, const float* __restrict__ noise,
+                                                                  const float* __restrict__ known, const float* __restrict__ noise_k,
+                                                                  const uint8_t* __restrict__ mask, const int64_t* __restrict__ step,
+                                                                  const int64_t* __restrict__ times,
+                                                                  const int64_t* __restrict__ times_next,
+                                                                  const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
+                                                                  const float* __restrict__ sigma, const float* __restrict__ ca,
+                                                                  const float* __restrict__ cb, const float* __restrict__ ra,
+                                                                  const float* __restrict__ rm, const float* __restrict__ sa,
+                                                                  const float* __restrict__ sb, float* out,   // out may alias xt
+                                                                  float* __restrict__ x_dup, int mean_type, int64_t inner, int S,
+                                                                  int T) {
+    const int b = blockIdx.y;
+    const bool first_all = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;           // one count per launch
+    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
+    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
+    const float w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        float y;
+        if (mask[base + i]) {
+            const float kv = known[base + i];
+            y = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
+        } else {
+            const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
+            y = predict_x0(x, m, d.A, d.Bc, mean_type, true);
+            if (!d.last) y = add_noise(ddim_mean(y, x, m, d, mean_type), noise[base + i], d.sg);
+        }
+        out[base + i] = y;
+        if (x_dup) x_dup[base + i] = y;
+    }
+}
+
 // Per-scene gate of the text-condition dropout (text_drop_prob): y[b, :] = keep[b] ? x[b, :] : 0 -- a select, a dropped scene's x is
 // not read.  Forward on the text features, backward on their incoming gradient.  y may alias x.
 __global__ __launch_bounds__(256) void scene_gate_kernel(const float* x, const uint8_t* __restrict__ keep, float* y, int64_t inner) {
@@ -813,6 +883,45 @@ extern "C" int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, c
     hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
                        x_t, model_out, scale, noise, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca, cb,
                        sqrt_recip_ac, sqrt_recipm1_ac, out, x_dup, x0_out, mean_type, inner, num_steps, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_p_sample_masked_cfg_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
+                                           const float* known, const float* noise_k, const uint8_t* mask, const int64_t* t,
+                                           const float* ca, const float* cb, const float* coef1, const float* coef2, const float* sigma,
+                                           const float* sqrt_ac, const float* sqrt_1mac, float* out, float* x_dup, int32_t mean_type,
+                                           int32_t clip, int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !scale || !noise || !known || !noise_k || !mask || !t || !coef1 || !coef2 || !sigma || !sqrt_ac ||
+        !sqrt_1mac || !out || b < 1 || inner < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(p_sample_masked_cfg_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, scale, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
+                       x_dup, mean_type, clip, inner, num_timesteps);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
+                                            const float* known, const float* noise_k, const uint8_t* mask, const int64_t* step,
+                                            const int64_t* times, const int64_t* times_next, const float* sqrt_alpha_next,
+                                            const float* c_noise, const float* sigma, const float* ca, const float* cb,
+                                            const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* sqrt_ac,
+                                            const float* sqrt_1mac, float* out, float* x_dup, int32_t mean_type, int32_t b,
+                                            int64_t inner, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x_t || !model_out || !scale || !noise || !known || !noise_k || !mask || !step || !times || !times_next || !sqrt_alpha_next ||
+        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || inner < 1 ||
+        num_steps < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_masked_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x_t, model_out, scale, noise, known, noise_k, mask, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
+                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, x_dup, mean_type, inner, num_steps, num_timesteps);
     DSC_LAUNCH_CHECK();
     return 0;
 }

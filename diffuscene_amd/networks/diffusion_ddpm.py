@@ -21,10 +21,10 @@ each a generator of states (x_T, then the state after every step), and two indep
   the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine)
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
 part -- and then numbers its own draws: main stream x_T = 0, 1, 2, ..., given stream 0, 1, 2, ... (scene_noise.py).
-The twelve public loops validate, hand over to the captured loop under _use_graph, build the two objects and run a core: nothing given --
+The fourteen public loops validate, hand over to the captured loop under _use_graph, build the two objects and run a core: nothing given --
 p_sample_loop, _trajectory, _arrange / ddim_sample_loop, ddim_arrange_loop (both arrange loops on the sub-shape); guided --
 p_sample_loop_guided / ddim_guided_loop; rows -- p_sample_loop_complete, _complete_ragged / ddim_complete_ragged_loop; mask --
-p_sample_loop_masked / ddim_masked_loop.
+p_sample_loop_masked / ddim_masked_loop; mask and guided -- p_sample_loop_masked_guided / ddim_masked_guided_loop.
 """
 import json
 import os
@@ -736,6 +736,47 @@ class GaussianDiffusion:
         return _last(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta, given), shape)
 
     @torch.no_grad()
+    def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
+                                    clip_denoised=True, keep_running=False, known=None, mask=None, graph=None):
+        """Text-guided element-wise in-painting in T steps: scene b is p_sample_loop_masked with m = u + w[b] * (c - u) in place of the
+        model output (c, u and ``guidance_scale`` as in p_sample_loop_guided; ``known`` / ``mask`` as in p_sample_loop_masked).  Both
+        halves of the 2 B model call see the same overwritten x_t.  Draws: exactly those of p_sample_loop_masked at batch B, in its
+        order.  The eager loop is built from the unfused pieces -- masked overwrite, the denoiser at 2 B, cfg_combine, p_sample, select;
+        the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
+        dsc_p_sample_masked_cfg_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        known, mask = self._masked_inputs(shape, device, known, mask, "p_sample_loop_masked_guided")
+        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale,
+                                                   "p_sample_loop_masked_guided")
+        total_steps = self._total_steps(keep_running)
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_masked_guided_loop
+            return graph_masked_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, clip_denoised, total_steps,
+                                            noise_fn, known, mask)
+        given = _GivenMask(self, device, noise_fn, shape, known, mask)
+        return _last(self._t_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, clip_denoised, total_steps,
+                                    given), shape)
+
+    @torch.no_grad()
+    def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
+                                sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None):
+        """Text-guided element-wise in-painting in S strided (DDIM) steps: scene b is ddim_masked_loop with the guided output m of
+        p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
+        ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
+        step whose update is the fused dsc_ddim_masked_cfg_step_f32, bit-identical."""
+        assert isinstance(shape, (tuple, list))
+        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        known, mask = self._masked_inputs(shape, device, known, mask, "ddim_masked_guided_loop")
+        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "ddim_masked_guided_loop")
+        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
+        if _use_graph(graph, noise_fn, denoise_fn):
+            from ..sampler import graph_ddim_masked_guided_loop
+            return graph_ddim_masked_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, S, eta, noise_fn, known,
+                                                 mask)
+        given = _GivenMask(self, device, noise_fn, shape, known, mask)
+        return _last(self._strided_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, S, eta, given), shape)
+
+    @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
                           ddim_sampling_eta=0., input_boxes=None, graph=None):
         """Strided (DDIM) re-arrangement: ddim_sample_loop on the sub-shape (B, N, translation_dim + angle_dim) under the arrange
@@ -1004,6 +1045,22 @@ class DiffusionPoint(nn.Module):
                                                condition_cross=condition_cross, noise_fn=noise_fn,
                                                sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
                                                known=known, mask=mask, graph=graph)
+
+    def inpaint_samples_guided(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
+                               clip_denoised=True, keep_running=False, known=None, mask=None, graph=None):
+        """inpaint_samples under classifier-free guidance (p_sample_loop_masked_guided)."""
+        return self.diffusion.p_sample_loop_masked_guided(self._denoise, shape=shape, device=device, condition=condition,
+                                                          condition_cross=condition_cross, guidance_scale=guidance_scale,
+                                                          noise_fn=noise_fn, clip_denoised=clip_denoised, keep_running=keep_running,
+                                                          known=known, mask=mask, graph=graph)
+
+    def inpaint_samples_guided_ddim(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
+                                    sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None):
+        """inpaint_samples_guided in S strided steps (ddim_masked_guided_loop)."""
+        return self.diffusion.ddim_masked_guided_loop(self._denoise, shape=shape, device=device, condition=condition,
+                                                      condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
+                                                      sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
+                                                      known=known, mask=mask, graph=graph)
 
     def arrange_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                              sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None):

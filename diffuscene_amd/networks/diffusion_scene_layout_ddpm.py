@@ -677,7 +677,7 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                              scene_seeds=None):
+                              scene_seeds=None, guidance_scale=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -685,15 +685,22 @@ class DiffusionSceneLayout_DDPM(Module):
         known.  ``known_mask``: (B, N, C) or (B, N) bool / uint8, e.g. from ``attribute_mask``.  Works on the ordinary unconditional,
         instance- or text-conditioned model (``text`` as in ``sample``); ``room_partial_condition`` / ``room_arrange_condition`` models
         are refused, their condition tensors already encode a prefix / a sub-shape.  Returns a list of B dicts; given elements are
-        filtered like any others (a row whose given 'empty' logit is >= 0 is dropped)."""
+        filtered like any others (a row whose given 'empty' logit is >= 0 is dropped).
+        ``guidance_scale`` (None: this method as it was, same code path, same draws): a float or B per-scene classifier-free guidance
+        scales of a text-conditioned model, as in ``sample`` -- the fixed elements pull the sample away from the prompt, the scale pulls
+        it back (``inpaint_samples_guided`` / ``inpaint_samples_guided_ddim``).  Needs ``text``; refused, before anything is drawn, on a
+        model without ``text_condition`` and on a text encoder that does not give (B, L, text_embed_dim) features."""
         from .. import ops
         if self.room_partial_condition or self.room_arrange_condition:
             raise ValueError("inpaint_scene_batched: a room_partial_condition / room_arrange_condition model conditions on a prefix / a "
                              "sub-shape of the scene (complete_scene_batched, arrange_scene_batched)")
+        if guidance_scale is not None:
+            self._check_guidance(text)
         device = room_mask.device
         if batch_size is None:
             batch_size = len(boxes) if isinstance(boxes, (list, tuple)) else int(boxes.shape[0])
         B, N, C = int(batch_size), int(num_points), int(point_dim)
+        scale = None if guidance_scale is None else ops.guidance_scales(guidance_scale, B, "cpu")   # checked on the host; the loop uploads it
         seeded = self._seeded(scene_seeds, batch_seeds, B, device)
         if isinstance(boxes, (list, tuple)):
             if len(boxes) != B:
@@ -719,10 +726,24 @@ class DiffusionSceneLayout_DDPM(Module):
             mask = (mask * valid[:, :, None].to(torch.uint8)).to(device).contiguous()
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+        if scale is not None:                                      # the last refusal of the keyword, still before any draw
+            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
+            if condition_cross is None or condition_cross.dim() != 3:
+                raise ValueError("guidance_scale: the text encoder must give (B, L, text_embed_dim) features, got %s (the null "
+                                 "condition is defined on the cross-attention features)"
+                                 % (None if condition_cross is None else tuple(condition_cross.shape),))
         torch.randn((B, N, C))                                     # CPU draw kept, as in sample (:232)
-        condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
+        if scale is None:
+            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
         print('scene in-painting sampling')
-        if sampling_timesteps is not None:
+        if scale is not None:
+            guided = dict(condition=condition, condition_cross=condition_cross, guidance_scale=scale, known=known, mask=mask, **seeded)
+            if sampling_timesteps is not None:
+                samples = self.diffusion.inpaint_samples_guided_ddim((B, N, C), device, sampling_timesteps=S, ddim_sampling_eta=eta,
+                                                                     **guided)
+            else:
+                samples = self.diffusion.inpaint_samples_guided((B, N, C), device, clip_denoised=clip_denoised, **guided)
+        elif sampling_timesteps is not None:
             samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
                                                           known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded)
         else:

@@ -790,6 +790,42 @@ def ddim_cfg_step(x_t, model_out, scale, noise, step, times, times_next, coef, c
     return out
 
 
+def p_sample_masked_cfg(x_t, model_out, scale, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac,
+                        mean_type, clip, out=None, x_dup=None):
+    """p_sample_masked on the guided model output, one launch: model_out (2 B, N, C) = [c; u], scale (B,) f32; known / noise_k / mask
+    are (B, N, C); ``x_dup`` receives a second copy of every written element.  Bit-identical to cfg_combine followed by
+    p_sample_masked.  See the C header."""
+    _c(noise, "noise")
+    b, inner = _masked_args(x_t, known, noise_k, mask)
+    _cfg_args(x_t, model_out, scale)
+    _scene_t(t, b)
+    out = _out_like("p_sample_masked_cfg", x_t, out, noise)
+    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out))
+    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
+    _lib.check(_lib.fn("dsc_p_sample_masked_cfg_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
+                                                      known.data_ptr(), noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(), *post,
+                                                      *extra, mean_type, 1 if clip else 0, b, inner, rows, stream_ptr()),
+               "dsc_p_sample_masked_cfg_f32")
+    return out
+
+
+def ddim_masked_cfg_step(x_t, model_out, scale, noise, known, noise_k, mask, step, times, times_next, coef, ca, cb, sqrt_recip_ac,
+                         sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, mean_type, out=None, x_dup=None):
+    """ddim_masked_step on the guided model output, one launch; operands as p_sample_masked_cfg, tables as ddim_masked_step (``noise``
+    and ``noise_k`` are not read on the final pair).  Bit-identical to cfg_combine followed by ddim_masked_step.  See the C header."""
+    _c(noise, "noise")
+    b, inner = _masked_args(x_t, known, noise_k, mask)
+    _cfg_args(x_t, model_out, scale)
+    strided, S = _strided_run(step, times, times_next, coef)
+    out = _out_like("ddim_masked_cfg_step", x_t, out, noise)
+    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out))
+    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
+    _lib.check(_lib.fn("dsc_ddim_masked_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
+                                                       known.data_ptr(), noise_k.data_ptr(), mask.data_ptr(), *strided, *tabs, *extra,
+                                                       mean_type, b, inner, S, rows, stream_ptr()), "dsc_ddim_masked_cfg_step_f32")
+    return out
+
+
 def scene_gate(x, keep, out=None):
     """y[b] = keep[b] ? x[b] : 0 for a (B, ...) f32 tensor and a (B,) bool / uint8 device tensor; a dropped scene is not read.  See the C
     header."""

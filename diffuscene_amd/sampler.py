@@ -17,13 +17,15 @@ Structure:
   _Ragged, _Masked   the given part of a scene (a row prefix with per-scene counts / a byte mask) in graph-owned buffers, its own
                   noise stream, shifted by one: draw 0 feeds a standalone overwrite in ``run``, the fused step re-noises for the NEXT
                   model call, the last step restores -- so a given element costs no posterior step and the draw order stays the eager one.
-What the eight classes add:
+What the ten classes add:
   _StepGraph (p_sample_loop, _complete)     optional sub-batch chains (_chains_for), optional dense overwrite before the model call
   _DDIMGraph (ddim_sample_loop, strided re-arrangement on the sub-shape)             dsc_ddim_step_f32
   _RaggedCompleteGraph / _DDIMCompleteGraph  _Ragged + dsc_p_sample_inpaint_f32 / dsc_ddim_inpaint_step_f32; fused=False: unfused kernels
   _MaskedGraph / _DDIMMaskedGraph            _Masked + dsc_p_sample_masked_f32 / dsc_ddim_masked_step_f32
   _GuidedStepGraph / _DDIMGuidedGraph        a plan at 2 B (text features | zeros), x kept in both halves of one (2 B, N, C) buffer,
                                              per-scene scales in a buffer, dsc_p_sample_cfg_f32 / dsc_ddim_cfg_step_f32; fused=False
+  _MaskedGuidedGraph / _DDIMMaskedGuidedGraph   _Masked + _Guided: known, mask and the known-draws at B under a plan at 2 B,
+                                             dsc_p_sample_masked_cfg_f32 / dsc_ddim_masked_cfg_step_f32; fused=False
 The graph_*_loop functions are the front ends behind diffusion_ddpm.py: one cached graph per diffusion object (_cached_loop).
 """
 import torch
@@ -358,7 +360,9 @@ class _Masked:
         self.known.copy_(known)                 # in place: the graphs hold these pointers
         self.mask.copy_(mask)
         self._upload((self.noise, noise_buffer, 1), (self.knoise, known_noise, 1))
-        ops.masked_overwrite(self.x, self.known, self.knoise.head(), self.mask, self.t, *self.q)
+        ops.masked_overwrite(self.x, self.known, self.knoise.head(), self.mask, self.t[:self.shape[0]], *self.q)
+        if self.x_null is not None:             # guided: both halves of the state stay current
+            self.x_null.copy_(self.x)
 
 
 class _StepGraph(_PosteriorLoop):
@@ -624,6 +628,72 @@ class _DDIMGuidedGraph(_Guided, _DDIMLoop):
         return self._replays(self.S)
 
 
+class _MaskedGuidedGraph(_Masked, _Guided, _PosteriorLoop):
+    """p_sample_loop_masked_guided: _MaskedGraph's step on a plan at 2 B with dsc_p_sample_masked_cfg_f32; known, mask and the
+    known-draws stay at B.  ``fused=False``: cfg_combine into ``m``, dsc_p_sample_masked_f32, a copy into the null half."""
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
+        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay, mult=2)
+        self._init_given(self.T)
+        self._init_guided(fused)
+        self._capture([False, True])
+
+    def _step(self, final):
+        mo = self._model_call()
+        noise = self.noise()
+        nk = self.known if final else self.knoise()             # not read at t == 0
+        if self.fused:
+            ops.p_sample_masked_cfg(self.x, mo, self.scale, noise, self.known, nk, self.mask, self.tB, *self.post, *self.q, *self.tail,
+                                    out=self.x, x_dup=self.x_null)
+        else:
+            ops.cfg_combine(mo, self.scale, out=self.m)
+            ops.p_sample_masked(self.x, self.m, noise, self.known, nk, self.mask, self.tB, *self.post, *self.q, *self.tail, out=self.x)
+            self.x_null.copy_(self.x)
+        if not final:
+            ops.add_scalar_i64(self.t, -1)
+
+    def run(self, x_T, total_steps, scale, known, mask, noise_buffer=None, known_noise=None):
+        self.check_current()
+        self._start(x_T, total_steps - 1)
+        self.scale.copy_(scale)                 # in place: the graph holds this pointer
+        self._begin_given(known, mask, noise_buffer, known_noise)
+        out = self._replays(total_steps)
+        self._park()
+        return out
+
+
+class _DDIMMaskedGuidedGraph(_Masked, _Guided, _DDIMLoop):
+    """ddim_masked_guided_loop: _DDIMMaskedGraph's step on a plan at 2 B with dsc_ddim_masked_cfg_step_f32; ``fused=False`` as in
+    _MaskedGuidedGraph, with dsc_ddim_masked_step_f32."""
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False, fused=True):
+        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay, mult=2)
+        self._init_given(S)
+        self._init_guided(fused)
+        self._capture(self.kinds)
+
+    def _step(self, final):
+        mo = self._model_call()
+        noise = self.x if final else self.noise()                # neither is read on the last pair
+        nk = self.known if final else self.knoise()
+        if self.fused:
+            ops.ddim_masked_cfg_step(self.x, mo, self.scale, noise, self.known, nk, self.mask, *self.tabs, *self.ddim, *self.q,
+                                     self.mean_type, out=self.x, x_dup=self.x_null)
+        else:
+            ops.cfg_combine(mo, self.scale, out=self.m)
+            ops.ddim_masked_step(self.x, self.m, noise, self.known, nk, self.mask, *self.tabs, *self.ddim, *self.q, self.mean_type,
+                                 out=self.x)
+            self.x_null.copy_(self.x)
+        self._advance(final)
+
+    def run(self, x_T, dtab, scale, known, mask, noise_buffer=None, known_noise=None):
+        t0 = self._load_tables(dtab)
+        self.scale.copy_(scale)
+        self._start(x_T, t0)
+        self._begin_given(known, mask, noise_buffer, known_noise)
+        return self._replays(self.S)
+
+
 def _cached_loop(name, diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, tag, make, run, mult=1, check=None,
                  ddim=None):
     """The front end of every graph_*_loop.  ``tag``: what of the loop's arguments shapes the graph (the loop, clip_denoised, S, Pmax,
@@ -788,6 +858,33 @@ def graph_ddim_guided_loop(diff, denoise_fn, shape, device, condition, condition
         lambda model, dev, replay: _DDIMGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay, fused),
         lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, buf), mult=2, check=_replay_check("the guided strided loop", S, shape),
         ddim=(S, eta))
+
+
+def graph_masked_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, clip_denoised, total_steps,
+                             noise_fn=torch.randn, known=None, mask=None, fused=True):
+    """p_sample_loop_masked_guided as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same
+    order, the same generator state afterwards).  ``condition`` / ``condition_cross`` arrive at 2 B, ``scale`` (B,) f32, ``known`` /
+    ``mask`` (B, N, C) are copied into the graph's own buffers: the cache key holds the shape, neither the mask nor the scales."""
+    return _cached_loop(
+        "graph_masked_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
+        ("masked_guided", bool(fused), bool(clip_denoised)),
+        lambda model, dev, replay: _MaskedGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay,
+                                                      fused),
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, scale, known, mask, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
+        mult=2, check=_replay_check("the guided masked loop", total_steps + 1, shape, total_steps, shape))
+
+
+def graph_ddim_masked_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, sampling_timesteps, eta,
+                                  noise_fn=torch.randn, known=None, mask=None, fused=True):
+    """ddim_masked_guided_loop as replayed hipGraphs; bit-identical to the eager loop.  The cache key holds the shape and S; it holds
+    neither eta, the mask nor the scales."""
+    S = int(sampling_timesteps)
+    return _cached_loop(
+        "graph_ddim_masked_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
+        ("ddim_masked_guided", S, bool(fused)),
+        lambda model, dev, replay: _DDIMMaskedGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay, fused),
+        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, known, mask, buf, pbuf), mult=2,
+        check=_replay_check("the guided strided masked loop", S, shape, S, shape), ddim=(S, eta))
 
 
 def _plan_key(g):

@@ -440,6 +440,28 @@ int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, const float*
                           int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
                           dsc_stream_t stream);
 
+/* Guided in-painting: dsc_p_sample_masked_f32 with m = u + scale[i] * (c - u) computed in registers from the two halves of model_out
+ * (2 b, inner); x_t / noise / known / noise_k / mask / out are (b, inner), scale is (b,).  x_dup (may be NULL): every written element,
+ * given or free, is written there too (the null half of a captured loop's (2 b, inner) state).  A given element reads mask, known and
+ * noise_k only (no noise_k at t == 0); a free one mask, x_t, both halves of model_out and noise only.  Bit-identical to
+ * dsc_cfg_combine_f32 followed by dsc_p_sample_masked_f32.  out may alias x_t; x_dup must not. */
+int dsc_p_sample_masked_cfg_f32(const float* x_t, const float* model_out, const float* scale, const float* noise, const float* known,
+                                const float* noise_k, const uint8_t* mask, const int64_t* t, const float* ca, const float* cb,
+                                const float* coef1, const float* coef2, const float* sigma, const float* sqrt_ac,
+                                const float* sqrt_1mac, float* out, float* x_dup /* may be NULL */, int32_t mean_type, int32_t clip,
+                                int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream);
+
+/* dsc_ddim_masked_step_f32 with the same change and the same x_dup (tables, step counter and clamping as there; on the last pair
+ * neither noise nor noise_k is read).  Bit-identical to dsc_cfg_combine_f32 followed by dsc_ddim_masked_step_f32.  out may alias x_t;
+ * x_dup must not. */
+int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise, const float* known,
+                                 const float* noise_k, const uint8_t* mask, const int64_t* step, const int64_t* times,
+                                 const int64_t* times_next, const float* sqrt_alpha_next, const float* c_noise, const float* sigma,
+                                 const float* ca, const float* cb, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac,
+                                 const float* sqrt_ac, const float* sqrt_1mac, float* out, float* x_dup /* may be NULL */,
+                                 int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
+                                 dsc_stream_t stream);
+
 /* Per-scene gate of the text-condition dropout (text_drop_prob): y[i, :] = keep[i] ? x[i, :] : 0 for b scenes of `inner` elements;
  * keep holds one byte per scene.  A select: the elements of a dropped scene are not read (NaN there does not propagate).  Used forward
  * on the text features and backward on their incoming gradient.  y may alias x. */
