@@ -112,54 +112,9 @@ __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void p_sample_kernel(const float* xt, const float* __restrict__ mo,
-                                                      const float* __restrict__ noise, const int64_t* __restrict__ t,
-                                                      const float* __restrict__ ca, const float* __restrict__ cb,
-                                                      const float* __restrict__ c1, const float* __restrict__ c2,
-                                                      const float* __restrict__ sigma, float* out,   // out may alias xt (in-place step)
-                                                      float* __restrict__ x0_out, int mean_type, int clip, int64_t inner, int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
-    const int64_t base = (int64_t)b * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = xt[base + i], m = mo[base + i];
-        const float x0 = predict_x0(x, m, p.A, p.Bc, mean_type, clip);
-        out[base + i] = add_noise(posterior_mean(x0, x, p), noise[base + i], p.sg);
-        if (x0_out) x0_out[base + i] = x0;
-    }
-}
-
 __global__ void add_scalar_i64_kernel(int64_t* t, int count, int64_t delta) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < count) t[i] += delta;
-}
-
-// One DDIM step (ddim_sample_loop, diffusion_ddpm.py:402-444, x_start / pred_noise as model_predictions(clip_x_start=True,
-// rederive_pred_noise=False), :242-264).  Every scene is at the same step: the step index k comes from a device counter and the
-// per-step scalars from device tables of S rows (t, t_next, sqrt(alpha_next), c, sigma), so the launch can be captured once and
-// replayed.  x_start is always clamped to [-1, 1] (the reference ignores clip_denoised here).  t_next < 0 (the last pair): out = x_start
-// and the noise is not read.  Each product and sum is rounded on its own, and the division is IEEE (no fast-math): bit-identical
-// to the reference's fp32 expressions.
-__global__ __launch_bounds__(256) void ddim_step_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ noise,
-                                                       const int64_t* __restrict__ step, const int64_t* __restrict__ times,
-                                                       const int64_t* __restrict__ times_next, const float* __restrict__ sqrt_an,
-                                                       const float* __restrict__ cnoise, const float* __restrict__ sigma,
-                                                       const float* __restrict__ ca, const float* __restrict__ cb,
-                                                       const float* __restrict__ ra, const float* __restrict__ rm,
-                                                       float* out,   // out may alias xt (in-place step)
-                                                       float* __restrict__ x0_out, int mean_type, int64_t inner, int S, int T) {
-    const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;               // one count per launch
-    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first, false);
-    const int64_t base = (int64_t)b * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = xt[base + i], m = mo[base + i];
-        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
-        if (x0_out) x0_out[base + i] = x0;
-        if (d.last) { out[base + i] = x0; continue; }
-        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
-    }
 }
 
 // Advance of the captured DDIM loop: step += 1, then t[i] = times[step] for the next model call.  One block: every thread reads the
@@ -171,187 +126,6 @@ __global__ __launch_bounds__(256) void ddim_advance_kernel(int64_t* step, const 
     if (threadIdx.x == 0) step[0] = k;
     const int64_t tv = times[dsc_checked_index(k, S, threadIdx.x == 0)];
     for (int i = threadIdx.x; i < count; i += blockDim.x) t[i] = tv;
-}
-
-__global__ __launch_bounds__(256) void complete_overwrite_kernel(float* __restrict__ x, const float* __restrict__ partial,
-                                                                const float* __restrict__ noise,
-                                                                const int64_t* __restrict__ t, const float* __restrict__ sa,
-                                                                const float* __restrict__ sb, int n, int p, int c, int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const float a = sa[tv], s = sb[tv];
-    const int64_t cnt = (int64_t)p * c;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        x[(int64_t)b * n * c + i] = renoise(partial[(int64_t)b * cnt + i], noise[(int64_t)b * cnt + i], a, s);   // rows [0,p) of scene b are the first p*c elements
-    }
-}
-
-// complete_overwrite_kernel with a per-scene row count: scene b writes rows [0, counts[b]) of x (n rows), reading rows of partial /
-// noise (pmax rows per scene; rows >= counts[b] are padding and never read).  counts[b] is clamped into [0, pmax] and an
-// out-of-range value counted like a bad timestep.  The grid covers pmax rows; a scene with count 0 writes nothing.
-__global__ __launch_bounds__(256) void complete_overwrite_ragged_kernel(float* __restrict__ x, const float* __restrict__ partial,
-                                                                       const float* __restrict__ noise,
-                                                                       const int64_t* __restrict__ counts,
-                                                                       const int64_t* __restrict__ t, const float* __restrict__ sa,
-                                                                       const float* __restrict__ sb, int n, int pmax, int c, int T) {
-    const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-    const int64_t tv = dsc_checked_index(t[b], T, first);
-    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
-    const float a = sa[tv], s = sb[tv];
-    const int64_t pbase = (int64_t)b * pmax * c;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
-        x[(int64_t)b * n * c + i] = renoise(partial[pbase + i], noise[pbase + i], a, s);   // rows [0,count) of scene b are its first count*c elements
-    }
-}
-
-// Fused step of the ragged completion loop: p_sample_kernel on rows >= counts[b]; rows < counts[b] (the given objects, whose
-// posterior step the next overwrite would discard) get what the loop writes there next -- q_sample(partial, t - 1, noise_p) when
-// t > 0 (the overwrite that precedes the next model call), partial itself when t == 0 (the final restore; noise_p is not read).
-// Same expressions, same rounding as p_sample_kernel and complete_overwrite_kernel: bit-identical to their composition.
-__global__ __launch_bounds__(256) void p_sample_inpaint_kernel(const float* xt, const float* __restrict__ mo,
-                                                              const float* __restrict__ noise, const float* __restrict__ partial,
-                                                              const float* __restrict__ noise_p,
-                                                              const int64_t* __restrict__ counts, const int64_t* __restrict__ t,
-                                                              const float* __restrict__ ca, const float* __restrict__ cb,
-                                                              const float* __restrict__ c1, const float* __restrict__ c2,
-                                                              const float* __restrict__ sigma, const float* __restrict__ sa,
-                                                              const float* __restrict__ sb, float* out,   // out may alias xt
-                                                              int mean_type, int clip, int n, int pmax, int c, int T) {
-    const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-    const int64_t tv = dsc_checked_index(t[b], T, first);
-    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
-    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
-    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
-    const int64_t inner = (int64_t)n * c;
-    const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        if (i < cnt) {
-            const float pv = partial[pbase + i];
-            out[base + i] = r.on ? renoise(pv, noise_p[pbase + i], r.a, r.s) : pv;
-            continue;
-        }
-        const float x = xt[base + i], m = mo[base + i];
-        out[base + i] = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
-    }
-}
-
-// Fused step of the strided (DDIM) ragged completion loop: ddim_step_kernel on rows >= counts[b]; rows < counts[b] (the given
-// objects, whose update the next overwrite would discard) get what the loop writes there next -- q_sample(partial, t_next, noise_p)
-// when t_next >= 0 (the overwrite that precedes the next model call), partial itself on the last pair (the final restore; neither
-// noise nor noise_p is read there).  Same expressions, same rounding as ddim_step_kernel and complete_overwrite_ragged_kernel:
-// bit-identical to their composition.
-__global__ __launch_bounds__(256) void ddim_inpaint_step_kernel(const float* xt, const float* __restrict__ mo,
-                                                               const float* __restrict__ noise, const float* __restrict__ partial,
-                                                               const float* __restrict__ noise_p,
-                                                               const int64_t* __restrict__ counts, const int64_t* __restrict__ step,
-                                                               const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
-                                                               const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
-                                                               const float* __restrict__ sigma, const float* __restrict__ ca,
-                                                               const float* __restrict__ cb, const float* __restrict__ ra,
-                                                               const float* __restrict__ rm, const float* __restrict__ sa,
-                                                               const float* __restrict__ sb, float* out,   // out may alias xt
-                                                               int mean_type, int n, int pmax, int c, int S, int T) {
-    const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && threadIdx.x == 0;                                  // one count per out-of-range scene
-    const bool first_all = first && blockIdx.y == 0;                                         // one count per launch
-    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
-    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
-    const int64_t cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
-    const int64_t inner = (int64_t)n * c;
-    const int64_t base = (int64_t)b * inner, pbase = (int64_t)b * pmax * c;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        if (i < cnt) {
-            const float pv = partial[pbase + i];
-            out[base + i] = r.on ? renoise(pv, noise_p[pbase + i], r.a, r.s) : pv;
-            continue;
-        }
-        const float x = xt[base + i], m = mo[base + i];
-        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
-        if (d.last) { out[base + i] = x0; continue; }
-        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
-    }
-}
-
-// Element-wise in-painting (p_sample_loop_masked, ddim_masked_loop): the set of given elements is a (b, n, c) byte mask, any non-zero
-// byte = given, instead of a row prefix.  known / noise / mask have x's shape.  Masked elements: x = sa[t] * known + sb[t] * noise;
-// the others are neither read nor written.
-__global__ __launch_bounds__(256) void masked_overwrite_kernel(float* __restrict__ x, const float* __restrict__ known,
-                                                              const float* __restrict__ noise, const uint8_t* __restrict__ mask,
-                                                              const int64_t* __restrict__ t, const float* __restrict__ sa,
-                                                              const float* __restrict__ sb, int64_t inner, int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const float a = sa[tv], s = sb[tv];
-    const int64_t base = (int64_t)b * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        if (!mask[base + i]) continue;
-        x[base + i] = renoise(known[base + i], noise[base + i], a, s);
-    }
-}
-
-// Fused step of the masked loop: p_sample_kernel on the free elements; a given element (whose posterior step the next overwrite
-// would discard) gets what the loop writes there next -- q_sample(known, t - 1, noise_k) when t > 0, known itself when t == 0 (the
-// final select; noise_k is not read).  A given element reads mask, known and noise_k only; a free one mask, xt, mo and noise only:
-// an all-free launch moves p_sample_kernel's bytes plus one byte per element.  Same expressions, same rounding as p_sample_kernel and
-// masked_overwrite_kernel: bit-identical to their composition.
-__global__ __launch_bounds__(256) void p_sample_masked_kernel(const float* xt, const float* __restrict__ mo,
-                                                             const float* __restrict__ noise, const float* __restrict__ known,
-                                                             const float* __restrict__ noise_k, const uint8_t* __restrict__ mask,
-                                                             const int64_t* __restrict__ t,
-                                                             const float* __restrict__ ca, const float* __restrict__ cb,
-                                                             const float* __restrict__ c1, const float* __restrict__ c2,
-                                                             const float* __restrict__ sigma, const float* __restrict__ sa,
-                                                             const float* __restrict__ sb, float* out,   // out may alias xt
-                                                             int mean_type, int clip, int64_t inner, int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
-    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
-    const int64_t base = (int64_t)b * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        if (mask[base + i]) {
-            const float kv = known[base + i];
-            out[base + i] = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
-            continue;
-        }
-        const float x = xt[base + i], m = mo[base + i];
-        out[base + i] = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
-    }
-}
-
-// Fused step of the strided (DDIM) masked loop: ddim_step_kernel on the free elements; a given element gets q_sample(known, t_next,
-// noise_k) when t_next >= 0, known itself on the last pair (neither noise nor noise_k is read there).  Reads per element as
-// p_sample_masked_kernel; index checks as ddim_inpaint_step_kernel.  Bit-identical to ddim_step_kernel followed by
-// masked_overwrite_kernel at t_next (or by the final select).
-__global__ __launch_bounds__(256) void ddim_masked_step_kernel(const float* xt, const float* __restrict__ mo,
-                                                              const float* __restrict__ noise, const float* __restrict__ known,
-                                                              const float* __restrict__ noise_k, const uint8_t* __restrict__ mask,
-                                                              const int64_t* __restrict__ step,
-                                                              const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
-                                                              const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
-                                                              const float* __restrict__ sigma, const float* __restrict__ ca,
-                                                              const float* __restrict__ cb, const float* __restrict__ ra,
-                                                              const float* __restrict__ rm, const float* __restrict__ sa,
-                                                              const float* __restrict__ sb, float* out,   // out may alias xt
-                                                              int mean_type, int64_t inner, int S, int T) {
-    const int b = blockIdx.y;
-    const bool first_all = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;           // one count per launch
-    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
-    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
-    const int64_t base = (int64_t)b * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        if (mask[base + i]) {
-            const float kv = known[base + i];
-            out[base + i] = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
-            continue;
-        }
-        const float x = xt[base + i], m = mo[base + i];
-        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
-        if (d.last) { out[base + i] = x0; continue; }
-        out[base + i] = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
-    }
 }
 
 // Classifier-free guidance (p_sample_loop_guided / ddim_guided_loop).  model_out holds 2 b scenes: rows [0, b) are the denoiser on the
@@ -374,127 +148,132 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
         out[base + i] = cfg_mix(mo[base + i], mo[half + base + i], w);
 }
 
-// p_sample_kernel with m computed in registers from the two halves of mo.  x_dup (may be NULL): a second copy of the new x, so that a
-// captured loop can keep x as one (2 b, inner) buffer with both halves current.  At t == 0 the noise is not read (p_sample_kernel
-// adds 0 * noise there).  Same expressions, same rounding as cfg_combine_kernel followed by p_sample_kernel: equal to their composition
-// on finite noise (torch.equal; the sign of a zero result may differ at t == 0).
-__global__ __launch_bounds__(256) void p_sample_cfg_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ scale,
-                                                          const float* __restrict__ noise, const int64_t* __restrict__ t,
-                                                          const float* __restrict__ ca, const float* __restrict__ cb,
-                                                          const float* __restrict__ c1, const float* __restrict__ c2,
-                                                          const float* __restrict__ sigma, float* out,   // out may alias xt
-                                                          float* __restrict__ x_dup, float* __restrict__ x0_out, int mean_type, int clip,
-                                                          int64_t inner, int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, false);
-    const float w = scale[b];
-    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-        const float x0 = predict_x0(x, m, p.A, p.Bc, mean_type, clip);
-        float y = posterior_mean(x0, x, p);       // t == 0: sigma is forced to 0 and the noise is not read
-        if (tv != 0) y = add_noise(y, noise[base + i], p.sg);
-        out[base + i] = y;
-        if (x_dup) x_dup[base + i] = y;
-        if (x0_out) x0_out[base + i] = x0;
-    }
-}
+// Which elements of a scene are given (completion, in-painting) instead of sampled: none, the first counts[b] rows, or a byte mask.
+enum { GIVEN_NONE = 0, GIVEN_ROWS = 1, GIVEN_MASK = 2 };
 
-// ddim_step_kernel with m computed in registers from the two halves of mo; x_dup as in p_sample_cfg_kernel.  On the last pair the
-// noise is not read.  Bit-identical to cfg_combine_kernel followed by ddim_step_kernel.
-__global__ __launch_bounds__(256) void ddim_cfg_step_kernel(const float* xt, const float* __restrict__ mo, const float* __restrict__ scale,
-                                                           const float* __restrict__ noise, const int64_t* __restrict__ step,
-                                                           const int64_t* __restrict__ times, const int64_t* __restrict__ times_next,
-                                                           const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
-                                                           const float* __restrict__ sigma, const float* __restrict__ ca,
-                                                           const float* __restrict__ cb, const float* __restrict__ ra,
-                                                           const float* __restrict__ rm, float* out,   // out may alias xt
-                                                           float* __restrict__ x_dup, float* __restrict__ x0_out, int mean_type,
-                                                           int64_t inner, int S, int T) {
+// The reverse step, one launch after the model call: every dsc_*p_sample*_f32 and dsc_ddim_*step_f32 is one instantiation.
+//
+//   STRIDED  false: the posterior step of p_sample (diffusion_ddpm.py:305-352) at the scene's own row tv = t[b]:
+//                   out = k1 * x0 + k2 * x + sigma[tv] * noise, x0 clamped to [-1, 1] per ``clip``.
+//            true:  one pair of ddim_sample_loop (:402-444; x_start / pred_noise as model_predictions(clip_x_start=True,
+//                   rederive_pred_noise=False), :242-264).  Every scene is at the same pair k = step[0], a device counter, and the
+//                   per-pair scalars come from device tables of S rows, so the launch can be captured once and replayed.  x0 is
+//                   always clamped (the reference ignores clip_denoised here).  times_next[k] < 0 marks the last pair: out = x0.
+//   GIVEN    none:  every element is free.
+//            rows:  rows [0, counts[b]) of scene b are given; given / noise_g hold pmax rows per scene (rows >= counts[b] are padding,
+//                   never read), so the given part is indexed at b * pmax * c + i, the rest at b * n * c + i.
+//            mask:  element i is given where mask[i] != 0; mask / given / noise_g have x's shape.
+//   GUIDED   mo holds 2 b scenes, [conditional; unconditional] on the same x, and m = cfg_mix(c, u, scale[b]) is formed in registers;
+//            x_dup (may be NULL) receives a second copy of every written element, given or free, so that a captured loop keeps x
+//            as one (2 b, inner) buffer with both halves current.
+//
+// A free element gets the step.  A given one, whose step the loop's next overwrite would discard, gets what the loop writes there
+// next: q_sample(given, t - 1 or times_next[k], noise_g) -- the overwrite that precedes the next model call -- or, at t == 0 / on the
+// last pair, given itself (the final restore).  What every instantiation keeps:
+//
+// * Rounding.  Every product, sum and difference is a statement of its own in the helpers above, operands in the reference's order,
+//   the division IEEE: a fused instantiation is bit-identical to the composition of the unfused ones (cfg_combine, then the plain
+//   step, then the overwrite at the next time or the restore), and the plain ones to the reference's fp32 expressions.
+// * Noise at t == 0.  The posterior instantiations force sigma to 0 at tv == 0 and still add 0 * noise: infinite noise gives NaN on
+//   a free element.  The exception is <posterior, none, guided> (SKIP_NOISE_AT_0): it loads sigma as tabulated and does not read the
+//   noise at tv == 0 -- equal to the composition on finite noise, up to the sign of a zero.  tests/test_gpu_sampler_core.py pins both.
+// * Last strided pair.  Neither noise nor noise_g is read.
+// * Read sets.  A given element reads mask (nothing, for rows), given and noise_g only -- no noise_g at t == 0 or on the last pair;
+//   a free one mask, xt, mo (both halves if guided) and noise only.  A pointer an instantiation has no use for is never loaded.
+// * Bad indices (clamped, then counted by one thread each).  t[b] and counts[b] (into [0, pmax]): once per out-of-range scene, by
+//   thread 0 of block x = 0.  step[0], times[k] and -- only where a given part exists and the pair is not the last -- times_next[k]:
+//   once per launch.
+// * Outputs.  out may alias xt (the in-place step), so neither is __restrict__, and an element is stored only after all of its loads.
+//   x0_out (may be NULL) exists only without a given part.
+template <bool STRIDED, int GIVEN, bool GUIDED>
+__global__ __launch_bounds__(256) void step_kernel(
+    const float* xt, const float* __restrict__ mo, const float* __restrict__ scale, const float* __restrict__ noise,
+    const float* __restrict__ given, const float* __restrict__ noise_g, const uint8_t* __restrict__ mask,
+    const int64_t* __restrict__ counts, const int64_t* __restrict__ t, const int64_t* __restrict__ step,
+    const int64_t* __restrict__ times, const int64_t* __restrict__ times_next, const float* __restrict__ sqrt_an,
+    const float* __restrict__ cnoise, const float* __restrict__ sigma, const float* __restrict__ ca, const float* __restrict__ cb,
+    const float* __restrict__ c1, const float* __restrict__ c2, const float* __restrict__ ra, const float* __restrict__ rm,
+    const float* __restrict__ sa, const float* __restrict__ sb, float* out, float* __restrict__ x_dup, float* __restrict__ x0_out,
+    int mean_type, int clip, int64_t inner, int pmax, int c, int S, int T) {
+    constexpr bool HAS_GIVEN = GIVEN != GIVEN_NONE;
+    constexpr bool SKIP_NOISE_AT_0 = !STRIDED && !HAS_GIVEN && GUIDED;
     const int b = blockIdx.y;
-    const bool first = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;               // one count per launch
-    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first, false);
-    const float w = scale[b];
-    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-        const float x0 = predict_x0(x, m, d.A, d.Bc, mean_type, true);
-        if (x0_out) x0_out[base + i] = x0;
-        float y = x0;
-        if (!d.last) y = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
-        out[base + i] = y;
-        if (x_dup) x_dup[base + i] = y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;                                  // one count per out-of-range scene
+    PosteriorCoef p{};
+    DdimCoef d{};
+    Renoise r{};
+    int64_t tv = 0;
+    if constexpr (STRIDED) {
+        d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first && b == 0, HAS_GIVEN);
+        if constexpr (HAS_GIVEN) r = renoise_coef(!d.last, d.tn, sa, sb);
+    } else {
+        tv = dsc_checked_index(t[b], T, first);
+        p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, !SKIP_NOISE_AT_0);
+        if constexpr (HAS_GIVEN) r = renoise_coef(tv > 0, tv - 1, sa, sb);
     }
-}
-
-// Guided in-painting (p_sample_loop_masked_guided): p_sample_masked_kernel with m computed in registers from the two halves of mo
-// (2 b, inner); known / noise_k / mask stay (b, inner).  x_dup as in p_sample_cfg_kernel: every written element, given or free, goes
-// there too.  A given element reads mask, known and noise_k only (no noise_k at t == 0); a free one mask, xt, both halves of mo and
-// noise only.  Bit-identical to cfg_combine_kernel followed by p_sample_masked_kernel.
-__global__ __launch_bounds__(256) void p_sample_masked_cfg_kernel(const float* xt, const float* __restrict__ mo,
-                                                                 const float* __restrict__ scale, const float* __restrict__ noise,
-                                                                 const float* __restrict__ known, const float* __restrict__ noise_k,
-                                                                 const uint8_t* __restrict__ mask, const int64_t* __restrict__ t,
-                                                                 const float* __restrict__ ca, const float* __restrict__ cb,
-                                                                 const float* __restrict__ c1, const float* __restrict__ c2,
-                                                                 const float* __restrict__ sigma, const float* __restrict__ sa,
-                                                                 const float* __restrict__ sb, float* out,   // out may alias xt
-                                                                 float* __restrict__ x_dup, int mean_type, int clip, int64_t inner,
-                                                                 int T) {
-    const int b = blockIdx.y;
-    const int64_t tv = dsc_checked_index(t[b], T, blockIdx.x == 0 && threadIdx.x == 0);      // one count per out-of-range scene
-    const PosteriorCoef p = posterior_coef(tv, ca, cb, c1, c2, sigma, mean_type, true);
-    const Renoise r = renoise_coef(tv > 0, tv - 1, sa, sb);
-    const float w = scale[b];
+    const float A = STRIDED ? d.A : p.A, Bc = STRIDED ? d.Bc : p.Bc;
+    int64_t cnt = 0;
+    if constexpr (GIVEN == GIVEN_ROWS) cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    float w = 0.f;
+    if constexpr (GUIDED) w = scale[b];
     const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    const int64_t gbase = GIVEN == GIVEN_ROWS ? (int64_t)b * pmax * c : base;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        float y;
-        if (mask[base + i]) {
-            const float kv = known[base + i];
-            y = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
+        bool is_given = false;
+        if constexpr (GIVEN == GIVEN_ROWS) is_given = i < cnt;
+        if constexpr (GIVEN == GIVEN_MASK) is_given = mask[base + i] != 0;
+        float y, x0 = 0.f;
+        if (is_given) {
+            const float g = given[gbase + i];
+            y = r.on ? renoise(g, noise_g[gbase + i], r.a, r.s) : g;
         } else {
-            const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-            y = add_noise(posterior_mean(predict_x0(x, m, p.A, p.Bc, mean_type, clip), x, p), noise[base + i], p.sg);
+            const float x = xt[base + i];
+            float m = mo[base + i];
+            if constexpr (GUIDED) m = cfg_mix(m, mo[half + base + i], w);
+            x0 = predict_x0(x, m, A, Bc, mean_type, STRIDED || clip);
+            if constexpr (STRIDED) {
+                y = x0;
+                if (!d.last) y = add_noise(ddim_mean(x0, x, m, d, mean_type), noise[base + i], d.sg);
+            } else {
+                y = posterior_mean(x0, x, p);
+                if (!SKIP_NOISE_AT_0 || tv != 0) y = add_noise(y, noise[base + i], p.sg);
+            }
         }
         out[base + i] = y;
-        if (x_dup) x_dup[base + i] = y;
+        if constexpr (GUIDED) {
+            if (x_dup) x_dup[base + i] = y;
+        }
+        if constexpr (!HAS_GIVEN) {
+            if (x0_out) x0_out[base + i] = x0;
+        }
     }
 }
 
-// The strided twin (ddim_masked_guided_loop): ddim_masked_step_kernel with the same change and the same x_dup; index checks as there.
-// On the last pair neither noise nor noise_k is read.  Bit-identical to cfg_combine_kernel followed by ddim_masked_step_kernel.
-__global__ __launch_bounds__(256) void ddim_masked_cfg_step_kernel(const float* xt, const float* __restrict__ mo,
-                                                                  const float* __restrict__ scale, const float* __restrict__ noise,
-                                                                  const float* __restrict__ known, const float* __restrict__ noise_k,
-                                                                  const uint8_t* __restrict__ mask, const int64_t* __restrict__ step,
-                                                                  const int64_t* __restrict__ times,
-                                                                  const int64_t* __restrict__ times_next,
-                                                                  const float* __restrict__ sqrt_an, const float* __restrict__ cnoise,
-                                                                  const float* __restrict__ sigma, const float* __restrict__ ca,
-                                                                  const float* __restrict__ cb, const float* __restrict__ ra,
-                                                                  const float* __restrict__ rm, const float* __restrict__ sa,
-                                                                  const float* __restrict__ sb, float* out,   // out may alias xt
-                                                                  float* __restrict__ x_dup, int mean_type, int64_t inner, int S,
-                                                                  int T) {
+// The standalone overwrite of the completion and in-painting loops (p_sample_loop_complete, diffusion_ddpm.py:462-466, and its ragged
+// and masked forms): the given branch of step_kernel at the scene's own t[b], x = sa[t] * given + sb[t] * noise_g, and no free
+// branch -- an element that is not given is neither read nor written.  rows: the grid covers the pmax * c elements of a scene's given
+// part; a scene with count 0 writes nothing; counts == NULL is the fixed form, every scene has pmax rows and nothing but t[b] is
+// counted.  mask: the grid covers the scene.  Indices and their counting as in step_kernel.
+template <int GIVEN>
+__global__ __launch_bounds__(256) void overwrite_kernel(float* __restrict__ x, const float* __restrict__ given,
+                                                       const float* __restrict__ noise_g, const uint8_t* __restrict__ mask,
+                                                       const int64_t* __restrict__ counts, const int64_t* __restrict__ t,
+                                                       const float* __restrict__ sa, const float* __restrict__ sb, int64_t inner,
+                                                       int pmax, int c, int T) {
+    static_assert(GIVEN == GIVEN_ROWS || GIVEN == GIVEN_MASK, "an overwrite needs a given part");
     const int b = blockIdx.y;
-    const bool first_all = blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;           // one count per launch
-    const DdimCoef d = ddim_coef(step, times, times_next, sqrt_an, cnoise, sigma, ca, cb, ra, rm, mean_type, S, T, first_all, true);
-    const Renoise r = renoise_coef(!d.last, d.tn, sa, sb);
-    const float w = scale[b];
-    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
-        float y;
-        if (mask[base + i]) {
-            const float kv = known[base + i];
-            y = r.on ? renoise(kv, noise_k[base + i], r.a, r.s) : kv;
-        } else {
-            const float x = xt[base + i], m = cfg_mix(mo[base + i], mo[half + base + i], w);
-            y = predict_x0(x, m, d.A, d.Bc, mean_type, true);
-            if (!d.last) y = add_noise(ddim_mean(y, x, m, d, mean_type), noise[base + i], d.sg);
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;                                  // one count per out-of-range scene
+    const int64_t tv = dsc_checked_index(t[b], T, first);
+    const float a = sa[tv], s = sb[tv];
+    int64_t cnt = inner;
+    if constexpr (GIVEN == GIVEN_ROWS) cnt = (counts ? dsc_checked_index(counts[b], (int64_t)pmax + 1, first) : (int64_t)pmax) * c;
+    const int64_t base = (int64_t)b * inner;
+    const int64_t gbase = GIVEN == GIVEN_ROWS ? (int64_t)b * pmax * c : base;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+        if constexpr (GIVEN == GIVEN_MASK) {
+            if (!mask[base + i]) continue;
         }
-        out[base + i] = y;
-        if (x_dup) x_dup[base + i] = y;
+        x[base + i] = renoise(given[gbase + i], noise_g[gbase + i], a, s);
     }
 }
 
@@ -647,6 +426,60 @@ inline unsigned grid_x(int64_t inner) {
     return (unsigned)(g > 64 ? 64 : g);
 }
 
+// The operands of step_kernel under its parameter names; an entry point fills what its instantiation reads and leaves the rest null.
+// rows: n, pmax, c describe the scene (inner = n * c); otherwise inner does.
+struct StepArgs {
+    const float *xt, *mo, *scale, *noise, *given, *noise_g;
+    const uint8_t* mask;
+    const int64_t *counts, *t, *step, *times, *times_next;
+    const float *sqrt_an, *cnoise, *sigma, *ca, *cb, *c1, *c2, *ra, *rm, *sa, *sb;
+    float *out, *x_dup, *x0_out;
+    int32_t mean_type, clip, b;
+    int64_t inner;
+    int32_t n, pmax, c, S, T;
+};
+
+// The argument checks and the launch of every step.  Required: the operands of the free branch, the tables of the axis values and
+// ca / cb as bad_mean_args says; x_dup and x0_out may be null.  blockIdx.y carries the scene: b <= 65535.
+template <bool STRIDED, int GIVEN, bool GUIDED>
+int launch_step(const StepArgs& a, dsc_stream_t stream) {
+    static_assert(!(GIVEN == GIVEN_ROWS && GUIDED), "guided completion has no caller: not instantiated");
+    constexpr bool HAS_GIVEN = GIVEN != GIVEN_NONE;
+    if (!a.xt || !a.mo || !a.noise || !a.sigma || !a.out || a.b < 1 || a.T < 1) return DSC_EINVAL;
+    if (STRIDED ? !a.step || !a.times || !a.times_next || !a.sqrt_an || !a.cnoise || !a.ra || !a.rm || a.S < 1 : !a.t || !a.c1 || !a.c2)
+        return DSC_EINVAL;
+    if (HAS_GIVEN && (!a.given || !a.noise_g || !a.sa || !a.sb)) return DSC_EINVAL;
+    if (GIVEN == GIVEN_ROWS ? !a.counts || a.n < 1 || a.pmax < 1 || a.pmax > a.n || a.c < 1 : a.inner < 1) return DSC_EINVAL;
+    if ((GIVEN == GIVEN_MASK && !a.mask) || (GUIDED && !a.scale)) return DSC_EINVAL;
+    if (bad_mean_args(a.mean_type, a.ca, a.cb)) return DSC_EINVAL;
+    if (a.b > 65535) return DSC_ERANGE;
+    const int64_t inner = GIVEN == GIVEN_ROWS ? (int64_t)a.n * a.c : a.inner;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL((step_kernel<STRIDED, GIVEN, GUIDED>), dim3(grid_x(inner), a.b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       a.xt, a.mo, a.scale, a.noise, a.given, a.noise_g, a.mask, a.counts, a.t, a.step, a.times, a.times_next, a.sqrt_an,
+                       a.cnoise, a.sigma, a.ca, a.cb, a.c1, a.c2, a.ra, a.rm, a.sa, a.sb, a.out, a.x_dup, a.x0_out, a.mean_type, a.clip,
+                       inner, a.pmax, a.c, a.S, a.T);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same for the three overwrites; counts is required by the ragged entry point alone, which checks it.
+template <int GIVEN>
+int launch_overwrite(float* x, const float* given, const float* noise_g, const uint8_t* mask, const int64_t* counts, const int64_t* t,
+                     const float* sa, const float* sb, int32_t b, int64_t inner, int32_t n, int32_t pmax, int32_t c, int32_t T,
+                     dsc_stream_t stream) {
+    if (!x || !given || !noise_g || !t || !sa || !sb || b < 1 || T < 1) return DSC_EINVAL;
+    if (GIVEN == GIVEN_ROWS ? n < 1 || pmax < 1 || pmax > n || c < 1 : !mask || inner < 1) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;
+    if (GIVEN == GIVEN_ROWS) inner = (int64_t)n * c;
+    const int64_t covered = GIVEN == GIVEN_ROWS ? (int64_t)pmax * c : inner;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL((overwrite_kernel<GIVEN>), dim3(grid_x(covered), b), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       x, given, noise_g, mask, counts, t, sa, sb, inner, pmax, c, T);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int dsc_q_sample_f32(const float* x0, const float* noise, const int64_t* t, const float* sqrt_ac,
@@ -664,14 +497,11 @@ extern "C" int dsc_p_sample_f32(const float* x_t, const float* model_out, const 
                                 const float* ca, const float* cb, const float* coef1, const float* coef2,
                                 const float* sigma, float* out, float* x0_out, int32_t mean_type, int32_t clip,
                                 int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !t || !coef1 || !coef2 || !sigma || !out || b < 1 || inner < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(p_sample_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, t, ca, cb, coef1, coef2, sigma, out, x0_out, mean_type, clip, inner, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out, a.x0_out = x0_out;
+    a.t = t, a.ca = ca, a.cb = cb, a.c1 = coef1, a.c2 = coef2, a.sigma = sigma;
+    a.mean_type = mean_type, a.clip = clip, a.b = b, a.inner = inner, a.T = num_timesteps;
+    return launch_step<false, GIVEN_NONE, false>(a, stream);
 }
 
 extern "C" int dsc_add_scalar_i64(int64_t* t, int32_t count, int64_t delta, dsc_stream_t stream) {
@@ -689,17 +519,12 @@ extern "C" int dsc_ddim_step_f32(const float* x_t, const float* model_out, const
                                  const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float* out, float* x0_out,
                                  int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
                                  dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
-        !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ddim_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca, cb,
-                       sqrt_recip_ac, sqrt_recipm1_ac, out, x0_out, mean_type, inner, num_steps, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out, a.x0_out = x0_out;
+    a.step = step, a.times = times, a.times_next = times_next, a.sqrt_an = sqrt_alpha_next, a.cnoise = c_noise, a.sigma = sigma;
+    a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
+    a.mean_type = mean_type, a.b = b, a.inner = inner, a.S = num_steps, a.T = num_timesteps;
+    return launch_step<true, GIVEN_NONE, false>(a, stream);
 }
 
 extern "C" int dsc_ddim_advance_i64(int64_t* step, const int64_t* times, int64_t* t, int32_t count, int32_t num_steps,
@@ -728,27 +553,20 @@ extern "C" int dsc_postfilter_compact_f32(const float* samples, int32_t b, int32
 extern "C" int dsc_complete_overwrite_f32(float* x, const float* partial, const float* noise, const int64_t* t,
                                           const float* sqrt_ac, const float* sqrt_1mac, int32_t b, int32_t n,
                                           int32_t p, int32_t c, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x || !partial || !noise || !t || !sqrt_ac || !sqrt_1mac || b < 1 || n < 1 || p < 1 || p > n || c < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(complete_overwrite_kernel, dim3(grid_x((int64_t)p * c), b), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, partial, noise, t, sqrt_ac, sqrt_1mac, n, p, c, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    return launch_overwrite<GIVEN_ROWS>(x, partial, noise, nullptr, nullptr, t, sqrt_ac, sqrt_1mac, b, 0, n, p, c, num_timesteps, stream);
 }
 
 extern "C" int dsc_complete_overwrite_ragged_f32(float* x, const float* partial, const float* noise, const int64_t* counts,
                                                  const int64_t* t, const float* sqrt_ac, const float* sqrt_1mac, int32_t b,
                                                  int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x || !partial || !noise || !counts || !t || !sqrt_ac || !sqrt_1mac || b < 1 || n < 1 || pmax < 1 || pmax > n || c < 1 ||
-        num_timesteps < 1)
-        return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(complete_overwrite_ragged_kernel, dim3(grid_x((int64_t)pmax * c), b), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), x, partial, noise, counts, t, sqrt_ac, sqrt_1mac, n, pmax, c, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    if (!counts) return DSC_EINVAL;
+    return launch_overwrite<GIVEN_ROWS>(x, partial, noise, nullptr, counts, t, sqrt_ac, sqrt_1mac, b, 0, n, pmax, c, num_timesteps, stream);
+}
+
+extern "C" int dsc_masked_overwrite_f32(float* x, const float* known, const float* noise, const uint8_t* mask, const int64_t* t,
+                                        const float* sqrt_ac, const float* sqrt_1mac, int32_t b, int64_t inner,
+                                        int32_t num_timesteps, dsc_stream_t stream) {
+    return launch_overwrite<GIVEN_MASK>(x, known, noise, mask, nullptr, t, sqrt_ac, sqrt_1mac, b, inner, 0, 0, 0, num_timesteps, stream);
 }
 
 extern "C" int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
@@ -756,17 +574,12 @@ extern "C" int dsc_p_sample_inpaint_f32(const float* x_t, const float* model_out
                                         const float* cb, const float* coef1, const float* coef2, const float* sigma,
                                         const float* sqrt_ac, const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip,
                                         int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !partial || !noise_p || !counts || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
-        !out || b < 1 || n < 1 || pmax < 1 || pmax > n || c < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(p_sample_inpaint_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, partial, noise_p, counts, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
-                       mean_type, clip, n, pmax, c, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out;
+    a.given = partial, a.noise_g = noise_p, a.counts = counts, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.t = t, a.ca = ca, a.cb = cb, a.c1 = coef1, a.c2 = coef2, a.sigma = sigma;
+    a.mean_type = mean_type, a.clip = clip, a.b = b, a.n = n, a.pmax = pmax, a.c = c, a.T = num_timesteps;
+    return launch_step<false, GIVEN_ROWS, false>(a, stream);
 }
 
 extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_out, const float* noise, const float* partial,
@@ -776,30 +589,13 @@ extern "C" int dsc_ddim_inpaint_step_f32(const float* x_t, const float* model_ou
                                          const float* sqrt_recipm1_ac, const float* sqrt_ac, const float* sqrt_1mac, float* out,
                                          int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t num_steps,
                                          int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !partial || !noise_p || !counts || !step || !times || !times_next || !sqrt_alpha_next ||
-        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || n < 1 || pmax < 1 ||
-        pmax > n || c < 1 || num_steps < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ddim_inpaint_step_kernel, dim3(grid_x((int64_t)n * c), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, partial, noise_p, counts, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
-                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, n, pmax, c, num_steps, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int dsc_masked_overwrite_f32(float* x, const float* known, const float* noise, const uint8_t* mask, const int64_t* t,
-                                        const float* sqrt_ac, const float* sqrt_1mac, int32_t b, int64_t inner,
-                                        int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x || !known || !noise || !mask || !t || !sqrt_ac || !sqrt_1mac || b < 1 || inner < 1 || num_timesteps < 1) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(masked_overwrite_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x, known, noise, mask, t, sqrt_ac, sqrt_1mac, inner, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out;
+    a.given = partial, a.noise_g = noise_p, a.counts = counts, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.step = step, a.times = times, a.times_next = times_next, a.sqrt_an = sqrt_alpha_next, a.cnoise = c_noise, a.sigma = sigma;
+    a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
+    a.mean_type = mean_type, a.b = b, a.n = n, a.pmax = pmax, a.c = c, a.S = num_steps, a.T = num_timesteps;
+    return launch_step<true, GIVEN_ROWS, false>(a, stream);
 }
 
 extern "C" int dsc_p_sample_masked_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
@@ -807,17 +603,12 @@ extern "C" int dsc_p_sample_masked_f32(const float* x_t, const float* model_out,
                                        const float* coef1, const float* coef2, const float* sigma, const float* sqrt_ac,
                                        const float* sqrt_1mac, float* out, int32_t mean_type, int32_t clip, int32_t b, int64_t inner,
                                        int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !known || !noise_k || !mask || !t || !coef1 || !coef2 || !sigma || !sqrt_ac || !sqrt_1mac ||
-        !out || b < 1 || inner < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(p_sample_masked_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
-                       mean_type, clip, inner, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out;
+    a.given = known, a.noise_g = noise_k, a.mask = mask, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.t = t, a.ca = ca, a.cb = cb, a.c1 = coef1, a.c2 = coef2, a.sigma = sigma;
+    a.mean_type = mean_type, a.clip = clip, a.b = b, a.inner = inner, a.T = num_timesteps;
+    return launch_step<false, GIVEN_MASK, false>(a, stream);
 }
 
 extern "C" int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out, const float* noise, const float* known,
@@ -827,18 +618,13 @@ extern "C" int dsc_ddim_masked_step_f32(const float* x_t, const float* model_out
                                         const float* sqrt_recipm1_ac, const float* sqrt_ac, const float* sqrt_1mac, float* out,
                                         int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
                                         dsc_stream_t stream) {
-    if (!x_t || !model_out || !noise || !known || !noise_k || !mask || !step || !times || !times_next || !sqrt_alpha_next ||
-        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || inner < 1 ||
-        num_steps < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ddim_masked_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, noise, known, noise_k, mask, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
-                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, mean_type, inner, num_steps, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.noise = noise, a.out = out;
+    a.given = known, a.noise_g = noise_k, a.mask = mask, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.step = step, a.times = times, a.times_next = times_next, a.sqrt_an = sqrt_alpha_next, a.cnoise = c_noise, a.sigma = sigma;
+    a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
+    a.mean_type = mean_type, a.b = b, a.inner = inner, a.S = num_steps, a.T = num_timesteps;
+    return launch_step<true, GIVEN_MASK, false>(a, stream);
 }
 
 extern "C" int dsc_cfg_combine_f32(const float* model_out, const float* scale, float* out, int32_t b, int64_t inner,
@@ -856,16 +642,11 @@ extern "C" int dsc_p_sample_cfg_f32(const float* x_t, const float* model_out, co
                                     const float* ca, const float* cb, const float* coef1, const float* coef2, const float* sigma,
                                     float* out, float* x_dup, float* x0_out, int32_t mean_type, int32_t clip, int32_t b,
                                     int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !scale || !noise || !t || !coef1 || !coef2 || !sigma || !out || b < 1 || inner < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(p_sample_cfg_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, scale, noise, t, ca, cb, coef1, coef2, sigma, out, x_dup, x0_out, mean_type, clip, inner,
-                       num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.scale = scale, a.noise = noise, a.out = out, a.x_dup = x_dup, a.x0_out = x0_out;
+    a.t = t, a.ca = ca, a.cb = cb, a.c1 = coef1, a.c2 = coef2, a.sigma = sigma;
+    a.mean_type = mean_type, a.clip = clip, a.b = b, a.inner = inner, a.T = num_timesteps;
+    return launch_step<false, GIVEN_NONE, true>(a, stream);
 }
 
 extern "C" int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
@@ -874,17 +655,12 @@ extern "C" int dsc_ddim_cfg_step_f32(const float* x_t, const float* model_out, c
                                      const float* cb, const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, float* out,
                                      float* x_dup, float* x0_out, int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps,
                                      int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !scale || !noise || !step || !times || !times_next || !sqrt_alpha_next || !c_noise || !sigma ||
-        !sqrt_recip_ac || !sqrt_recipm1_ac || !out || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ddim_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, scale, noise, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca, cb,
-                       sqrt_recip_ac, sqrt_recipm1_ac, out, x_dup, x0_out, mean_type, inner, num_steps, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.scale = scale, a.noise = noise, a.out = out, a.x_dup = x_dup, a.x0_out = x0_out;
+    a.step = step, a.times = times, a.times_next = times_next, a.sqrt_an = sqrt_alpha_next, a.cnoise = c_noise, a.sigma = sigma;
+    a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
+    a.mean_type = mean_type, a.b = b, a.inner = inner, a.S = num_steps, a.T = num_timesteps;
+    return launch_step<true, GIVEN_NONE, true>(a, stream);
 }
 
 extern "C" int dsc_p_sample_masked_cfg_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
@@ -892,17 +668,12 @@ extern "C" int dsc_p_sample_masked_cfg_f32(const float* x_t, const float* model_
                                            const float* ca, const float* cb, const float* coef1, const float* coef2, const float* sigma,
                                            const float* sqrt_ac, const float* sqrt_1mac, float* out, float* x_dup, int32_t mean_type,
                                            int32_t clip, int32_t b, int64_t inner, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !scale || !noise || !known || !noise_k || !mask || !t || !coef1 || !coef2 || !sigma || !sqrt_ac ||
-        !sqrt_1mac || !out || b < 1 || inner < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(p_sample_masked_cfg_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, scale, noise, known, noise_k, mask, t, ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac, out,
-                       x_dup, mean_type, clip, inner, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.scale = scale, a.noise = noise, a.out = out, a.x_dup = x_dup;
+    a.given = known, a.noise_g = noise_k, a.mask = mask, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.t = t, a.ca = ca, a.cb = cb, a.c1 = coef1, a.c2 = coef2, a.sigma = sigma;
+    a.mean_type = mean_type, a.clip = clip, a.b = b, a.inner = inner, a.T = num_timesteps;
+    return launch_step<false, GIVEN_MASK, true>(a, stream);
 }
 
 extern "C" int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model_out, const float* scale, const float* noise,
@@ -912,18 +683,13 @@ extern "C" int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model
                                             const float* sqrt_recip_ac, const float* sqrt_recipm1_ac, const float* sqrt_ac,
                                             const float* sqrt_1mac, float* out, float* x_dup, int32_t mean_type, int32_t b,
                                             int64_t inner, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream) {
-    if (!x_t || !model_out || !scale || !noise || !known || !noise_k || !mask || !step || !times || !times_next || !sqrt_alpha_next ||
-        !c_noise || !sigma || !sqrt_recip_ac || !sqrt_recipm1_ac || !sqrt_ac || !sqrt_1mac || !out || b < 1 || inner < 1 ||
-        num_steps < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (bad_mean_args(mean_type, ca, cb)) return DSC_EINVAL;
-    if (b > 65535) return DSC_ERANGE;
-    DSC_CLEAR_STALE_ERROR();
-    hipLaunchKernelGGL(ddim_masked_cfg_step_kernel, dim3(grid_x(inner), b), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       x_t, model_out, scale, noise, known, noise_k, mask, step, times, times_next, sqrt_alpha_next, c_noise, sigma, ca,
-                       cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, out, x_dup, mean_type, inner, num_steps, num_timesteps);
-    DSC_LAUNCH_CHECK();
-    return 0;
+    StepArgs a{};
+    a.xt = x_t, a.mo = model_out, a.scale = scale, a.noise = noise, a.out = out, a.x_dup = x_dup;
+    a.given = known, a.noise_g = noise_k, a.mask = mask, a.sa = sqrt_ac, a.sb = sqrt_1mac;
+    a.step = step, a.times = times, a.times_next = times_next, a.sqrt_an = sqrt_alpha_next, a.cnoise = c_noise, a.sigma = sigma;
+    a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
+    a.mean_type = mean_type, a.b = b, a.inner = inner, a.S = num_steps, a.T = num_timesteps;
+    return launch_step<true, GIVEN_MASK, true>(a, stream);
 }
 
 extern "C" int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y, int32_t b, int64_t inner, dsc_stream_t stream) {

@@ -299,7 +299,7 @@ int dsc_q_sample_f32(const float* x0, const float* noise, const int64_t* t,
  *        (mean_type eps) ca[t]*x_t - cb[t]*model_out      ca=sqrt_recip_ac,  cb=sqrt_recipm1_ac
  *        (mean_type x0)  model_out
  *   clamp to [-1,1] if clip; mean = coef1[t]*x0 + coef2[t]*x_t; out = mean + (t != 0) * sigma[t] * noise
- * sigma[t] = exp(0.5 * posterior_log_variance_clipped[t]) is tabulated by the host. */
+ * sigma[t] = exp(0.5 * posterior_log_variance_clipped[t]) is tabulated by the host.  b > 65535: DSC_ERANGE, as for every step. */
 #define DSC_MEAN_EPS 0
 #define DSC_MEAN_X0  1
 #define DSC_MEAN_V   2
@@ -340,7 +340,7 @@ int dsc_postfilter_compact_f32(const float* samples, int32_t b, int32_t n, int32
                                int32_t keep_empty, float* packed, int32_t* counts, dsc_stream_t stream);
 
 /* Inpainting overwrite of p_sample_loop_complete (:462-466): rows [0,p) of every scene of x
- * (b, n, c) are replaced by q_sample(partial, t, noise) (partial/noise are (b, p, c)). */
+ * (b, n, c) are replaced by q_sample(partial, t, noise) (partial/noise are (b, p, c)).  b > 65535: DSC_ERANGE, as for the ragged form. */
 int dsc_complete_overwrite_f32(float* x, const float* partial, const float* noise, const int64_t* t,
                                const float* sqrt_ac, const float* sqrt_1mac,
                                int32_t b, int32_t n, int32_t p, int32_t c, int32_t num_timesteps, dsc_stream_t stream);

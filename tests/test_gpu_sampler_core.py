@@ -1,5 +1,6 @@
-"""GPU: what the eight captured loops share (sampler._LoopGraph and its two layers) and what the eight step kernels share (the device
-helpers of csrc/diffusion.hip), at the shapes where the shared code can go wrong and no per-feature test looks.
+"""GPU: what the eight captured loops share (sampler._LoopGraph and its two layers) and what the ten step entry points share (the
+step_kernel template of csrc/diffusion.hip and its device helpers), at the shapes where the shared code can go wrong and no per-feature
+test looks.
 
 * the capture path at its edge step counts: every loop at 1 and 2 steps -- with one step the step graph is never replayed (the strided
   loops have none), only the standalone overwrite and ``final`` run -- eager, then graph (capturing), then graph (cached) under one
@@ -192,6 +193,11 @@ def test_posterior_kernels_past_one_trip_of_the_grid_stride_loop(mean_type, N, C
         want = ops.p_sample(x, ops.cfg_combine(mo2, scale), noise, t, *post, *tail, x0_out=x0_want)
         got = ops.p_sample_cfg(x, mo2, scale, noise, t, *post, *tail, x_dup=dup, x0_out=x0_got)
         assert torch.equal(got, want) and torch.equal(dup, want) and torch.equal(x0_got, x0_want), (mean_type, clip)
+        # guided in-painting: cfg_combine, then p_sample_masked (tests/test_gpu_guided_inpaint.py)
+        dup = torch.empty_like(x)
+        want = ops.p_sample_masked(x, ops.cfg_combine(mo2, scale), noise, given, gnoise, mask, t, *post, sa, sb, *tail)
+        got = ops.p_sample_masked_cfg(x, mo2, scale, noise, given, gnoise, mask, t, *post, sa, sb, *tail, x_dup=dup)
+        assert torch.equal(got, want) and torch.equal(dup, want), (mean_type, clip, float((got - want).abs().max()))
 
 
 @pytest.mark.parametrize("N,C", KSHAPES)
@@ -231,11 +237,17 @@ def test_ddim_kernels_past_one_trip_of_the_grid_stride_loop(mean_type, N, C):
         want = ops.ddim_step(x, ops.cfg_combine(mo2, scale), noise, step, *narrow, x0_out=x0_want)
         got = ops.ddim_cfg_step(x, mo2, scale, noise, step, *narrow, x_dup=dup, x0_out=x0_got)
         assert torch.equal(got, want) and torch.equal(dup, want) and torch.equal(x0_got, x0_want), (mean_type, k)
+        # guided in-painting (tests/test_gpu_guided_inpaint.py)
+        dup = torch.empty_like(x)
+        want = ops.ddim_masked_step(x, ops.cfg_combine(mo2, scale), noise, given, gnoise, mask, step, *wide)
+        got = ops.ddim_masked_cfg_step(x, mo2, scale, noise, given, gnoise, mask, step, *wide, x_dup=dup)
+        assert torch.equal(got, want) and torch.equal(dup, want), (mean_type, k, float((got - want).abs().max()))
 
 
 def test_who_reads_the_noise_at_t_zero_and_on_the_last_pair():
-    """p_sample, p_sample_inpaint and p_sample_masked force sigma to 0 at t == 0 and still add 0 * noise: infinite noise gives NaN on
-    every free element; p_sample_cfg does not read it.  A given element reads neither.  On the last DDIM pair no kernel reads a noise."""
+    """p_sample, p_sample_inpaint, p_sample_masked and p_sample_masked_cfg force sigma to 0 at t == 0 and still add 0 * noise: infinite
+    noise gives NaN on every free element; p_sample_cfg does not read it.  A given element reads neither.  On the last DDIM pair no
+    kernel reads a noise."""
     from diffuscene_amd import ops
     N, C = KSHAPES[1]
     gd = _gdiff("v")
@@ -254,6 +266,8 @@ def test_who_reads_the_noise_at_t_zero_and_on_the_last_pair():
     got = ops.p_sample_cfg(x, mo2, scale, inf, t, *post, mt, True)
     m = ops.cfg_combine(mo2, scale)
     assert torch.isfinite(got).all() and torch.equal(got.cpu(), _host_posterior_mean(gd, x.cpu(), m.cpu(), t.cpu(), True))
+    got = ops.p_sample_masked_cfg(x, mo2, scale, inf, given, inf, mask, t, *post, sa, sb, mt, True)
+    assert torch.isnan(got[mask == 0]).all() and torch.equal(got[mask != 0], given[mask != 0])
     # the last pair: x_start, whatever the noises hold
     dtab = gd.ddim_tables(S_K, ETA_K, dev())
     wide, narrow = _step_args(gd, dtab), _ddim_args(gd, dtab)
@@ -266,5 +280,8 @@ def test_who_reads_the_noise_at_t_zero_and_on_the_last_pair():
     assert torch.isfinite(got).all() and torch.equal(got, torch.where(is_given, given, x_start))
     got = ops.ddim_masked_step(x, mo, inf, given, inf, mask, step, *wide)
     assert torch.isfinite(got).all() and torch.equal(got, torch.where(mask != 0, given, x_start))
+    x_start_g = _host_x0(gd, x.cpu(), m.cpu(), t_last, True).to(dev())
     got = ops.ddim_cfg_step(x, mo2, scale, inf, step, *narrow)
-    assert torch.isfinite(got).all() and torch.equal(got, _host_x0(gd, x.cpu(), m.cpu(), t_last, True).to(dev()))
+    assert torch.isfinite(got).all() and torch.equal(got, x_start_g)
+    got = ops.ddim_masked_cfg_step(x, mo2, scale, inf, given, inf, mask, step, *wide)
+    assert torch.isfinite(got).all() and torch.equal(got, torch.where(mask != 0, given, x_start_g))

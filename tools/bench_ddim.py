@@ -9,7 +9,7 @@
 * generate_layout_batched(256) at N = 80 (the metric shape), scenes per second, DDIM S = 50 against DDPM.
 Every variant has its own model (identical seeded weights): the graph cache keeps one live graph per model, so alternating variants
 on one model would time a capture per call.  Each variant is warmed up (capture) first, then the variants are timed in alternation,
-with a device synchronise around every call; the median is reported.  ``--kernel-db`` adds the ddim_step_kernel line of a rocprofv3
+with a device synchronise around every call; the median is reported.  ``--kernel-db`` adds the DDIM step kernel's line of a rocprofv3
 trace of ``--trace-only`` (warm-up, then one batched S = 50 call): achieved HBM bytes/s of the step (3 fp32 reads + 1 write per element)
 against the 8.0 TB/s peak of the MI355X."""
 import argparse
@@ -96,20 +96,23 @@ def batched(device, reps, S=50):
             "speedup": round(med[None] / med[S], 2)}
 
 
+# dsc_ddim_step_f32 launches step_kernel<STRIDED = true, GIVEN = none, GUIDED = false> (csrc/diffusion.hip); demangled or mangled name
+DDIM_STEP_KERNEL = "(name like '%step_kernel<true, 0, false>%' or name like '%step_kernelILb1ELi0ELb0E%')"
+
+
 def kernel_line(db, B=256, N=80, C=65):
     con = sqlite3.connect(db)
     cur = con.cursor()
-    r = cur.execute("select count(*), avg(end-start), min(end-start), max(end-start) from kernels where name like '%ddim_step_kernel%'"
-                    ).fetchone()
+    r = cur.execute("select count(*), avg(end-start), min(end-start), max(end-start) from kernels where " + DDIM_STEP_KERNEL).fetchone()
     if not r or not r[0]:
-        return {"error": "no ddim_step_kernel dispatch in %s" % db}
+        return {"error": "no step_kernel<true, 0, false> dispatch in %s" % db}
     n, avg_ns, mn, mx = r
-    full = cur.execute("select count(*), avg(end-start) from kernels where name like '%ddim_step_kernel%' and end-start > ?",
+    full = cur.execute("select count(*), avg(end-start) from kernels where " + DDIM_STEP_KERNEL + " and end-start > ?",
                        (0.5 * avg_ns,)).fetchone()
     elems = B * N * C
     bytes_step = 4 * elems * 4            # x_t, model output, noise read; x written
     tl = cur.execute("select min(start), max(end), sum(end-start), count(*) from kernels").fetchone()
-    return {"kernel": "ddim_step_kernel", "dispatches": n, "avg_us": round(avg_ns / 1e3, 2), "min_us": round(mn / 1e3, 2),
+    return {"kernel": "step_kernel<true, 0, false>", "dispatches": n, "avg_us": round(avg_ns / 1e3, 2), "min_us": round(mn / 1e3, 2),
             "max_us": round(mx / 1e3, 2), "shape": [B, N, C], "bytes_per_step": bytes_step,
             "achieved_TBps": round(bytes_step / (mn * 1e-9) / 1e12, 2), "achieved_TBps_avg": round(bytes_step / (avg_ns * 1e-9) / 1e12, 2),
             "hbm_peak_TBps": HBM_PEAK / 1e12, "fraction_of_peak_best": round(bytes_step / (mn * 1e-9) / HBM_PEAK, 3),
