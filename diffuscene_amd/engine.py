@@ -103,12 +103,8 @@ class Plan:
     # ---- step emitters -------------------------------------------------------------------------
     def gemm(self, a, w, out, bias=None, a2=None, residual=None, act_in=ACT_NONE, act_out=ACT_NONE, row_invariant=False):
         g = ops.make_gemm_args(a, w, out, bias, a2, residual, act_in, act_out, row_invariant=row_invariant)
-        lay = ops.planes_layout(g)                       # planes only for launches that will use them, in the layout their kernel reads
-        pl = self.eng.planes_of(w, lay) if lay >= 0 else None
-        if pl is not None:
-            ops.attach_planes(g, pl, layout=lay)
-        self.keep.append(_own((g, a, w, out, bias, a2, residual, pl)))
-        self.steps.append((_lib.fn("dsc_gemm_f32"), (C.byref(g),)))
+        pl = ops.planes_for(g, False, w, self.eng.planes_of)      # planes only for launches that will use them, in the layout their kernel reads
+        self.call("dsc_gemm_f32", C.byref(g), keep=(g, a, w, out, bias, a2, residual, pl))
         return out
 
     def gemm_batched(self, a, w, out, bias, batch, sa, sw, sy, sbias, act_out=ACT_NONE):
@@ -122,29 +118,25 @@ class Plan:
         # dense [batch n][K] matrix and the problem stride one block; anything else multiplies on the f32 kernel
         whole = (stacked.dim() == 2 and stacked.is_contiguous() and w.data_ptr() == stacked.data_ptr()
                  and stacked.shape[0] == batch * w.shape[0] and stacked.shape[1] == w.shape[1] and sw == w.shape[0] * w.shape[1])
-        lay = ops.planes_layout(g) if whole else -1
-        pl = self.eng.planes_of(stacked, lay) if lay >= 0 else None
-        if pl is not None:
-            ops.attach_planes(g, pl, layout=lay)
-        self.keep.append(_own((g, a, w, out, bias, pl)))
-        self.steps.append((_lib.fn("dsc_gemm_f32"), (C.byref(g),)))
+        pl = ops.planes_for(g, False, stacked, self.eng.planes_of) if whole else None
+        self.call("dsc_gemm_f32", C.byref(g), keep=(g, a, w, out, bias, pl))
         return out
 
     def gemm_gn(self, a, w, out, bias, gamma, beta, a2=None, ss=None, ss_mode=SS_NONE, residual=None):
         g = ops.make_gemm_args(a, w, out, bias, a2, residual, gamma=gamma, beta=beta, eps=1e-5,
                                tokens_per_scene=self.N, scale_shift=ss, ss_mode=ss_mode if ss is not None else SS_NONE,
                                ss_index=self.t_in if (ss is not None and ss_mode == SS_BY_INDEX) else None)
-        lay = ops.planes_layout(g, gn=True)
-        pl = self.eng.planes_of(w, lay) if lay >= 0 else None
-        if pl is not None:
-            ops.attach_planes(g, pl, gn=True, layout=lay)
-        self.keep.append(_own((g, a, w, out, bias, a2, residual, gamma, beta, ss, pl)))
-        self.steps.append((_lib.fn("dsc_gemm_gn_silu_f32"), (C.byref(g),)))
+        pl = ops.planes_for(g, True, w, self.eng.planes_of)
+        self.call("dsc_gemm_gn_silu_f32", C.byref(g), keep=(g, a, w, out, bias, a2, residual, gamma, beta, ss, pl))
         return out
 
     def call(self, name, *args, keep=()):
         self.keep.append(_own(keep))
         self.steps.append((_lib.fn(name), args))
+
+    def rec(self, rec):
+        """A launch record of ops (name, args, keep) as the next step."""
+        self.call(rec[0], *rec[1], keep=rec[2])
 
     def hoist(self, first):
         """Move the launches emitted since index ``first`` out of the per-step list (sampling plans: time_table)."""
@@ -172,10 +164,7 @@ class Plan:
                 _lib.check(rc, f.__name__)
 
     def layernorm(self, x, g, out, residual=None):
-        self.call("dsc_layernorm_f32", x.data_ptr(), x.stride(0), g.data_ptr(),
-                  residual.data_ptr() if residual is not None else None,
-                  residual.stride(0) if residual is not None else 0,
-                  out.data_ptr(), out.stride(0), x.shape[0], x.shape[1], 1e-5, keep=(x, g, out, residual))
+        self.rec(ops.layernorm_rec(x, g, out, residual))
         return out
 
     def out_proj_ln(self, a, conv, ln_gain, residual):
@@ -187,8 +176,7 @@ class Plan:
         if (M + 95) // 96 >= 160:
             g = ops.make_gemm_args(a, conv.weight, out, conv.bias, None, residual, gamma=ln_gain.view(-1), beta=ln_gain.view(-1),
                                    eps=1e-5)
-            self.keep.append(_own((g, a, conv.weight, out, conv.bias, residual, ln_gain)))
-            self.steps.append((_lib.fn("dsc_gemm_layernorm_f32"), (C.byref(g),)))
+            self.call("dsc_gemm_layernorm_f32", C.byref(g), keep=(g, a, conv.weight, out, conv.bias, residual, ln_gain))
             return out
         o = self.gemm(a, conv.weight, self.pool.get(M, D), conv.bias)
         self.layernorm(o, ln_gain, out, residual=residual)
@@ -232,8 +220,8 @@ class Plan:
         qkv = self.gemm(y, att.to_qkv.weight, self.pool.get(M, 3 * HID))
         self.pool.put(y)
         a = self.pool.get(M, HID)
-        self.call("dsc_linear_attention_f32", qkv.data_ptr(), 3 * HID, qkv.data_ptr() + 4 * HID, 3 * HID,
-                  qkv.data_ptr() + 8 * HID, 3 * HID, a.data_ptr(), HID, B, N, N, float(att.scale), keep=(qkv, a))
+        q, k, v = qkv.split(HID, dim=1)
+        self.rec(ops.linear_attention_rec(q, k, v, a, B, N, N, float(att.scale)))
         self.pool.put(qkv)
         out = self.out_proj_ln(a, att.to_out[0], att.to_out[1].g, x)
         self.pool.put(a)
@@ -249,8 +237,7 @@ class Plan:
         kv = self.gemm(self.cross_in, att.to_kv.weight, self.pool.get(B * L, 2 * HID))
         kv_is_invariant = self.hoist(first)             # sampling: computed once per loop, its buffer is never recycled
         a = self.pool.get(M, HID)
-        self.call("dsc_linear_attention_f32", q.data_ptr(), HID, kv.data_ptr(), 2 * HID, kv.data_ptr() + 4 * HID,
-                  2 * HID, a.data_ptr(), HID, B, N, L, float(att.scale), keep=(q, kv, a))
+        self.rec(ops.linear_attention_rec(q, kv[:, :HID], kv[:, HID:], a, B, N, L, float(att.scale)))
         self.pool.put(q)
         if not kv_is_invariant:
             self.pool.put(kv)
@@ -265,8 +252,8 @@ class Plan:
         qkv = self.gemm(y, att.to_qkv.weight, self.pool.get(M, 3 * HID))
         self.pool.put(y)
         a = self.pool.get(M, HID)
-        self.call("dsc_attention_f32", qkv.data_ptr(), 3 * HID, qkv.data_ptr() + 4 * HID, 3 * HID,
-                  qkv.data_ptr() + 8 * HID, 3 * HID, a.data_ptr(), HID, B, N, float(att.scale), keep=(qkv, a))
+        q, k, v = qkv.split(HID, dim=1)
+        self.rec(ops.attention_rec(q, k, v, a, B, N, float(att.scale)))
         self.pool.put(qkv)
         out = self.gemm(a, att.to_out.weight, self.pool.get(M, D), att.to_out.bias, residual=x)
         self.pool.put(a)
@@ -283,8 +270,7 @@ class Plan:
             self.ss_t = e.ss_table()
         else:
             temb = pool.get(B, D)
-            self.call("dsc_time_embedding_f32", self.t_in.data_ptr(), B, D, e.time_table.data_ptr(),
-                      e.time_table.shape[0], e.time_freq.data_ptr(), temb.data_ptr(), keep=(temb,))
+            self.rec(ops.time_embedding_rec(self.t_in, D, e.time_table, e.time_freq, temb))
             # row_invariant: ss_table() below builds the same rows with m = T for the captured loops -- a row must not depend on the number
             # of rows, so these three stay on the exact-f32 tile kernels at every B (the library wants no planes for them)
             t1 = self.gemm(temb, net.time_mlp[1].weight, pool.get(B, 4 * D), net.time_mlp[1].bias, act_out=ACT_GELU, row_invariant=True)
@@ -294,8 +280,7 @@ class Plan:
         if self.ctx_in is not None:
             first = len(self.steps)
             cact = pool.get(self.ctx_in.shape[0], self.ctx_in.shape[1])       # SiLU of ResnetBlock.mlp (:181-184), once
-            self.call("dsc_activation_f32", self.ctx_in.data_ptr(), cact.data_ptr(), self.ctx_in.numel(), ACT_SILU,
-                      keep=(cact,))
+            self.rec(ops.activation_rec(self.ctx_in, cact, ACT_SILU))
             self.ss_c = self.gemm(cact, e.c_pack_w, pool.get(self.ctx_in.shape[0], e.c_pack_w.shape[0]), e.c_pack_b)
             self.hoist(first)                         # sampling: the context never changes inside a reverse loop
         else:
@@ -308,14 +293,9 @@ class Plan:
             h1 = pool.get(M, H * D)
             # layer 1: tiny K on un-aligned column slices -- all heads in ONE launch (round 4: three launches of 22-40 us, each too
             # short to fill the chip; bit-identical results)
-            items = (_lib.SmallKItem * H)()
-            for i, (seq, c0, k) in enumerate(e.enc_heads):
-                xs = self.x_in[:, c0:c0 + k]
-                items[i].x, items[i].ldx, items[i].k_in = xs.data_ptr(), self.x_in.stride(0), k
-                items[i].w, items[i].ldw, items[i].bias = seq[0].weight.data_ptr(), k, seq[0].bias.data_ptr()
-                items[i].y, items[i].ldy = h1.data_ptr() + 4 * i * D, H * D
-            self.call("dsc_linear_smallk_grouped_f32", items, H, M, D, ACT_GELU,
-                      keep=(items, h1, [(seq[0].weight, seq[0].bias) for seq, _, _ in e.enc_heads]))
+            self.rec(ops.linear_smallk_grouped_rec([self.x_in[:, c0:c0 + k] for _, c0, k in e.enc_heads],
+                                                   [seq[0].weight for seq, _, _ in e.enc_heads],
+                                                   [seq[0].bias for seq, _, _ in e.enc_heads], list(h1.split(D, dim=1)), ACT_GELU))
             h2 = pool.get(M, H * 2 * D)
             self.gemm_batched(h1[:, :D], e.enc_w2[:2 * D], h2[:, :2 * D], e.enc_b2[:2 * D], H, D, 2 * D * D, 2 * D, 2 * D,
                               act_out=ACT_GELU)
@@ -326,10 +306,7 @@ class Plan:
             pool.put(emb)
         else:
             x = pool.get(M, D)
-            k = net.channels
-            self.call("dsc_linear_smallk_f32", self.x_in.data_ptr(), self.x_in.stride(0), k,
-                      net.init_conv.weight.data_ptr(), k, net.init_conv.bias.data_ptr(), x.data_ptr(), D, M, D,
-                      ACT_NONE, keep=(x, net.init_conv.weight, net.init_conv.bias))
+            self.rec(ops.linear_smallk_rec(self.x_in, net.init_conv.weight, net.init_conv.bias, x))
         r = x           # `r = x.clone()` of the reference: the buffer is simply never recycled
         skips = []
         text = net.text_condition
@@ -402,13 +379,11 @@ class Plan:
             P = e.dec_pad
             pad = pool.get(M, Hd * P)
             self.gemm_batched(d2[:, :D], e.dec_w3p[:P], pad[:, :P], e.dec_b3p[:P], Hd, D, P * D, P, P)
-            spans = (_lib.ColSpan * Hd)()
-            col = 0
+            spans, col = [], 0
             for i, (seq, width) in enumerate(e.dec_heads):
-                spans[i].src_col, spans[i].dst_col, spans[i].width = i * P, col, width
+                spans.append((i * P, col, width))
                 col += width
-            self.call("dsc_gather_columns_f32", self.out.data_ptr(), self.out.stride(0), pad.data_ptr(), pad.stride(0), M, spans, Hd,
-                      keep=(spans, pad))
+            self.rec(ops.gather_columns_rec(self.out, pad, spans))
             pool.put(pad)
             pool.put(d2)
         else:

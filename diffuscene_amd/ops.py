@@ -26,6 +26,15 @@ def _dev(t, name="tensor", dtype=torch.float32):
     return t
 
 
+def issue(rec, stream=None):
+    """Run one launch record on ``stream`` (default: the current torch stream).  A record is what every ``*_rec`` function below returns:
+    (entry point name, its arguments without the trailing stream, keep) -- ``keep`` lists everything a raw pointer among the arguments
+    refers to (tensors, ctypes arrays and structs).  The eager wrappers issue their record at once; launch plans (engine.Plan,
+    train_plan.HipBackend) store it and own ``keep``.  A ``*_rec`` function checks its operands and never allocates."""
+    name, args, _ = rec
+    _lib.check(_lib.fn(name)(*args, stream if stream is not None else stream_ptr()), name)
+
+
 def _mat(t, name):
     """2-D row-major view with contiguous columns; returns (ptr, ld)."""
     _dev(t, name)
@@ -143,6 +152,17 @@ def attach_planes(g, planes, gn=False, layout=None):
     return g
 
 
+def planes_for(g, gn, w, planes_of):
+    """The planes decision of one GEMM launch, on its finished dsc_gemm_args: ask the library which layout the launch wants, fetch the
+    planes of weight operand ``w`` from the caller's cache -- ``planes_of(w, layout)`` -- and attach them in that layout.  Returns the
+    planes, or None when the launch stays on the exact-f32 kernel or the cache has none for it."""
+    lay = planes_layout(g, gn)
+    pl = planes_of(w, lay) if lay >= 0 else None
+    if pl is not None:
+        attach_planes(g, pl, gn, layout=lay)
+    return pl
+
+
 def planes_wanted(n, k):
     """Shapes the split-bf16 GEMM path covers (gemm_split.hip): callers skip the plane copy for everything else."""
     return n % 128 == 0 and k % 32 == 0 and 6 * n * k < 0x7fffffff
@@ -156,7 +176,6 @@ def split_planes(items, stream=None):
         tr = int(tr)                       # bit 0: planes of w^T; bit 1 (2): fragment-major output (PLANES_FRAGMENT)
         frag, tr = tr & 2, tr & 1
         w2 = as2d(_dev(w, "w"))
-        ptr, ldw = _mat(w2, "w")
         r, c = w2.shape
         shape = (3, c, r) if tr else (3, r, c)
         if planes is None:
@@ -166,15 +185,20 @@ def split_planes(items, stream=None):
         planes._dsc_layout = PLANES_FRAGMENT if frag else PLANES_ROWMAJOR
         planes._dsc_fragment = None        # attach_planes' converted copy: the kernel writes through a raw pointer, planes._version does not move
         out.append(planes)
-        batch.append((ptr, ldw, r, c, planes.data_ptr(), (1 if tr else 0) | frag, w2, planes))
+        batch.append((w2, planes, tr | frag))
     for i in range(0, len(batch), _lib.WS_MAX):
-        part = batch[i:i + _lib.WS_MAX]
-        arr = (SplitItem * len(part))()
-        for j, (ptr, ldw, r, c, pp, tr, _, _) in enumerate(part):
-            arr[j].w, arr[j].ldw, arr[j].rows, arr[j].cols, arr[j].planes, arr[j].transpose = ptr, ldw, r, c, pp, tr
-        _lib.check(_lib.fn("dsc_split_bf16x3_f32")(arr, len(part), stream if stream is not None else stream_ptr()),
-                   "dsc_split_bf16x3_f32")
+        issue(split_rec(batch[i:i + _lib.WS_MAX]), stream)
     return out
+
+
+def split_rec(ents):
+    """ents: <= DSC_WS_MAX of (w2d, planes, flags): the planes of w2d -- of its transpose with bit 0 of ``flags`` --, fragment-major with bit 1."""
+    arr = (SplitItem * len(ents))()
+    for j, (w, planes, flags) in enumerate(ents):
+        arr[j].w, arr[j].ldw = _mat(w, "w")
+        arr[j].rows, arr[j].cols = w.shape
+        arr[j].planes, arr[j].transpose = planes.data_ptr(), flags
+    return "dsc_split_bf16x3_f32", (arr, len(ents)), (arr, ents)
 
 
 def gemm_uses_split(g, gn=False):
@@ -213,30 +237,38 @@ def gemm_gn_silu(a, w_std, bias, gamma, beta, tokens_per_scene, a2=None, scale_s
     return out
 
 
+def _mats(*named):
+    """The (ptr, ld, ptr, ld, ...) run of (tensor, name) pairs; an absent (None) optional operand gives (None, 0)."""
+    run = ()
+    for t, name in named:
+        run += _mat(t, name) if t is not None else (None, 0)
+    return run
+
+
+def linear_smallk_rec(x, w, bias, out, act_out=ACT_NONE):
+    w2 = as2d(w)
+    xp, ldx, wp, ldw, yp, ldy = _mats((x, "x"), (w2, "w"), (out, "y"))
+    return ("dsc_linear_smallk_f32", (xp, ldx, x.shape[1], wp, ldw, _opt(bias), yp, ldy, x.shape[0], w2.shape[0], act_out),
+            (x, w, bias, out))
+
+
 def linear_smallk(x, w, bias, act_out=ACT_NONE, out=None):
     """x may be a column slice of a wider row-major tensor (arbitrary alignment)."""
-    xp, ldx = _mat(x, "x")
-    w2 = as2d(w)
-    wp, ldw = _mat(w2, "w")
     if out is None:
-        out = torch.empty((x.shape[0], w2.shape[0]), device=x.device, dtype=torch.float32)
-    yp, ldy = _mat(out, "y")
-    _lib.check(_lib.fn("dsc_linear_smallk_f32")(xp, ldx, x.shape[1], wp, ldw,
-                                                bias.data_ptr() if bias is not None else None,
-                                                yp, ldy, x.shape[0], w2.shape[0], act_out, stream_ptr()),
-               "dsc_linear_smallk_f32")
+        out = torch.empty((x.shape[0], as2d(w).shape[0]), device=x.device, dtype=torch.float32)
+    issue(linear_smallk_rec(x, w, bias, out, act_out))
     return out
 
 
-def make_ws_items(pairs):
-    """pairs: list of (w2d, out2d) contiguous tensors -> ctypes array."""
+def weight_standardize_rec(pairs, eps=1e-5):
+    """pairs: <= DSC_WS_MAX of (w, out), contiguous matrices (or (out, in, 1) conv weights)."""
     arr = (WsItem * len(pairs))()
     for i, (w, o) in enumerate(pairs):
         w2, o2 = as2d(_dev(w)), as2d(_dev(o))
         if not (w2.is_contiguous() and o2.is_contiguous()):
             raise RuntimeError("weight_standardize needs contiguous matrices")
         arr[i].w, arr[i].out, arr[i].rows, arr[i].cols = w2.data_ptr(), o2.data_ptr(), w2.shape[0], w2.shape[1]
-    return arr
+    return "dsc_weight_standardize_f32", (arr, len(pairs), eps), (arr, pairs)
 
 
 def weight_standardize(weights, outs=None, eps=1e-5):
@@ -244,63 +276,59 @@ def weight_standardize(weights, outs=None, eps=1e-5):
     if outs is None:
         outs = [torch.empty_like(as2d(w)) for w in weights]
     for i in range(0, len(weights), _lib.WS_MAX):
-        chunk = list(zip(weights[i:i + _lib.WS_MAX], outs[i:i + _lib.WS_MAX]))
-        arr = make_ws_items(chunk)
-        _lib.check(_lib.fn("dsc_weight_standardize_f32")(arr, len(chunk), eps, stream_ptr()),
-                   "dsc_weight_standardize_f32")
+        issue(weight_standardize_rec(list(zip(weights[i:i + _lib.WS_MAX], outs[i:i + _lib.WS_MAX])), eps))
     return outs
 
 
+def layernorm_rec(x, g, out, residual=None, eps=1e-5):
+    xp, ldx, rp, ldr, yp, ldy = _mats((x, "x"), (residual, "residual"), (out, "y"))
+    return "dsc_layernorm_f32", (xp, ldx, _dev(g).data_ptr(), rp, ldr, yp, ldy, x.shape[0], x.shape[1], eps), (x, g, out, residual)
+
+
 def layernorm(x, g, residual=None, eps=1e-5, out=None):
-    xp, ldx = _mat(x, "x")
     if out is None:
         out = torch.empty((x.shape[0], x.shape[1]), device=x.device, dtype=torch.float32)
-    yp, ldy = _mat(out, "y")
-    rp, ldr = _mat(residual, "residual") if residual is not None else (None, 0)
-    _lib.check(_lib.fn("dsc_layernorm_f32")(xp, ldx, _dev(g).data_ptr(), rp, ldr, yp, ldy, x.shape[0], x.shape[1],
-                                            eps, stream_ptr()), "dsc_layernorm_f32")
+    issue(layernorm_rec(x, g, out, residual, eps))
     return out
+
+
+def linear_attention_rec(q, k, v, out, scenes, nq, nk, scale):
+    """q, k, v may be column blocks of one wider projection buffer."""
+    return ("dsc_linear_attention_f32", _mats((q, "q"), (k, "k"), (v, "v"), (out, "out")) + (scenes, nq, nk, scale), (q, k, v, out))
 
 
 def linear_attention(q, k, v, scenes, nq, nk, scale, out=None):
-    qp, ldq = _mat(q, "q")
-    kp, ldk = _mat(k, "k")
-    vp, ldv = _mat(v, "v")
     if out is None:
         out = torch.empty((q.shape[0], 128), device=q.device, dtype=torch.float32)
-    op, ldo = _mat(out, "out")
-    _lib.check(_lib.fn("dsc_linear_attention_f32")(qp, ldq, kp, ldk, vp, ldv, op, ldo, scenes, nq, nk, scale,
-                                                   stream_ptr()), "dsc_linear_attention_f32")
+    issue(linear_attention_rec(q, k, v, out, scenes, nq, nk, scale))
     return out
+
+
+def attention_rec(q, k, v, out, scenes, n, scale):
+    return "dsc_attention_f32", _mats((q, "q"), (k, "k"), (v, "v"), (out, "out")) + (scenes, n, scale), (q, k, v, out)
 
 
 def attention(q, k, v, scenes, n, scale, out=None):
-    qp, ldq = _mat(q, "q")
-    kp, ldk = _mat(k, "k")
-    vp, ldv = _mat(v, "v")
     if out is None:
         out = torch.empty((q.shape[0], 128), device=q.device, dtype=torch.float32)
-    op, ldo = _mat(out, "out")
-    _lib.check(_lib.fn("dsc_attention_f32")(qp, ldq, kp, ldk, vp, ldv, op, ldo, scenes, n, scale, stream_ptr()),
-               "dsc_attention_f32")
+    issue(attention_rec(q, k, v, out, scenes, n, scale))
     return out
+
+
+def time_embedding_rec(t, dim, table, freq, out):
+    _dev(t, "t", torch.int64)
+    return ("dsc_time_embedding_f32", (t.data_ptr(), t.shape[0], dim, _opt(table), table.shape[0] if table is not None else 0,
+                                       _dev(freq).data_ptr(), out.data_ptr()), (t, table, freq, out))
 
 
 def time_embedding(t, dim, table, freq, out=None):
-    _dev(t, "t", torch.int64)
     if out is None:
         out = torch.empty((t.shape[0], dim), device=t.device, dtype=torch.float32)
-    _lib.check(_lib.fn("dsc_time_embedding_f32")(t.data_ptr(), t.shape[0], dim,
-                                                 table.data_ptr() if table is not None else None,
-                                                 table.shape[0] if table is not None else 0,
-                                                 _dev(freq).data_ptr(), out.data_ptr(), stream_ptr()),
-               "dsc_time_embedding_f32")
+    issue(time_embedding_rec(t, dim, table, freq, out))
     return out
 
 
-def linear_smallk_grouped(xs, ws, biases, outs, act_out=ACT_NONE):
-    """``len(xs)`` <= 4 small-K linears of one output width in ONE launch (dsc_linear_smallk_grouped_f32): xs[i] [m, k_i] may be column
-    slices of a wider tensor, outs[i] [m, n] column blocks of a wider buffer."""
+def linear_smallk_grouped_rec(xs, ws, biases, outs, act_out=ACT_NONE):
     n_items = len(xs)
     items = (_lib.SmallKItem * n_items)()
     m, n = outs[0].shape
@@ -309,33 +337,44 @@ def linear_smallk_grouped(xs, ws, biases, outs, act_out=ACT_NONE):
         items[i].x, items[i].ldx = _mat(xs[i], "x")
         items[i].k_in = xs[i].shape[1]
         items[i].w, items[i].ldw = _mat(w2, "w")
-        items[i].bias = biases[i].data_ptr() if biases[i] is not None else None
+        items[i].bias = _opt(biases[i])
         items[i].y, items[i].ldy = _mat(outs[i], "y")
         if tuple(outs[i].shape) != (m, n) or w2.shape[0] != n or xs[i].shape[0] != m:
             raise RuntimeError("linear_smallk_grouped: every head must produce the same [m, n] block")
-    _lib.check(_lib.fn("dsc_linear_smallk_grouped_f32")(items, n_items, m, n, act_out, stream_ptr()), "dsc_linear_smallk_grouped_f32")
+    return "dsc_linear_smallk_grouped_f32", (items, n_items, m, n, act_out), (items, xs, ws, biases, outs)
+
+
+def linear_smallk_grouped(xs, ws, biases, outs, act_out=ACT_NONE):
+    """``len(xs)`` <= 4 small-K linears of one output width in ONE launch (dsc_linear_smallk_grouped_f32): xs[i] [m, k_i] may be column
+    slices of a wider tensor, outs[i] [m, n] column blocks of a wider buffer."""
+    issue(linear_smallk_grouped_rec(xs, ws, biases, outs, act_out))
     return outs
+
+
+def gather_columns_rec(dst, src, spans):
+    arr = (_lib.ColSpan * len(spans))()
+    for i, (sc, dc, w) in enumerate(spans):
+        arr[i].src_col, arr[i].dst_col, arr[i].width = sc, dc, w
+    return "dsc_gather_columns_f32", _mats((dst, "dst"), (src, "src")) + (dst.shape[0], arr, len(spans)), (arr, dst, src)
 
 
 def gather_columns(dst, src, spans):
     """dst[:, d:d+w] = src[:, s:s+w] for (s, d, w) in spans (<= 4), one launch."""
-    arr = (_lib.ColSpan * len(spans))()
-    for i, (sc, dc, w) in enumerate(spans):
-        arr[i].src_col, arr[i].dst_col, arr[i].width = sc, dc, w
-    dp, ldd = _mat(dst, "dst")
-    sp, lds = _mat(src, "src")
-    _lib.check(_lib.fn("dsc_gather_columns_f32")(dp, ldd, sp, lds, dst.shape[0], arr, len(spans), stream_ptr()), "dsc_gather_columns_f32")
+    issue(gather_columns_rec(dst, src, spans))
     return dst
 
 
-def activation(x, act, out=None):
+def activation_rec(x, out, act):
     _dev(x)
-    if not x.is_contiguous():
+    if not (x.is_contiguous() and out.is_contiguous()):
         raise RuntimeError("activation needs a contiguous tensor")
+    return "dsc_activation_f32", (x.data_ptr(), out.data_ptr(), x.numel(), act), (x, out)
+
+
+def activation(x, act, out=None):
     if out is None:
         out = torch.empty_like(x)
-    _lib.check(_lib.fn("dsc_activation_f32")(x.data_ptr(), out.data_ptr(), x.numel(), act, stream_ptr()),
-               "dsc_activation_f32")
+    issue(activation_rec(x, out, act))
     return out
 
 
@@ -395,14 +434,17 @@ def _out_like(what, x_t, out, *operands):
     return out
 
 
-def q_sample(x0, noise, t, sqrt_ac, sqrt_1mac, want_v=False):
+def q_sample_rec(x0, noise, t, sqrt_ac, sqrt_1mac, xt, v=None):
     _c(x0, "x0"); _c(noise, "noise"); _dev(t, "t", torch.int64)
+    b = x0.shape[0]
+    return ("dsc_q_sample_f32", (x0.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(), sqrt_1mac.data_ptr(), xt.data_ptr(),
+                                 _opt(v), b, x0.numel() // b, _table_rows(sqrt_ac, sqrt_1mac)), (x0, noise, t, sqrt_ac, sqrt_1mac, xt, v))
+
+
+def q_sample(x0, noise, t, sqrt_ac, sqrt_1mac, want_v=False):
     xt = torch.empty_like(x0)
     v = torch.empty_like(x0) if want_v else None
-    b = x0.shape[0]
-    _lib.check(_lib.fn("dsc_q_sample_f32")(x0.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(),
-                                           sqrt_1mac.data_ptr(), xt.data_ptr(), v.data_ptr() if want_v else None,
-                                           b, x0.numel() // b, _table_rows(sqrt_ac, sqrt_1mac), stream_ptr()), "dsc_q_sample_f32")
+    issue(q_sample_rec(x0, noise, t, sqrt_ac, sqrt_1mac, xt, v))
     return (xt, v) if want_v else xt
 
 
@@ -859,155 +901,227 @@ def scratch(device, floats):
     return t
 
 
+def transpose_rec(w, out):
+    if tuple(out.shape) != (w.shape[1], w.shape[0]):
+        raise RuntimeError("transpose: out must be %s, got %s" % ((w.shape[1], w.shape[0]), tuple(out.shape)))
+    return "dsc_transpose_f32", _mats((w, "w"), (out, "out")) + tuple(w.shape), (w, out)
+
+
 def transpose(w, out=None, ldo=None):
-    wp, ldi = _mat(w, "w")
-    rows, cols = w.shape
     if out is None:
-        out = torch.empty((cols, rows), device=w.device, dtype=torch.float32)
-    op, ld = _mat(out, "out")
-    _lib.check(_lib.fn("dsc_transpose_f32")(wp, ldi, op, ld, rows, cols, stream_ptr()), "dsc_transpose_f32")
+        out = torch.empty((w.shape[1], w.shape[0]), device=w.device, dtype=torch.float32)
+    issue(transpose_rec(w, out))
     return out
+
+
+def transpose_batched_rec(pairs):
+    """pairs: <= DSC_WS_MAX of (w (rows, cols), out (cols, rows)), both contiguous."""
+    arr = (WsItem * len(pairs))()
+    for j, (m, o) in enumerate(pairs):
+        if not (_dev(m).is_contiguous() and m.dim() == 2 and _dev(o).is_contiguous()):
+            raise RuntimeError("transpose_many needs contiguous 2-D matrices")
+        arr[j].w, arr[j].out = m.data_ptr(), o.data_ptr()
+        arr[j].rows, arr[j].cols = m.shape
+    return "dsc_transpose_batched_f32", (arr, len(pairs)), (arr, pairs)
 
 
 def transpose_many(mats):
     """[w_i (rows_i, cols_i)] -> [w_i^T], one launch per DSC_WS_MAX matrices."""
     outs = [torch.empty((m.shape[1], m.shape[0]), device=m.device, dtype=torch.float32) for m in mats]
     for i in range(0, len(mats), _lib.WS_MAX):
-        ms, os_ = mats[i:i + _lib.WS_MAX], outs[i:i + _lib.WS_MAX]
-        arr = (_lib.WsItem * len(ms))()
-        for j, (m, o) in enumerate(zip(ms, os_)):
-            if not (_dev(m).is_contiguous() and m.dim() == 2):
-                raise RuntimeError("transpose_many needs contiguous 2-D matrices")
-            arr[j].w, arr[j].out = m.data_ptr(), o.data_ptr()
-            arr[j].rows, arr[j].cols = m.shape
-        _lib.check(_lib.fn("dsc_transpose_batched_f32")(arr, len(ms), stream_ptr()), "dsc_transpose_batched_f32")
+        issue(transpose_batched_rec(list(zip(mats[i:i + _lib.WS_MAX], outs[i:i + _lib.WS_MAX]))))
     return outs
+
+
+def copy2d_rec(dst, src):
+    """dst = src, row-major 2-D views of one shape (arbitrary alignment)."""
+    return "dsc_copy2d_f32", _mats((dst, "dst"), (src, "src")) + tuple(dst.shape), (dst, src)
+
+
+def add2d_rec(dst, src):
+    """dst += src."""
+    return "dsc_add2d_f32", _mats((dst, "dst"), (src, "src")) + tuple(dst.shape), (dst, src)
+
+
+def tn_operands(a, dy, out, a2=None, kvalid=None, what="gemm_tn"):
+    """The operand run (a1, lda1, k1, a2, lda2, k2, dy, ldd, out, ldo) and (m, n, kvalid) of one weight-gradient product
+    out[n][k] = sum_m dy[m][n] * [a|a2][m][k], after the shape and alignment checks dsc_gemm_tn_f32 makes on the host -- made here
+    because the grouped entry points see only a device table of these."""
+    ap, lda, a2p, lda2, dp, ldd, op, ldo = _mats((a, "a"), (a2, "a2"), (dy, "dy"), (out, "out"))
+    k1, k2 = a.shape[1], (a2.shape[1] if a2 is not None else 0)
+    m, n = dy.shape
+    kv = (k1 + k2) if kvalid is None else kvalid
+    if (k1 & 3) or (k2 & 3) or (n & 3) or (k2 > 0 and k1 % 128) or not (1 <= kv <= k1 + k2):
+        raise RuntimeError("%s: bad shape m=%d n=%d k1=%d k2=%d kvalid=%d" % (what, m, n, k1, k2, kv))
+    if (ap % 16) or (lda & 3) or (dp % 16) or (ldd & 3) or (k2 and ((a2p % 16) or (lda2 & 3))):
+        raise RuntimeError("%s: operands must be 16-byte aligned with row strides multiple of 4" % what)
+    if a.shape[0] != m or (a2 is not None and a2.shape[0] != m) or tuple(out.shape) != (n, kv):
+        raise RuntimeError("%s: shape mismatch" % what)
+    return (ap, lda, k1, a2p, lda2, k2, dp, ldd, op, ldo), (m, n, kv)
+
+
+def gemm_tn_rec(a, dy, out, a2, kvalid, dbias, ws_ptr, ws_floats):
+    """``ws_ptr`` / ``ws_floats``: the caller's workspace of at least dsc_gemm_tn_workspace_floats(m, n, kvalid) floats (None, 0 when that is 0)."""
+    run, (m, n, kv) = tn_operands(a, dy, out, a2, kvalid)
+    return "dsc_gemm_tn_f32", run + (_opt(dbias), m, n, kv, ws_ptr, ws_floats), (a, dy, out, a2, dbias)
 
 
 def gemm_tn(a, dy, a2=None, kvalid=None, out=None, want_bias=False):
     """out[n][k] = sum_m dy[m][n] * [a|a2][m][k]  (+ column sums of dy when want_bias) -> out or (out, dbias)"""
-    ap, lda = _mat(a, "a")
-    dp, ldd = _mat(dy, "dy")
-    k1 = a.shape[1]
-    a2p, lda2, k2 = (None, 0, 0)
-    if a2 is not None:
-        a2p, lda2 = _mat(a2, "a2")
-        k2 = a2.shape[1]
-    K = k1 + k2
-    kv = K if kvalid is None else kvalid
     m, n = dy.shape
+    kv = (a.shape[1] + (a2.shape[1] if a2 is not None else 0)) if kvalid is None else kvalid
     if out is None:
         out = torch.empty((n, kv), device=a.device, dtype=torch.float32)
-    op, ldo = _mat(out, "out")
     wsf = _lib.fn("dsc_gemm_tn_workspace_floats")(m, n, kv)
     ws = scratch(a.device, wsf) if wsf else None
     db = torch.empty((n,), device=a.device, dtype=torch.float32) if want_bias else None
-    _lib.check(_lib.fn("dsc_gemm_tn_f32")(ap, lda, k1, a2p, lda2, k2, dp, ldd, op, ldo,
-                                          db.data_ptr() if want_bias else None, m, n, kv,
-                                          ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                          stream_ptr()), "dsc_gemm_tn_f32")
+    issue(gemm_tn_rec(a, dy, out, a2, kvalid, db, _opt(ws), ws.numel() if ws is not None else 0))
     return (out, db) if want_bias else out
 
 
-def colsum(x, out=None):
+def colsum_rec(x, out, ws_ptr, ws_floats):
+    """out[n] = column sums of x [m, n]; the workspace holds at least 64 n floats."""
     xp, ldx = _mat(x, "x")
     m, n = x.shape
+    return "dsc_colsum_f32", (xp, ldx, m, n, out.data_ptr(), ws_ptr, ws_floats), (x, out)
+
+
+def colsum(x, out=None):
     if out is None:
-        out = torch.empty((n,), device=x.device, dtype=torch.float32)
-    ws = scratch(x.device, 64 * n)
-    _lib.check(_lib.fn("dsc_colsum_f32")(xp, ldx, m, n, out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()),
-               "dsc_colsum_f32")
+        out = torch.empty((x.shape[1],), device=x.device, dtype=torch.float32)
+    ws = scratch(x.device, 64 * x.shape[1])
+    issue(colsum_rec(x, out, ws.data_ptr(), ws.numel()))
     return out
+
+
+def device_table(arr, device):
+    """A ctypes array of structs as a uint8 device tensor (the grouped entry points read their items from device memory)."""
+    import numpy as np
+    return torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(device)
+
+
+def colsum_grouped_rec(pairs, device):
+    """pairs: [(x [m, n] with contiguous rows, out [n] contiguous)] -> ONE launch over a device table of them."""
+    arr = (_lib.ColsumItem * len(pairs))()
+    for i, (x, out) in enumerate(pairs):
+        if not (out.is_contiguous() and out.numel() == x.shape[1]):
+            raise RuntimeError("colsum_grouped: out must be a contiguous (%d,) tensor" % x.shape[1])
+        arr[i].x, arr[i].ldx = _mat(x, "x")
+        arr[i].m, arr[i].n, arr[i].out = x.shape[0], x.shape[1], out.data_ptr()
+    table = device_table(arr, device)
+    return "dsc_colsum_grouped_f32", (table.data_ptr(), len(pairs), max(x.shape[1] for x, _ in pairs)), (table, pairs)
+
+
+def gn_silu_bwd_rec(z, dy, gamma, beta, ss, ss_mode, dz, part, order, dss, scenes, n_tok, eps=1e-5):
+    """``part`` [scenes, 3 C]: the per-scene partial sums, three blocks of C columns; ``order`` = the block index of (dgamma, dbeta,
+    dbias) in a row.  ``ss`` None: no scale / shift."""
+    zp, ldz, dp, ldy, sp, ld_ss, dzp, lddz, dsp, ld_dss = _mats((z, "z"), (dy, "dy"), (ss, "ss"), (dz, "dz"), (dss, "dss"))
+    Cc = z.shape[1]
+    pg, pb, pB = (_mat(part, "part")[0] + 4 * Cc * o for o in order)
+    return ("dsc_gn_silu_bwd_f32", (zp, ldz, dp, ldy, _dev(gamma).data_ptr(), _dev(beta).data_ptr(), sp, ld_ss,
+                                    ss_mode if sp else SS_NONE, dzp, lddz, pg, pb, pB, part.stride(0), dsp, ld_dss, scenes, n_tok,
+                                    Cc, eps), (z, dy, gamma, beta, ss, dz, part, dss))
 
 
 def gn_silu_bwd(z, dy, gamma, beta, ss, ss_mode, scenes, n_tok, eps=1e-5):
     """-> dz [M,512], (dgamma, dbeta, dbias) [512] each, dss (per-scene [B,1024] | per-token [M,1024] | None)"""
-    zp, ldz = _mat(z, "z")
-    dp, ldy = _mat(dy, "dy")
     M, Cc = z.shape
     dz = torch.empty((M, Cc), device=z.device, dtype=torch.float32)
     part = torch.empty((scenes, 3 * Cc), device=z.device, dtype=torch.float32)     # [dgamma | dbeta | dbias] per scene
     dss = None
-    sp, ld_ss, ld_dss = None, 0, 0
     if ss is not None and ss_mode != SS_NONE:
-        sp, ld_ss = _mat(ss, "ss")
         dss = torch.empty((scenes if ss_mode == SS_PER_SCENE else M, 2 * Cc), device=z.device, dtype=torch.float32)
-        ld_dss = 2 * Cc
-    _lib.check(_lib.fn("dsc_gn_silu_bwd_f32")(zp, ldz, dp, ldy, _dev(gamma).data_ptr(), _dev(beta).data_ptr(), sp, ld_ss,
-                                              ss_mode if sp else SS_NONE, dz.data_ptr(), Cc, part.data_ptr(),
-                                              part.data_ptr() + 4 * Cc, part.data_ptr() + 8 * Cc, 3 * Cc,
-                                              dss.data_ptr() if dss is not None else None, ld_dss, scenes, n_tok, Cc,
-                                              eps, stream_ptr()), "dsc_gn_silu_bwd_f32")
+    issue(gn_silu_bwd_rec(z, dy, gamma, beta, ss if dss is not None else None, ss_mode, dz, part, (0, 1, 2), dss, scenes, n_tok, eps))
     red = colsum(part)                  # one column sum over the scenes for the three per-channel gradients
     return dz, red[:Cc], red[Cc:2 * Cc], red[2 * Cc:], dss
+
+
+def weight_standardize_bwd_rec(triples, eps=1e-5):
+    """triples: <= DSC_WS_MAX of (w, dw_std, dw), contiguous matrices (w, dw may be (out, in, 1) conv weights)."""
+    arr = (_lib.WsBwdItem * len(triples))()
+    for j, (w, g, o) in enumerate(triples):
+        w2, g2, o2 = as2d(_dev(w)), _dev(g), as2d(_dev(o))
+        if not (w2.is_contiguous() and g2.is_contiguous() and o2.is_contiguous()):
+            raise RuntimeError("weight_standardize_bwd needs contiguous matrices")
+        arr[j].w, arr[j].dw_std, arr[j].dw = w2.data_ptr(), g2.data_ptr(), o2.data_ptr()
+        arr[j].rows, arr[j].cols = w2.shape
+    return "dsc_weight_standardize_bwd_f32", (arr, len(triples), eps), (arr, triples)
 
 
 def weight_standardize_bwd(weights, dw_stds, eps=1e-5):
     outs = [torch.empty_like(as2d(w)) for w in weights]
     for i in range(0, len(weights), _lib.WS_MAX):
-        ws, gs, os_ = weights[i:i + _lib.WS_MAX], dw_stds[i:i + _lib.WS_MAX], outs[i:i + _lib.WS_MAX]
-        arr = (_lib.WsBwdItem * len(ws))()
-        for j, (w, g, o) in enumerate(zip(ws, gs, os_)):
-            w2, g2 = as2d(_dev(w)), _dev(g)
-            if not (w2.is_contiguous() and g2.is_contiguous()):
-                raise RuntimeError("weight_standardize_bwd needs contiguous matrices")
-            arr[j].w, arr[j].dw_std, arr[j].dw = w2.data_ptr(), g2.data_ptr(), o.data_ptr()
-            arr[j].rows, arr[j].cols = w2.shape
-        _lib.check(_lib.fn("dsc_weight_standardize_bwd_f32")(arr, len(ws), eps, stream_ptr()),
-                   "dsc_weight_standardize_bwd_f32")
+        s = slice(i, i + _lib.WS_MAX)
+        issue(weight_standardize_bwd_rec(list(zip(weights[s], dw_stds[s], outs[s])), eps))
     return outs
 
 
+def layernorm_bwd_rec(x, g, dy, dx, dg_part, addend=None, eps=1e-5):
+    """dx (+ ``addend``) and, per block of rows, one row of ``dg_part`` [blocks, D] with the gain's partial gradient."""
+    run = _mats((dy, "dy"), (dx, "dx"), (addend, "addend"))
+    return ("dsc_layernorm_bwd_f32", _mat(x, "x") + (_dev(g).data_ptr(),) + run + (dg_part.data_ptr(), dg_part.shape[0], x.shape[0],
+                                                                                   x.shape[1], eps), (x, g, dy, dx, dg_part, addend))
+
+
 def layernorm_bwd(x, g, dy, eps=1e-5):
-    xp, ldx = _mat(x, "x")
-    dp, ldy = _mat(dy, "dy")
     M, Dd = x.shape
     dx = torch.empty((M, Dd), device=x.device, dtype=torch.float32)
-    nblk = min((M + 3) // 4, 512)
-    part = torch.empty((nblk, Dd), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.fn("dsc_layernorm_bwd_f32")(xp, ldx, _dev(g).data_ptr(), dp, ldy, dx.data_ptr(), Dd, None, 0, part.data_ptr(),
-                                                nblk, M, Dd, eps, stream_ptr()), "dsc_layernorm_bwd_f32")
+    part = torch.empty((min((M + 3) // 4, 512), Dd), device=x.device, dtype=torch.float32)
+    issue(layernorm_bwd_rec(x, g, dy, dx, part, None, eps))
     return dx, colsum(part)
 
 
+def _qkv_grads(q, k, v, dout, dq, dk, dv):
+    return _mats((q, "q"), (k, "k"), (v, "v"), (dout, "dout"), (dq, "dq"), (dk, "dk"), (dv, "dv"))
+
+
+def linear_attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, nq, nk, scale):
+    return "dsc_linear_attention_bwd_f32", _qkv_grads(q, k, v, dout, dq, dk, dv) + (scenes, nq, nk, scale), (q, k, v, dout, dq, dk, dv)
+
+
 def linear_attention_bwd(q, k, v, dout, dq, dk, dv, scenes, nq, nk, scale):
-    args = []
-    for t, nme in ((q, "q"), (k, "k"), (v, "v"), (dout, "dout"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
-        args += list(_mat(t, nme))
-    _lib.check(_lib.fn("dsc_linear_attention_bwd_f32")(*args, scenes, nq, nk, scale, stream_ptr()),
-               "dsc_linear_attention_bwd_f32")
+    issue(linear_attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, nq, nk, scale))
+
+
+def attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, n, scale):
+    return "dsc_attention_bwd_f32", _qkv_grads(q, k, v, dout, dq, dk, dv) + (scenes, n, scale), (q, k, v, dout, dq, dk, dv)
 
 
 def attention_bwd(q, k, v, dout, dq, dk, dv, scenes, n, scale):
-    args = []
-    for t, nme in ((q, "q"), (k, "k"), (v, "v"), (dout, "dout"), (dq, "dq"), (dk, "dk"), (dv, "dv")):
-        args += list(_mat(t, nme))
-    _lib.check(_lib.fn("dsc_attention_bwd_f32")(*args, scenes, n, scale, stream_ptr()), "dsc_attention_bwd_f32")
+    issue(attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, n, scale))
+
+
+def activation_bwd_rec(x, dy, dx, act):
+    _c(x, "x"); _c(dy, "dy"); _c(dx, "dx")
+    return "dsc_activation_bwd_f32", (x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), act), (x, dy, dx)
 
 
 def activation_bwd(x, dy, act):
-    _c(x, "x"); _c(dy, "dy")
     dx = torch.empty_like(x)
-    _lib.check(_lib.fn("dsc_activation_bwd_f32")(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), act,
-                                                 stream_ptr()), "dsc_activation_bwd_f32")
+    issue(activation_bwd_rec(x, dy, dx, act))
     return dx
+
+
+def ddpm_loss_rec(target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, bounds, dims, separate, iou, mean_type, grad_scale,
+                  losses, parts, dout):
+    _c(target, "target"); _c(out, "out"); _c(x_t, "x_t"); _dev(t, "t", torch.int64)
+    B, N, Cc = out.shape
+    barr = (C.c_float * 12)(*[float(v) for v in bounds]) if bounds is not None else None
+    return ("dsc_ddpm_loss_f32", (
+        target.data_ptr(), out.data_ptr(), x_t.data_ptr(), t.data_ptr(), loss_weight.data_ptr(), _opt(ca), _opt(cb),
+        _opt(alphas_cumprod), barr, losses.data_ptr(), parts.data_ptr(), dout.data_ptr(), B, N, Cc, dims["translation_dim"],
+        dims["size_dim"], dims["bbox_dim"], dims["class_dim"], dims["objectness_dim"], dims["objfeat_dim"], 1 if separate else 0,
+        1 if iou else 0, mean_type, float(grad_scale), _table_rows(loss_weight, ca, cb, alphas_cumprod)),
+        (target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, barr, losses, parts, dout))
 
 
 def ddpm_loss(target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, bounds, dims, separate, iou, mean_type,
               grad_scale=1.0):
     """-> losses_weight [B], parts [B, 9], dout [B, N, C] (grad_scale * d losses_weight[b] / d out[b])"""
-    _c(target, "target"); _c(out, "out"); _c(x_t, "x_t"); _dev(t, "t", torch.int64)
-    B, N, Cc = out.shape
+    B = out.shape[0]
     losses = torch.empty((B,), device=out.device, dtype=torch.float32)
     parts = torch.empty((B, 9), device=out.device, dtype=torch.float32)
     dout = torch.empty_like(out)
-    barr = (C.c_float * 12)(*[float(v) for v in bounds]) if bounds is not None else None
-    _lib.check(_lib.fn("dsc_ddpm_loss_f32")(
-        target.data_ptr(), out.data_ptr(), x_t.data_ptr(), t.data_ptr(), loss_weight.data_ptr(),
-        ca.data_ptr() if ca is not None else None, cb.data_ptr() if cb is not None else None,
-        alphas_cumprod.data_ptr() if alphas_cumprod is not None else None, barr,
-        losses.data_ptr(), parts.data_ptr(), dout.data_ptr(), B, N, Cc, dims["translation_dim"], dims["size_dim"],
-        dims["bbox_dim"], dims["class_dim"], dims["objectness_dim"], dims["objfeat_dim"], 1 if separate else 0,
-        1 if iou else 0, mean_type, float(grad_scale), _table_rows(loss_weight, ca, cb, alphas_cumprod), stream_ptr()),
-        "dsc_ddpm_loss_f32")
+    issue(ddpm_loss_rec(target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, bounds, dims, separate, iou, mean_type, grad_scale,
+                        losses, parts, dout))
     return losses, parts, dout

@@ -26,6 +26,7 @@ import os
 
 import torch
 
+from . import engine, ops
 from ._lib import ACT_GELU, ACT_NONE, ACT_SILU, SS_NONE, SS_PER_SCENE, SS_PER_SLOT, SS_PER_TOKEN
 
 D = 512
@@ -142,7 +143,6 @@ class HipBackend:
     def planes_of(self, w, rows, layout=0):
         """bf16 planes of weight operand ``w`` ([n][K], rows contiguous) for a product with ``rows`` activation rows, in ``layout``
         (ops.planes_layout of the launch: row-major for the block-staged split kernel, fragment-major for the wave-autonomous one), or None."""
-        from . import ops
         if not self.split or rows < 256 or w.dim() != 2 or w.stride(1) != 1 or not ops.planes_wanted(w.shape[0], w.shape[1]):
             return None
         key = (w.data_ptr(), tuple(w.shape), w.stride(0), layout)
@@ -162,33 +162,19 @@ class HipBackend:
     def split_steps(self):
         """Launches that (re-)split every weight registered since the last call; the plan places them where those weights are
         final for the step (after the weight standardisation in the forward list, after the transposes in the backward list)."""
-        from . import ops
         ents, self._planes_new = self._planes_new, []
-        steps = []
-        for i in range(0, len(ents), self.lib.WS_MAX):
-            part = ents[i:i + self.lib.WS_MAX]
-            arr = (self.lib.SplitItem * len(part))()
-            for j, (w, planes, src, frag) in enumerate(part):      # frag: 2 = fragment-major output (DSC_SPLIT_FRAGMENT)
-                if src is not None:              # planes of w = src^T, read from the source: the f32 copy w is never needed for this
-                    ptr, ldw = ops._mat(src, "w")
-                    arr[j].w, arr[j].ldw, arr[j].rows, arr[j].cols, arr[j].planes, arr[j].transpose = (
-                        ptr, ldw, src.shape[0], src.shape[1], planes.data_ptr(), 1 | frag)
-                    continue
-                ptr, ldw = ops._mat(w, "w")
-                arr[j].w, arr[j].ldw, arr[j].rows, arr[j].cols, arr[j].planes, arr[j].transpose = (
-                    ptr, ldw, w.shape[0], w.shape[1], planes.data_ptr(), frag)
-            steps.append(self._call("dsc_split_bf16x3_f32", arr, len(part), keep=(arr, part)))
-        return steps
+        # planes of w = src^T are read from the source with the transpose folded in (flag 1): the f32 copy w is never needed for this
+        ents = [(w, planes, frag) if src is None else (src, planes, 1 | frag) for w, planes, src, frag in ents]
+        return [self._rec(ops.split_rec(ents[i:i + self.lib.WS_MAX])) for i in range(0, len(ents), self.lib.WS_MAX)]
 
     # -- helpers
-    def _mat(self, t):
-        from .ops import _mat
-        return _mat(t, "plan tensor")
-
     def _call(self, name, *args, keep=()):
-        from .engine import _own
-        self.keep.append(_own(keep))          # parameters as aliases of their storage: the launch's pointers stay owned by the plan
+        self.keep.append(engine._own(keep))          # parameters as aliases of their storage: the launch's pointers stay owned by the plan
         return (self.lib.fn(name), args, name)
+
+    def _rec(self, rec):
+        """A launch record of ops (name, args, keep) as a step of this plan."""
+        return self._call(rec[0], *rec[1], keep=rec[2])
 
     def finalize(self):
         """Allocate the shared split-reduction workspace (kernels of one stream run in order, so it is shared)."""
@@ -206,53 +192,48 @@ class HipBackend:
         self._scratch_users.append(fix)
         return holder
 
+    def _attach_planes(self, g, w, rows, gn=False):
+        """The planes of weight operand ``w`` attached to launch ``g`` of ``rows`` activation rows, or None (ops.planes_for)."""
+        return ops.planes_for(g, gn, w, lambda w, lay: self.planes_of(w, rows, lay))
+
+    def _reads_f32(self, w):
+        self.f32_reads.add(w.untyped_storage().data_ptr())
+
     # -- forward ops
     def fuse_act_ok(self, a, w, out, a2=None, bias=None, preact=None, actgrad_x=None):
         """Can this product carry an activation epilogue of the training step (pre-activation also stored / result multiplied by the
         derivative)?  Only the split-bf16 kernel implements them: ask the library whether it takes the launch -- with the argument
         struct of the launch itself (bias / preact / actgrad_x pointers and strides take part in its decision: alignment)."""
-        from . import ops
         if not self.split or a.shape[0] < 256 or os.environ.get("DSC_FUSE_ACT", "1") == "0":      # (A/B switch of the measurement tools)
             return False
         g = ops.make_gemm_args(a, w, out, bias, a2, act_out=ACT_GELU if (preact is not None or actgrad_x is not None) else ACT_NONE,
                                preact=preact, actgrad_x=actgrad_x)
-        lay = ops.planes_layout(g)
-        return lay >= 0 and self.planes_of(w, a.shape[0], lay) is not None
+        return self._attach_planes(g, w, a.shape[0]) is not None
 
     def gemm(self, a, w, out, bias=None, a2=None, residual=None, act_out=ACT_NONE, preact=None, actgrad_x=None):
-        from . import ops
         m, K = a.shape
-        if preact is not None or actgrad_x is not None:
-            g = ops.make_gemm_args(a, w, out, bias, a2, residual, ACT_NONE, act_out, preact=preact, actgrad_x=actgrad_x)
-            lay = ops.planes_layout(g)
-            pl = self.planes_of(w, m, lay) if lay >= 0 else None
-            if pl is None:
-                raise RuntimeError("HipBackend.gemm: an activation epilogue was planned for a launch the split kernel does not take")
-            ops.attach_planes(g, pl, layout=lay)
-            return self._call("dsc_gemm_f32", C.byref(g), keep=(g, a, w, out, bias, a2, residual, pl, preact, actgrad_x))
+        g = ops.make_gemm_args(a, w, out, bias, a2, residual, ACT_NONE, act_out, preact=preact, actgrad_x=actgrad_x)
+        epilogue = preact is not None or actgrad_x is not None
         # short, deep products (time / context MLPs: m = B or N rows, K >= 1024): split K over the batch dimension
         tiles = ((m + 63) // 64) * ((out.shape[1] + 63) // 64)        # output tiles: fewer than CUs -> parallelise K instead
-        if a2 is None and act_out == ACT_NONE and tiles < 256 and K >= 1024 and (m * out.shape[1]) % 4 == 0:
+        if not epilogue and a2 is None and act_out == ACT_NONE and tiles < 256 and K >= 1024 and (m * out.shape[1]) % 4 == 0:
             splits = next((s for s in (8, 4, 2) if K % (32 * s) == 0 and K // s >= 128), 0)
             if splits:
-                fn = self.lib.fn("dsc_gemm_splitk_f32")
-                floats = splits * m * out.shape[1]
-                g = ops.make_gemm_args(a, w, out, bias, a2, residual, ACT_NONE, act_out)
-                from .engine import _own
-                self.keep.append(_own((g, a, w, out, bias, residual)))       # the plan owns the storages its raw pointers refer to
-                self.f32_reads.add(w.untyped_storage().data_ptr())
-                return self._with_scratch(floats, lambda wp, wn: (fn, (C.byref(g), splits, wp, wn), "dsc_gemm_splitk_f32"))
-        g = ops.make_gemm_args(a, w, out, bias, a2, residual, ACT_NONE, act_out)
-        lay = ops.planes_layout(g)                      # planes only for launches that will use them, in the layout their kernel reads
-        pl = self.planes_of(w, m, lay) if lay >= 0 else None
-        if pl is not None:
-            ops.attach_planes(g, pl, layout=lay)
-        else:
-            self.f32_reads.add(w.untyped_storage().data_ptr())
-        return self._call("dsc_gemm_f32", C.byref(g), keep=(g, a, w, out, bias, a2, residual, pl))
+                return self._splitk(g, splits, w, keep=(g, a, w, out, bias, residual))
+        pl = self._attach_planes(g, w, m)                      # planes only for launches that will use them, in the layout their kernel reads
+        if pl is None and epilogue:
+            raise RuntimeError("HipBackend.gemm: an activation epilogue was planned for a launch the split kernel does not take")
+        if pl is None:
+            self._reads_f32(w)
+        return self._call("dsc_gemm_f32", C.byref(g), keep=(g, a, w, out, bias, a2, residual, pl, preact, actgrad_x))
+
+    def _splitk(self, g, splits, w, keep):
+        """One dsc_gemm_splitk_f32 launch of ``g`` over ``splits`` slabs of K, reduced through the shared workspace."""
+        self._reads_f32(w)
+        return self._with_scratch(splits * g.m * g.n,
+                                  lambda wp, wn: self._call("dsc_gemm_splitk_f32", C.byref(g), splits, wp, wn, keep=keep))
 
     def _gnbwd_args(self, dy, wt, dz, gn, part):
-        from . import ops
         Cc = dz.shape[1]
         # row layout [dbias | dgamma | dbeta] (the order of the parameters in G), as gn_bwd; part None: the question only (any aligned addresses)
         pp, ps = (part.data_ptr(), part.stride(0)) if part is not None else (0x100000, 3 * Cc)
@@ -261,134 +242,78 @@ class HipBackend:
                                gnb=dict(z=gn["z"], dgamma=pp + 4 * Cc, dbeta=pp + 8 * Cc, dbias=pp, pstride=ps, dss=gn["dss"]))
         return g
 
+    def _planes_fragment(self, g, wt, rows):
+        """As _attach_planes, for a launch only the wave-autonomous kernel (fragment-major planes) can take."""
+        return ops.planes_for(g, False, wt, lambda w, lay: self.planes_of(w, rows, lay) if lay == ops.PLANES_FRAGMENT else None)
+
     def fuse_gnbwd_ok(self, dy, wt, like, gn):
         """Can the input-gradient GEMM dh = dy . W carry the GroupNorm backward of the Block that produced h in its epilogue (round 6: the
         wave-autonomous kernel's row-layout epilogue; include/diffuscene_hip.h, gnb_*)?  The library decides, on a struct of the launch's
         shape (``like``: a tensor of the output's shape and alignment -- nothing is allocated for the question)."""
-        from . import ops
         if not self.split or os.environ.get("DSC_FUSE_GNBWD", "1") == "0" or gn["ss_mode"] not in (SS_NONE, SS_PER_SCENE):
             return False
-        g = self._gnbwd_args(dy, wt, like, gn, None)
-        return ops.planes_layout(g) == ops.PLANES_FRAGMENT and self.planes_of(wt, dy.shape[0], ops.PLANES_FRAGMENT) is not None
+        return self._planes_fragment(self._gnbwd_args(dy, wt, like, gn, None), wt, dy.shape[0]) is not None
 
     def gemm_gnbwd(self, dy, wt, dz, gn, part):
-        from . import ops
         g = self._gnbwd_args(dy, wt, dz, gn, part)
-        lay = ops.planes_layout(g)
-        pl = self.planes_of(wt, dy.shape[0], lay) if lay >= 0 else None
+        pl = self._attach_planes(g, wt, dy.shape[0])
         if pl is None:
             raise RuntimeError("HipBackend.gemm_gnbwd: planned for a launch the wave-autonomous kernel does not take")
-        ops.attach_planes(g, pl, layout=lay)
         return self._call("dsc_gemm_f32", C.byref(g), keep=(g, dy, wt, dz, gn["z"], gn["gamma"], gn["beta"], gn["ss"], gn["dss"], part, pl))
 
     def gemm_long_k(self, a, w, out, residual=None):
         """out = a @ w^T (+ residual) for a LONG reduction (K > 4096) with few output tiles: one dsc_gemm_splitk_f32 launch with the most
         slabs (<= 64) that keep a slab >= 256 terms -- or None when the shape does not fit that entry point (the caller chunks)."""
-        from . import ops
         m, K = a.shape
-        n = out.shape[1]
-        if (m * n) % 4 or K % 32:
-            return None
-        splits = long_k_splits(K)
+        splits = 0 if (m * out.shape[1]) % 4 or K % 32 else long_k_splits(K)
         if not splits:
             return None
-        fn = self.lib.fn("dsc_gemm_splitk_f32")
         g = ops.make_gemm_args(a, w, out, None, None, residual, ACT_NONE, ACT_NONE)
-        from .engine import _own
-        self.keep.append(_own((g, a, w, out, residual)))
-        self.f32_reads.add(w.untyped_storage().data_ptr())
-        floats = splits * m * n
-        return self._with_scratch(floats, lambda wp, wn: (fn, (C.byref(g), splits, wp, wn), "dsc_gemm_splitk_f32"))
+        return self._splitk(g, splits, w, keep=(g, a, w, out, residual))
 
     def gemm_gn(self, a, w, out, bias, gamma, beta, n_tok, a2=None, ss=None, ss_mode=SS_NONE, residual=None, preact=None):
-        from . import ops
         g = ops.make_gemm_args(a, w, out, bias, a2, residual, gamma=gamma, beta=beta, eps=1e-5, tokens_per_scene=n_tok,
                                scale_shift=ss, ss_mode=ss_mode if ss is not None else SS_NONE, preact=preact)
-        lay = ops.planes_layout(g, gn=True)
-        pl = self.planes_of(w, a.shape[0], lay) if lay >= 0 else None
-        if pl is not None:
-            ops.attach_planes(g, pl, gn=True, layout=lay)
-        else:
-            self.f32_reads.add(w.untyped_storage().data_ptr())
+        pl = self._attach_planes(g, w, a.shape[0], gn=True)
+        if pl is None:
+            self._reads_f32(w)
         return self._call("dsc_gemm_gn_silu_f32", C.byref(g), keep=(g, a, w, out, bias, gamma, beta, a2, ss, residual, preact, pl))
 
     def smallk(self, x, w, bias, out, act_out=ACT_NONE):
-        xp, ldx = self._mat(x)
-        wp, ldw = self._mat(w)
-        yp, ldy = self._mat(out)
-        return self._call("dsc_linear_smallk_f32", xp, ldx, x.shape[1], wp, ldw, bias.data_ptr() if bias is not None else None,
-                          yp, ldy, x.shape[0], w.shape[0], act_out, keep=(x, w, bias, out))
+        return self._rec(ops.linear_smallk_rec(x, w, bias, out, act_out))
 
     def ws(self, weights, outs):
-        from . import ops
-        steps = []
-        for i in range(0, len(weights), self.lib.WS_MAX):
-            arr = ops.make_ws_items(list(zip(weights[i:i + self.lib.WS_MAX], outs[i:i + self.lib.WS_MAX])))
-            steps.append(self._call("dsc_weight_standardize_f32", arr, len(arr), 1e-5, keep=(arr, weights, outs)))
-        return steps
+        n = self.lib.WS_MAX
+        return [self._rec(ops.weight_standardize_rec(list(zip(weights[i:i + n], outs[i:i + n])))) for i in range(0, len(weights), n)]
 
     def time_embedding(self, t, table, freq, out):
-        return self._call("dsc_time_embedding_f32", t.data_ptr(), t.shape[0], out.shape[1], table.data_ptr(), table.shape[0],
-                          freq.data_ptr(), out.data_ptr(), keep=(t, table, freq, out))
+        return self._rec(ops.time_embedding_rec(t, out.shape[1], table, freq, out))
 
     def act(self, x, out, kind):
-        assert x.is_contiguous() and out.is_contiguous()
-        return self._call("dsc_activation_f32", x.data_ptr(), out.data_ptr(), x.numel(), kind, keep=(x, out))
+        return self._rec(ops.activation_rec(x, out, kind))
 
     def layernorm(self, x, g, out, residual=None):
-        xp, ldx = self._mat(x)
-        yp, ldy = self._mat(out)
-        rp, ldr = self._mat(residual) if residual is not None else (None, 0)
-        return self._call("dsc_layernorm_f32", xp, ldx, g.data_ptr(), rp, ldr, yp, ldy, x.shape[0], x.shape[1], 1e-5,
-                          keep=(x, g, out, residual))
+        return self._rec(ops.layernorm_rec(x, g, out, residual))
 
     def linattn(self, q, k, v, out, scenes, nq, nk, scale):
-        a = []
-        for t in (q, k, v, out):
-            a += list(self._mat(t))
-        return self._call("dsc_linear_attention_f32", *a, scenes, nq, nk, scale, keep=(q, k, v, out))
+        return self._rec(ops.linear_attention_rec(q, k, v, out, scenes, nq, nk, scale))
 
     def attn(self, q, k, v, out, scenes, n, scale):
-        a = []
-        for t in (q, k, v, out):
-            a += list(self._mat(t))
-        return self._call("dsc_attention_f32", *a, scenes, n, scale, keep=(q, k, v, out))
+        return self._rec(ops.attention_rec(q, k, v, out, scenes, n, scale))
 
     def q_sample(self, x0, noise, t, sqrt_ac, sqrt_1mac, xt, v):
-        b = x0.shape[0]
-        return self._call("dsc_q_sample_f32", x0.data_ptr(), noise.data_ptr(), t.data_ptr(), sqrt_ac.data_ptr(),
-                          sqrt_1mac.data_ptr(), xt.data_ptr(), v.data_ptr() if v is not None else None, b, x0.numel() // b,
-                          int(sqrt_ac.numel()), keep=(x0, noise, t, sqrt_ac, sqrt_1mac, xt, v))
+        return self._rec(ops.q_sample_rec(x0, noise, t, sqrt_ac, sqrt_1mac, xt, v))
 
     def loss(self, target, out, x_t, t, tb, ca, cb, bounds, dims, separate, iou, mean_type, losses, parts, dout, scale):
-        B, N, Cc = out.shape
-        barr = (C.c_float * 12)(*[float(v) for v in bounds]) if bounds is not None else None
-        return self._call("dsc_ddpm_loss_f32", target.data_ptr(), out.data_ptr(), x_t.data_ptr(), t.data_ptr(),
-                          tb["loss_weight"].data_ptr(), ca.data_ptr() if ca is not None else None,
-                          cb.data_ptr() if cb is not None else None, tb["alphas_cumprod"].data_ptr(), barr,
-                          losses.data_ptr(), parts.data_ptr(), dout.data_ptr(), B, N, Cc, dims["translation_dim"],
-                          dims["size_dim"], dims["bbox_dim"], dims["class_dim"], dims["objectness_dim"], dims["objfeat_dim"],
-                          1 if separate else 0, 1 if iou else 0, mean_type, float(scale), int(tb["loss_weight"].numel()),
-                          keep=(target, out, x_t, t, tb, ca, cb, barr, losses, parts, dout))
+        return self._rec(ops.ddpm_loss_rec(target, out, x_t, t, tb["loss_weight"], ca, cb, tb["alphas_cumprod"], bounds, dims, separate,
+                                           iou, mean_type, scale, losses, parts, dout))
 
     # -- backward ops
     def gemm_tn(self, a, dy, out, a2=None, kvalid=None, dbias=None):
-        ap, lda = self._mat(a)
-        dp, ldd = self._mat(dy)
-        a2p, lda2, k2 = (None, 0, 0)
-        if a2 is not None:
-            a2p, lda2 = self._mat(a2)
-            k2 = a2.shape[1]
-        k1 = a.shape[1]
-        kv = (k1 + k2) if kvalid is None else kvalid
-        m, n = dy.shape
-        op, ldo = self._mat(out)
-        wsf = self.lib.fn("dsc_gemm_tn_workspace_floats")(m, n, kv)
-        fn = self.lib.fn("dsc_gemm_tn_f32")
-        self.keep.append((a, dy, out, a2, dbias))
-        dbp = dbias.data_ptr() if dbias is not None else None
-        return self._with_scratch(wsf, lambda wp, wn: (fn, (ap, lda, k1, a2p, lda2, k2, dp, ldd, op, ldo, dbp, m, n, kv,
-                                                            wp if wsf else None, wn if wsf else 0), "dsc_gemm_tn_f32"))
+        kv = (a.shape[1] + (a2.shape[1] if a2 is not None else 0)) if kvalid is None else kvalid
+        wsf = self.lib.fn("dsc_gemm_tn_workspace_floats")(dy.shape[0], dy.shape[1], kv)
+        return self._with_scratch(wsf, lambda wp, wn: self._rec(ops.gemm_tn_rec(a, dy, out, a2, kvalid, dbias, wp if wsf else None,
+                                                                                wn if wsf else 0)))
 
     def gemm_tn_grouped(self, items):
         """items: dicts(a, dy, out, a2, kvalid, dbias) -> ONE launch (plus the slab reduction when the tokens are split)."""
@@ -396,45 +321,31 @@ class HipBackend:
         # longest groups first (the block scheduler hands out tiles in id order): the short ones fill the tail
         items = sorted(items, key=lambda it: -it["dy"].shape[0])
         arr = (self.lib.TnGroup * len(items))()
-        tile0, ws_off = 0, 0
-        tile0s = 0                                    # 256 x 128 tile numbering of the split-bf16 form
+        total = tile0s = 0                            # 128 x 128 tile numbering; 256 x 128 numbering of the split-bf16 form
         use_split = self.split
-        per_group = []
-        shapes = [(it["dy"].shape[0], it["dy"].shape[1], it["a"].shape[1] + (it["a2"].shape[1] if it.get("a2") is not None else 0))
-                  for it in items]
-        for i, it in enumerate(items):
-            a, dy, out, a2, dbias = it["a"], it["dy"], it["out"], it.get("a2"), it.get("dbias")
-            ap, lda = self._mat(a)
-            dp, ldd = self._mat(dy)
-            op, ldo = self._mat(out)
-            k1 = a.shape[1]
-            a2p, lda2, k2 = (None, 0, 0)
-            if a2 is not None:
-                a2p, lda2 = self._mat(a2)
-                k2 = a2.shape[1]
-            m, n = dy.shape
-            kv = (k1 + k2) if it.get("kvalid") is None else it["kvalid"]
-            # the checks dsc_gemm_tn_f32 makes on the host (the grouped entry point only sees a device table)
-            if (k1 & 3) or (k2 & 3) or (n & 3) or (k2 > 0 and k1 % 128) or not (1 <= kv <= k1 + k2):
-                raise RuntimeError("gemm_tn_grouped: bad shape m=%d n=%d k1=%d k2=%d kvalid=%d" % (m, n, k1, k2, kv))
-            if (ap % 16) or (lda & 3) or (dp % 16) or (ldd & 3) or (k2 and ((a2p % 16) or (lda2 & 3))):
-                raise RuntimeError("gemm_tn_grouped: operands must be 16-byte aligned with row strides multiple of 4")
-            if a.shape[0] != m or (a2 is not None and a2.shape[0] != m) or tuple(out.shape) != (n, kv):
-                raise RuntimeError("gemm_tn_grouped: shape mismatch")
-            g = arr[i]
-            g.a1, g.lda1, g.k1, g.a2, g.lda2, g.k2 = ap, lda, k1, a2p, lda2, k2
-            g.dy, g.ldd, g.out, g.ldo = dp, ldd, op, ldo
-            g.dbias = dbias.data_ptr() if dbias is not None else None
-            g.m, g.n, g.kvalid, g.tile0 = m, n, kv, tile0
-            nt = ((n + 127) // 128) * ((k1 + k2 + 127) // 128)
-            tile0 += nt
-            g.tile0s = tile0s
-            nts = ((n + 255) // 256) * ((k1 + k2 + 127) // 128)
-            tile0s += nts
-            if m * max(lda, ldd, lda2) * 4 >= 0x7fffffff:
+        shapes = []
+        for g, it in zip(arr, items):
+            # the host checks of dsc_gemm_tn_f32: the grouped entry points only see a device table
+            run, (m, n, kv) = ops.tn_operands(it["a"], it["dy"], it["out"], it.get("a2"), it.get("kvalid"), "gemm_tn_grouped")
+            g.a1, g.lda1, g.k1, g.a2, g.lda2, g.k2, g.dy, g.ldd, g.out, g.ldo = run
+            g.dbias = it["dbias"].data_ptr() if it.get("dbias") is not None else None
+            g.m, g.n, g.kvalid, g.tile0, g.tile0s = m, n, kv, total, tile0s
+            K = g.k1 + g.k2
+            total += ((n + 127) // 128) * ((K + 127) // 128)
+            tile0s += ((n + 255) // 256) * ((K + 127) // 128)
+            if m * max(g.lda1, g.ldd, g.lda2) * 4 >= 0x7fffffff:
                 use_split = False                      # 32-bit byte offsets inside an operand
-            per_group.append((n, kv, ldo))
-        total = tile0
+            shapes.append((m, n, K))
+
+        def slab_offsets(splits):
+            ws_off = 0
+            if splits > 1:
+                for g in arr:
+                    if g.ldo != g.kvalid:
+                        raise RuntimeError("gemm_tn_grouped: split outputs must be dense [n][kvalid]")
+                    g.ws_offset = ws_off
+                    ws_off += (g.n * g.kvalid + g.n) * splits
+            return ws_off
         if use_split:
             # one 8-wave block per CU: cut the tokens until the long tiles make ~3 rounds of 256 blocks (measured, living80: the three
             # grouped launches of a step 8.35 ms at 8 rounds / 7.9 ms at 3 / 8.6 ms at 2 -- fewer slabs to write and re-read against a
@@ -447,138 +358,65 @@ class HipBackend:
             # reduction launch for 6 missing tiles; arrange: 470 -- hence the margin of 64)
             rounds = int(os.environ.get("DSC_TN_ROUNDS", "3" if tile_k == 128 else "2"))
             splits, _ = tn_token_slices(shapes, 256, rounds * 256 - (64 if tile_k == 256 else 0), tile_k)
-            ws_off = 0
-            if splits > 1:
-                for i, (n, kv, ldo) in enumerate(per_group):
-                    if ldo != kv:
-                        raise RuntimeError("gemm_tn_grouped: split outputs must be dense [n][kvalid]")
-                    arr[i].ws_offset = ws_off
-                    ws_off += (n * kv + n) * splits
-            table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
+            ws_off = slab_offsets(splits)
+            table = ops.device_table(arr, self.device)
             bmap = np.asarray(tn_block_map(shapes, tile_k=tile_k), dtype=np.int32).reshape(-1, 2)
             want_tiles = sum(((n + 255) // 256) * ((k + tile_k - 1) // tile_k) for _, n, k in shapes)
             assert int((bmap[:, 0] >= 0).sum()) == want_tiles, "block map must cover every 256 x %d tile exactly once" % tile_k
             bmap_dev = torch.from_numpy(bmap.copy()).to(self.device)
-            self.keep.append((table, items, bmap_dev))
-            fn = self.lib.fn("dsc_gemm_tn_grouped_split_f32")
-            tp, cnt, bp, nblk = table.data_ptr(), len(items), bmap_dev.data_ptr(), bmap.shape[0]
-            return self._with_scratch(ws_off, lambda wp, wn: (fn, (tp, cnt, total, bp, nblk, splits, wp if splits > 1 else None,
-                                                                    wn if splits > 1 else 0, ws_off, tile_k), "dsc_gemm_tn_grouped_split_f32"))
+            return self._with_scratch(ws_off, lambda wp, wn: self._call(
+                "dsc_gemm_tn_grouped_split_f32", table.data_ptr(), len(items), total, bmap_dev.data_ptr(), bmap.shape[0], splits,
+                wp if splits > 1 else None, wn if splits > 1 else 0, ws_off, tile_k, keep=(table, items, bmap_dev)))
         # the long tiles set the duration: cut the tokens until they make ~8 rounds of 2 blocks per CU (tail < 1/8); with all
         # layers of a step in one group that is 2 slabs per gradient instead of the 32 of a per-layer launch
         splits, _ = tn_token_slices(shapes, 128, 8 * 512)
-        if splits > 1:
-            for i, (n, kv, ldo) in enumerate(per_group):
-                if ldo != kv:
-                    raise RuntimeError("gemm_tn_grouped: split outputs must be dense [n][kvalid]")
-                arr[i].ws_offset = ws_off
-                ws_off += (n * kv + n) * splits
-        table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
-        self.keep.append((table, items))
-        fn = self.lib.fn("dsc_gemm_tn_grouped_f32")
-        tp, cnt = table.data_ptr(), len(items)
-        return self._with_scratch(ws_off, lambda wp, wn: (fn, (tp, cnt, total, splits, wp if splits > 1 else None,
-                                                                wn if splits > 1 else 0, ws_off), "dsc_gemm_tn_grouped_f32"))
+        ws_off = slab_offsets(splits)
+        table = ops.device_table(arr, self.device)
+        return self._with_scratch(ws_off, lambda wp, wn: self._call(
+            "dsc_gemm_tn_grouped_f32", table.data_ptr(), len(items), total, splits, wp if splits > 1 else None,
+            wn if splits > 1 else 0, ws_off, keep=(table, items)))
 
     def colsum(self, x, out):
-        xp, ldx = self._mat(x)
-        m, n = x.shape
-        fn = self.lib.fn("dsc_colsum_f32")
-        self.keep.append((x, out))
-        op = out.data_ptr()
-        return self._with_scratch(64 * n, lambda wp, wn: (fn, (xp, ldx, m, n, op, wp, wn), "dsc_colsum_f32"))
+        return self._with_scratch(64 * x.shape[1], lambda wp, wn: self._rec(ops.colsum_rec(x, out, wp, wn)))
 
     def colsum_grouped(self, pairs):
         """pairs: [(x [m, n] with contiguous rows, out [n] contiguous)] -> ONE launch."""
-        import numpy as np
-        arr = (self.lib.ColsumItem * len(pairs))()
-        max_n = 0
-        for i, (x, out) in enumerate(pairs):
-            xp, ldx = self._mat(x)
-            assert out.is_contiguous() and out.numel() == x.shape[1]
-            arr[i].x, arr[i].ldx, arr[i].m, arr[i].n, arr[i].out = xp, ldx, x.shape[0], x.shape[1], out.data_ptr()
-            max_n = max(max_n, x.shape[1])
-        table = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(self.device)
-        return self._call("dsc_colsum_grouped_f32", table.data_ptr(), len(pairs), max_n, keep=(table, pairs))
+        return self._rec(ops.colsum_grouped_rec(pairs, self.device))
 
     def gn_bwd(self, z, dy, gamma, beta, ss, ss_mode, dz, part, dss, scenes, n_tok):
-        zp, ldz = self._mat(z)
-        dp, ldy = self._mat(dy)
-        dzp, lddz = self._mat(dz)
-        Cc = z.shape[1]
-        sp, ld_ss = self._mat(ss) if ss is not None else (None, 0)
-        dsp, ld_dss = self._mat(dss) if dss is not None else (None, 0)
-        pp = part.data_ptr()                       # row layout [dbias | dgamma | dbeta] (the order of the parameters in G)
-        return self._call("dsc_gn_silu_bwd_f32", zp, ldz, dp, ldy, gamma.data_ptr(), beta.data_ptr(), sp, ld_ss,
-                          ss_mode if sp else SS_NONE, dzp, lddz, pp + 4 * Cc, pp + 8 * Cc, pp, part.stride(0), dsp, ld_dss,
-                          scenes, n_tok, Cc, 1e-5, keep=(z, dy, gamma, beta, ss, dz, part, dss))
+        # row layout [dbias | dgamma | dbeta] (the order of the parameters in G)
+        return self._rec(ops.gn_silu_bwd_rec(z, dy, gamma, beta, ss, ss_mode, dz, part, (1, 2, 0), dss, scenes, n_tok))
 
     def ws_bwd(self, weights, dws, outs):
-        steps = []
-        for i in range(0, len(weights), self.lib.WS_MAX):
-            ws_, gs, os_ = weights[i:i + self.lib.WS_MAX], dws[i:i + self.lib.WS_MAX], outs[i:i + self.lib.WS_MAX]
-            arr = (self.lib.WsBwdItem * len(ws_))()
-            for j, (w, g, o) in enumerate(zip(ws_, gs, os_)):
-                w2, o2 = _as2d(w), _as2d(o)
-                assert w2.is_contiguous() and g.is_contiguous() and o2.is_contiguous()
-                arr[j].w, arr[j].dw_std, arr[j].dw = w2.data_ptr(), g.data_ptr(), o2.data_ptr()
-                arr[j].rows, arr[j].cols = w2.shape
-            steps.append(self._call("dsc_weight_standardize_bwd_f32", arr, len(ws_), 1e-5, keep=(arr, ws_, gs, os_)))
-        return steps
+        n = self.lib.WS_MAX
+        return [self._rec(ops.weight_standardize_bwd_rec(list(zip(weights[i:i + n], dws[i:i + n], outs[i:i + n]))))
+                for i in range(0, len(weights), n)]
 
     def layernorm_bwd(self, x, g, dy, dx, dg_part, addend=None):
-        xp, ldx = self._mat(x)
-        dp, ldy = self._mat(dy)
-        dxp, lddx = self._mat(dx)
-        ap, lda = self._mat(addend) if addend is not None else (None, 0)
-        return self._call("dsc_layernorm_bwd_f32", xp, ldx, g.data_ptr(), dp, ldy, dxp, lddx, ap, lda, dg_part.data_ptr(),
-                          dg_part.shape[0], x.shape[0], x.shape[1], 1e-5, keep=(x, g, dy, dx, dg_part, addend))
+        return self._rec(ops.layernorm_bwd_rec(x, g, dy, dx, dg_part, addend))
 
     def linattn_bwd(self, q, k, v, dout, dq, dk, dv, scenes, nq, nk, scale):
-        a = []
-        for t in (q, k, v, dout, dq, dk, dv):
-            a += list(self._mat(t))
-        return self._call("dsc_linear_attention_bwd_f32", *a, scenes, nq, nk, scale, keep=(q, k, v, dout, dq, dk, dv))
+        return self._rec(ops.linear_attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, nq, nk, scale))
 
     def attn_bwd(self, q, k, v, dout, dq, dk, dv, scenes, n, scale):
-        a = []
-        for t in (q, k, v, dout, dq, dk, dv):
-            a += list(self._mat(t))
-        return self._call("dsc_attention_bwd_f32", *a, scenes, n, scale, keep=(q, k, v, dout, dq, dk, dv))
+        return self._rec(ops.attention_bwd_rec(q, k, v, dout, dq, dk, dv, scenes, n, scale))
 
     def act_bwd(self, x, dy, dx, kind):
-        assert x.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
-        return self._call("dsc_activation_bwd_f32", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), x.numel(), kind,
-                          keep=(x, dy, dx))
+        return self._rec(ops.activation_bwd_rec(x, dy, dx, kind))
 
     def transpose_many(self, pairs):
         """pairs of (w [r,c] contiguous, out [c,r] contiguous) -> batched launches; strided outputs -> single launches."""
-        steps, batch = [], []
-        for w, o in pairs:
-            if w.is_contiguous() and o.is_contiguous():
-                batch.append((w, o))
-            else:
-                wp, ldi = self._mat(w)
-                op, ldo = self._mat(o)
-                steps.append(self._call("dsc_transpose_f32", wp, ldi, op, ldo, w.shape[0], w.shape[1], keep=(w, o)))
-        for i in range(0, len(batch), self.lib.WS_MAX):
-            part = batch[i:i + self.lib.WS_MAX]
-            arr = (self.lib.WsItem * len(part))()
-            for j, (w, o) in enumerate(part):
-                arr[j].w, arr[j].out = w.data_ptr(), o.data_ptr()
-                arr[j].rows, arr[j].cols = w.shape
-            steps.append(self._call("dsc_transpose_batched_f32", arr, len(part), keep=(arr, part)))
-        return steps
+        batch = [(w, o) for w, o in pairs if w.is_contiguous() and o.is_contiguous()]
+        steps = [self._rec(ops.transpose_rec(w, o)) for w, o in pairs if not (w.is_contiguous() and o.is_contiguous())]
+        n = self.lib.WS_MAX
+        return steps + [self._rec(ops.transpose_batched_rec(batch[i:i + n])) for i in range(0, len(batch), n)]
 
     def copy(self, dst, src):
-        dp, ldd = self._mat(dst)
-        sp, lds = self._mat(src)
-        return self._call("dsc_copy2d_f32", dp, ldd, sp, lds, dst.shape[0], dst.shape[1], keep=(dst, src))
+        return self._rec(ops.copy2d_rec(dst, src))
 
     def add(self, dst, src):
-        dp, ldd = self._mat(dst)
-        sp, lds = self._mat(src)
-        return self._call("dsc_add2d_f32", dp, ldd, sp, lds, dst.shape[0], dst.shape[1], keep=(dst, src))
+        return self._rec(ops.add2d_rec(dst, src))
+
 
     # -- execution
     def run(self, steps, stream):

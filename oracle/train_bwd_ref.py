@@ -189,6 +189,12 @@ def colsum(x, dtype=torch.float64):
     return _t(x, dtype).sum(dim=0)
 
 
+def gemm_tn(a, dy, kvalid=None, dtype=torch.float64):
+    """weight gradient out[n][k] = sum_m dy[m][n] a[m][k] over the first ``kvalid`` columns of a, and dbias[n] = sum_m dy[m][n]"""
+    a, dy = _t(a, dtype), _t(dy, dtype)
+    return dy.t() @ a[:, :kvalid], dy.sum(dim=0)
+
+
 # ================================================================================================ input generators (float32 numpy)
 def noise(shape, seed, scale=1.0):
     return (np.random.RandomState(seed).standard_normal(shape) * scale).astype(np.float32)

@@ -58,6 +58,32 @@ def test_plane_split_is_exact_and_transposable(scale):
     assert torch.equal(pv, pc)
 
 
+def test_plan_backend_split_steps_match_the_eager_split():
+    """train_plan.HipBackend.split_steps, the training plan's route to the launch record of dsc_split_bf16x3_f32, at the smallest shape the
+    plane cache takes (128 x 32): a row-strided weight in both plane layouts and a transposed copy whose planes are split straight from
+    its source (the copy itself, NaN here, is never read).  The planes are exact and bit-equal to the eager wrapper's."""
+    from diffuscene_amd import ops
+    from diffuscene_amd.train_plan import HipBackend
+    be = HipBackend(dev())
+    be.split = True                                     # the plane cache whatever DSC_GEMM says: the split launch is the same
+    w = rnd(128, 96, seed=3).to(dev())[:, 32:64]        # [128][32], rows of a wider buffer: ldw = 96
+    src = rnd(32, 192, seed=4).to(dev())[:, 32:160]     # [32][128]; its transpose is the weight operand wt
+    wt = torch.full((128, 32), float("nan"), device=dev())
+    be.transposed_of[wt.data_ptr()] = src
+    pr, pf = be.planes_of(w, 256, ops.PLANES_ROWMAJOR), be.planes_of(w, 256, ops.PLANES_FRAGMENT)
+    pt = be.planes_of(wt, 256, ops.PLANES_ROWMAJOR)
+    assert pr is not None and pf is not None and pt is not None and pr is not pf
+    steps = be.split_steps()
+    assert len(steps) == 1 and be.split_steps() == []
+    be.finalize()
+    be.run(steps, ops.stream_ptr())
+    torch.cuda.synchronize()
+    f, ft = planes_to_f32(pr), planes_to_f32(pt)
+    assert torch.equal((f[0] + f[1]) + f[2], w) and torch.equal((ft[0] + ft[1]) + ft[2], src.t())
+    er, et = ops.split_planes([(w, None, False), (src, None, True)])
+    assert torch.equal(pr, er) and torch.equal(pf, ops.fragment_major(er)) and torch.equal(pt, et)
+
+
 @pytest.mark.parametrize("m,n,k,taken", [(20480, 512, 512, True), (5376, 512, 512, True), (10240, 512, 1024, True), (10240, 384, 512, True),
                                          (1536, 1024, 512, False), (300, 128, 96, False), (40000, 128, 96, True), (20480, 3072, 512, True),
                                          (2560, 2048, 2048, True)])

@@ -439,6 +439,34 @@ def test_activation_bwd(name, count):
                        whole, float(np.abs(d["dy"]).max()))])
 
 
+# ================================================================================================ single-launch weight gradient
+@pytest.mark.parametrize("m,k1,k2,kvalid", [(5, 8, 0, None), (5, 128, 4, 130), (300, 128, 4, 130)])
+def test_gemm_tn_single_launch(m, k1, k2, kvalid):
+    """dsc_gemm_tn_f32 recorded by HipBackend.gemm_tn (training plans group their weight gradients, so nothing else takes this route to
+    the entry point's launch record): one slab without a workspace (5 rows, strided output) and token slabs reduced through the shared
+    workspace (300 rows, dense output), one K segment and two with kvalid inside the second, operands as 16-byte aligned column slices of
+    wider tensors (their row strides are the leading dimensions), the bias gradient on the same pass.  Small integers: every order of
+    summation is exact, so out and dbias are bit-equal to the float64 statement."""
+    _lib, _ = lib()
+    n, K = 12, k1 + k2
+    kv = K if kvalid is None else kvalid
+    slabs = _lib.fn("dsc_gemm_tn_workspace_floats")(m, n, kv) > 0
+    assert slabs == (m == 300)
+    a_h, dy_h = T.small_ints((m, K), seed=m + K), T.small_ints((m, n), seed=m + n)
+    assert m * T.INT_MAX_ABS ** 2 < 2 ** 24
+    c = Case()
+    a, dy = c.inp(a_h[:, :k1]), c.inp(dy_h)
+    a2 = c.inp(a_h[:, k1:]) if k2 else None
+    out = c.pool([n * kv])[0].view(n, kv) if slabs else c.out(n, kv)
+    dbias = c.out1(n)
+    be = backend()
+    launch(be, be.gemm_tn(a, dy, out, a2=a2, kvalid=kvalid, dbias=dbias))
+    c.check("gemm_tn %dx%dx%d+%d" % (m, n, k1, k2))
+    want, want_b = T.gemm_tn(a_h, dy_h, kv)
+    assert exact(out, want.numpy()), "gemm_tn m=%d k=%d+%d kvalid=%s: integer products differ" % (m, k1, k2, kvalid)
+    assert exact(dbias, want_b.numpy()), "gemm_tn m=%d: integer column sums of dy differ" % m
+
+
 # ================================================================================================ column sums
 COLSUM = [(1, 1), (3, 63), (29, 64), (33, 65), (256, 70), (257, 130), (257, 132), (1000, 25), (16640, 64), (1000, 24), (700, 68)]
 

@@ -54,7 +54,7 @@ def test_text_training_plan_builds_on_the_host_with_short_slice_counts(tmp_path,
     from diffuscene_amd.flat import FlatStorage
     from diffuscene_amd.networks.denoise_net import Unet1D
     from diffuscene_amd.networks.diffusion_ddpm import DiffusionPoint
-    monkeypatch.setattr(ops, "_dev", lambda t, name=None: t)
+    monkeypatch.setattr(ops, "_dev", lambda t, name=None, dtype=None: t)      # (the helper's own signature: the records check dtypes too)
     chosen = []
     real = train_plan.tn_token_slices
 

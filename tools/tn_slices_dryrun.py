@@ -13,7 +13,7 @@ from diffuscene_amd._lib import SS_PER_SLOT, SS_PER_TOKEN
 from diffuscene_amd.flat import FlatStorage
 from diffuscene_amd.networks.denoise_net import Unet1D
 from diffuscene_amd.networks.diffusion_ddpm import DiffusionPoint
-ops._dev = lambda t, name=None: t
+ops._dev = lambda t, name=None, dtype=None: t
 real = train_plan.tn_token_slices
 def old_rule(groups, tile_n, target):
     m_max = max(m for m, _, _ in groups)
