@@ -21,7 +21,8 @@ each a generator of states (x_T, then the state after every step), and two indep
   the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine)
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
 part -- and then numbers its own draws: main stream x_T = 0, 1, 2, ..., given stream 0, 1, 2, ... (scene_noise.py).
-The fourteen public loops validate, hand over to the captured loop under _use_graph, build the two objects and run a core: nothing given --
+The public loops state their spec -- strided (S, eta) or not, the given part, the guidance scale -- and GaussianDiffusion._loop does the
+rest once: validates, hands over to the captured loop under _use_graph, builds the two objects and runs a core: nothing given --
 p_sample_loop, _trajectory, _arrange / ddim_sample_loop, ddim_arrange_loop (both arrange loops on the sub-shape); guided --
 p_sample_loop_guided / ddim_guided_loop; rows -- p_sample_loop_complete, _complete_ragged / ddim_complete_ragged_loop; mask --
 p_sample_loop_masked / ddim_masked_loop; mask and guided -- p_sample_loop_masked_guided / ddim_masked_guided_loop.
@@ -459,15 +460,59 @@ class GaussianDiffusion:
     def p_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                       clip_denoised=True, keep_running=False, graph=None):
         """Generate samples, reference :355-371 (draw order: x_T, then one draw per step)."""
+        return self._loop("p_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          clip_denoised=clip_denoised, keep_running=keep_running)
+
+    def _loop(self, what, denoise_fn, shape, device, condition, condition_cross, noise_fn, graph, strided=None, given=None, scale=None,
+              clip_denoised=True, keep_running=False, say_last=False, all_states=False):
+        """What every public loop does behind its signature.  The spec: ``strided`` = (sampling_timesteps, ddim_sampling_eta) or None for
+        T steps; ``given`` = None, ("dense", partial_boxes), ("ragged", partial_boxes, num_partial) or ("mask", known, mask); ``scale`` =
+        the guidance scale or None.  Validates (ValueError names ``what``), keeps (eta, S) on the instance as the reference does (:404-405),
+        hands over to the captured loop under _use_graph -- the front end front_end_name(spec) of sampler.py, looked up when called -- and
+        otherwise runs the eager core on the given part and the model call of the spec.  ``say_last``: the reference's print, after the
+        eager loop / before the captured one; ``all_states``: the list of states (eager)."""
         assert isinstance(shape, (tuple, list))
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_sample_loop
-            return graph_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross,
-                                     clip_denoised, self._total_steps(keep_running), noise_fn)
-        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised,
-                                     self._total_steps(keep_running)), shape)
-        assert img_t.shape == shape
-        return img_t
+        if strided is not None:
+            S, eta = _check_ddim(self.num_timesteps, *strided)
+        kind, values = (None, ()) if given is None else (given[0], given[1:])
+        if kind == "dense":
+            values = (values[0].contiguous(),)
+        elif kind == "ragged":
+            values = self._ragged_inputs(shape, device, *values, what)
+        elif kind == "mask":
+            values = self._masked_inputs(shape, device, *values, what)
+        if scale is not None:
+            condition, condition_cross, scale = self._guided_inputs(shape, device, condition, condition_cross, scale, what)
+        if strided is not None:
+            self.ddim_sampling_eta, self.sampling_timesteps = eta, S
+            sched = (S, eta)
+        else:
+            sched = (clip_denoised, self._total_steps(keep_running))
+        if not all_states and _use_graph(graph, noise_fn, denoise_fn):
+            from .. import sampler
+            if say_last:
+                self._say_last()
+            front = getattr(sampler, front_end_name(strided is not None, kind, scale is not None))
+            return front(self, denoise_fn, tuple(shape), device, condition, condition_cross, *(() if scale is None else (scale,)), *sched,
+                         noise_fn, *values)
+        model = _model(denoise_fn, condition, condition_cross) if scale is None else _guided_model(denoise_fn, condition, condition_cross, scale)
+        part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
+            self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
+        if strided is not None:
+            states = self._strided_states(model, shape, device, noise_fn, S, eta, part)
+        elif scale is not None and kind is None:        # p_sample_loop_guided: the device check before the first draw, its own draw keywords
+            self.tables(device)
+            states = self._t_states(model, shape, device, noise_fn, *sched, part, draw=dict(size=shape, dtype=torch.float, device=device))
+        else:
+            states = self._t_states(model, shape, device, noise_fn, *sched, part)
+        if all_states:
+            imgs = list(states)
+            assert imgs[-1].shape == tuple(shape)
+            return imgs
+        img = _last(states, shape)
+        if say_last:
+            self._say_last()
+        return img
 
     def p_sample_loop_trajectory(self, denoise_fn, shape, device, freq, condition, condition_cross,
                                  noise_fn=torch.randn, clip_denoised=True, keep_running=False):
@@ -539,15 +584,8 @@ class GaussianDiffusion:
         x_start is always clamped to [-1, 1], as in the reference, whatever ``clip_denoised`` says.  The network runs on the static
         plan, each update is one HIP kernel (dsc_ddim_step_f32); by default (``graph=None``, the rules of p_sample_loop) the loop is a
         replayed hipGraph step.  ``return_all_timesteps=True`` returns the S + 1 states (eager loop)."""
-        assert isinstance(shape, (tuple, list))
-        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        self.ddim_sampling_eta, self.sampling_timesteps = eta, S          # the reference keeps both on the instance (:404-405)
-        if not return_all_timesteps and _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_ddim_sample_loop
-            return graph_ddim_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn)
-        imgs = list(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta))
-        assert imgs[-1].shape == tuple(shape)
-        return imgs if return_all_timesteps else imgs[-1]
+        return self._loop("ddim_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          strided=(sampling_timesteps, ddim_sampling_eta), all_states=return_all_timesteps)
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
@@ -577,15 +615,8 @@ class GaussianDiffusion:
         p_sample_loop at batch B, in its order; both halves of the 2 B model call see the same x_t.  This eager loop is built from the
         unfused pieces -- the denoiser at 2 B, cfg_combine, p_sample; the graph path (the default, by the rules of p_sample_loop)
         replays one captured step whose update is the fused dsc_p_sample_cfg_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "p_sample_loop_guided")
-        total_steps = self._total_steps(keep_running)
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_guided_loop
-            return graph_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, clip_denoised, total_steps, noise_fn)
-        self.tables(device)                     # the device check, before the first draw
-        return _last(self._t_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, clip_denoised, total_steps,
-                                    draw=dict(size=shape, dtype=torch.float, device=device)), shape)
+        return self._loop("p_sample_loop_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running)
 
     @torch.no_grad()
     def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
@@ -595,33 +626,16 @@ class GaussianDiffusion:
         Draws: exactly those of ddim_sample_loop at batch B (x_T, then one per pair except the last).  The eager loop is built from the
         unfused pieces (the denoiser at 2 B, cfg_combine, ddim_step); the graph path replays one captured step whose update is the fused
         dsc_ddim_cfg_step_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "ddim_guided_loop")
-        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_ddim_guided_loop
-            return graph_ddim_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, S, eta, noise_fn)
-        return _last(self._strided_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, S, eta), shape)
+        return self._loop("ddim_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          strided=(sampling_timesteps, ddim_sampling_eta), scale=guidance_scale)
 
     # ------------------------------------------------------------------ completion, in-painting, re-arrangement
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
         model call) and overwrites the first P rows of x_t in place; at t == 0 the clean objects are restored."""
-        assert isinstance(shape, (tuple, list))
-        partial_boxes = partial_boxes.contiguous()
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_sample_loop
-            self._say_last()
-            return graph_sample_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised,
-                                     self._total_steps(keep_running), noise_fn, partial_boxes=partial_boxes)
-        given = _GivenRows(self, device, noise_fn, partial_boxes)
-        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised,
-                                     self._total_steps(keep_running), given), shape)
-        self._say_last()
-        assert img_t.shape == shape
-        return img_t
+        return self._loop("p_sample_loop_complete", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          given=("dense", partial_boxes), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True)
 
     @torch.no_grad()
     def p_sample_loop_complete_ragged(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
@@ -633,19 +647,8 @@ class GaussianDiffusion:
         then per step noise_fn(size=(B, Pmax, C)) (rows at or beyond the count are ignored) followed by noise_fn(size=(B, N, C)).
         This eager loop is built from the unfused pieces -- ragged overwrite, p_sample, restore; the graph path (the default, by the
         rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        partial_boxes, counts = self._ragged_inputs(shape, device, partial_boxes, num_partial, "p_sample_loop_complete_ragged")
-        total_steps = self._total_steps(keep_running)
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_complete_ragged_loop
-            self._say_last()
-            return graph_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised,
-                                              total_steps, noise_fn, partial_boxes, counts)
-        given = _GivenRagged(self, device, noise_fn, partial_boxes, counts)
-        img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised, total_steps,
-                                     given), shape)
-        self._say_last()
-        return img_t
+        return self._loop("p_sample_loop_complete_ragged", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          given=("ragged", partial_boxes, num_partial), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True)
 
     @torch.no_grad()
     def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
@@ -663,16 +666,8 @@ class GaussianDiffusion:
         This eager loop is built from the unfused pieces -- ragged overwrite at the pair's t, model call, ddim_step, ddim_advance,
         restore; the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
         dsc_ddim_inpaint_step_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        partial_boxes, counts = self._ragged_inputs(shape, device, partial_boxes, num_partial, "ddim_complete_ragged_loop")
-        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_ddim_complete_ragged_loop
-            return graph_ddim_complete_ragged_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn,
-                                                   partial_boxes, counts)
-        return _last(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta,
-                                          _GivenRagged(self, device, noise_fn, partial_boxes, counts)), shape)
+        return self._loop("ddim_complete_ragged_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial))
 
     def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
         """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
@@ -704,16 +699,8 @@ class GaussianDiffusion:
         returns, bit for bit under the same seed.  An all-zero mask is plain generation on the main draws, an all-ones mask returns
         ``known``.  This eager loop is built from the unfused pieces -- masked overwrite, p_sample, select; the graph path (the default,
         by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        known, mask = self._masked_inputs(shape, device, known, mask, "p_sample_loop_masked")
-        total_steps = self._total_steps(keep_running)
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_masked_loop
-            return graph_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, clip_denoised, total_steps,
-                                     noise_fn, known, mask)
-        given = _GivenMask(self, device, noise_fn, shape, known, mask)
-        return _last(self._t_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, clip_denoised, total_steps,
-                                    given), shape)
+        return self._loop("p_sample_loop_masked", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          given=("mask", known, mask), clip_denoised=clip_denoised, keep_running=keep_running)
 
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
@@ -725,15 +712,8 @@ class GaussianDiffusion:
         known-draw (B, N, C), the model call and a main draw (B, N, C), the last pair without the main draw: 2 S draws -- so a mask of
         whole rows [0, counts[b]) returns what that loop returns, bit for bit.  The eager loop is built from the unfused pieces; the
         graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        known, mask = self._masked_inputs(shape, device, known, mask, "ddim_masked_loop")
-        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_ddim_masked_loop
-            return graph_ddim_masked_loop(self, denoise_fn, tuple(shape), device, condition, condition_cross, S, eta, noise_fn, known, mask)
-        given = _GivenMask(self, device, noise_fn, shape, known, mask)
-        return _last(self._strided_states(_model(denoise_fn, condition, condition_cross), shape, device, noise_fn, S, eta, given), shape)
+        return self._loop("ddim_masked_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask))
 
     @torch.no_grad()
     def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
@@ -744,18 +724,8 @@ class GaussianDiffusion:
         order.  The eager loop is built from the unfused pieces -- masked overwrite, the denoiser at 2 B, cfg_combine, p_sample, select;
         the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
         dsc_p_sample_masked_cfg_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        known, mask = self._masked_inputs(shape, device, known, mask, "p_sample_loop_masked_guided")
-        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale,
-                                                   "p_sample_loop_masked_guided")
-        total_steps = self._total_steps(keep_running)
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_masked_guided_loop
-            return graph_masked_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, clip_denoised, total_steps,
-                                            noise_fn, known, mask)
-        given = _GivenMask(self, device, noise_fn, shape, known, mask)
-        return _last(self._t_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, clip_denoised, total_steps,
-                                    given), shape)
+        return self._loop("p_sample_loop_masked_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          given=("mask", known, mask), scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running)
 
     @torch.no_grad()
     def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
@@ -764,17 +734,8 @@ class GaussianDiffusion:
         p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
         ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
         step whose update is the fused dsc_ddim_masked_cfg_step_f32, bit-identical."""
-        assert isinstance(shape, (tuple, list))
-        S, eta = _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
-        known, mask = self._masked_inputs(shape, device, known, mask, "ddim_masked_guided_loop")
-        cond2, cross2, scale = self._guided_inputs(shape, device, condition, condition_cross, guidance_scale, "ddim_masked_guided_loop")
-        self.ddim_sampling_eta, self.sampling_timesteps = eta, S
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_ddim_masked_guided_loop
-            return graph_ddim_masked_guided_loop(self, denoise_fn, tuple(shape), device, cond2, cross2, scale, S, eta, noise_fn, known,
-                                                 mask)
-        given = _GivenMask(self, device, noise_fn, shape, known, mask)
-        return _last(self._strided_states(_guided_model(denoise_fn, cond2, cross2, scale), shape, device, noise_fn, S, eta, given), shape)
+        return self._loop("ddim_masked_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale)
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
@@ -803,13 +764,8 @@ class GaussianDiffusion:
         """Re-arrangement, reference :478-506: diffuse [translation | angle] only, re-assemble at t == 0."""
         assert isinstance(shape, (tuple, list))
         sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
-        if _use_graph(graph, noise_fn, denoise_fn):
-            from ..sampler import graph_sample_loop
-            img_t = graph_sample_loop(self, denoise_fn, sub, device, condition, condition_cross, clip_denoised,
-                                      self._total_steps(keep_running), noise_fn)
-        else:
-            img_t = _last(self._t_states(_model(denoise_fn, condition, condition_cross), sub, device, noise_fn, clip_denoised,
-                                         self._total_steps(keep_running)), sub)
+        img_t = self._loop("p_sample_loop_arrange", denoise_fn, sub, device, condition, condition_cross, noise_fn, graph,
+                           clip_denoised=clip_denoised, keep_running=keep_running)
         self._say_last()
         img_t = self._arranged(img_t, input_boxes)
         assert img_t.shape == shape
@@ -917,6 +873,12 @@ def _check_ddim(num_timesteps, sampling_timesteps, ddim_sampling_eta):
     if not 0.0 <= eta <= 1.0:
         raise ValueError("ddim_sampling_eta must lie in [0, 1], got %r" % (ddim_sampling_eta,))
     return int(S), eta
+
+
+def front_end_name(strided, given, guided):
+    """The captured loop of a spec (GaussianDiffusion._loop), by its name in sampler.py; the dense prefix rides on the plain T-step loop."""
+    middle = {None: "", "dense": "", "ragged": "complete_ragged_", "mask": "masked_"}[given] + ("guided_" if guided else "")
+    return "graph_%s%sloop" % ("ddim_" if strided else "", middle or "sample_")
 
 
 def _use_graph(graph, noise_fn, denoise_fn=None):

@@ -405,12 +405,6 @@ def _opt(t, name=None):
     return (t if name is None else _c(t, name)).data_ptr()
 
 
-def _table_run(ca, cb, *tables):
-    """(the pointer run ca, cb, tables... of a step kernel, the rows they share).  The posterior steps pass (coef1, coef2, sigma), the
-    strided ones (sqrt_recip_ac, sqrt_recipm1_ac), the in-painting ones append (sqrt_ac, sqrt_1mac); ca / cb are absent for mean type x0."""
-    return (_opt(ca), _opt(cb)) + tuple(tb.data_ptr() for tb in tables), _table_rows(ca, cb, *tables)
-
-
 def _strided_run(step, times, times_next, coef):
     """(the pointer run step, times, times_next, coef rows 0..2 of a strided step kernel, S): the (1,) int64 device counter, the (S,)
     int64 pairs and the (3, S) fp32 rows [sqrt(alpha_next), c, sigma]."""
@@ -426,12 +420,9 @@ def _same_shape(what, x_t, *operands, out=None):
         raise RuntimeError("diffuscene_amd: %s operands of different shapes" % what)
 
 
-def _out_like(what, x_t, out, *operands):
-    """``out`` of a fused step, allocated when absent: it and every operand have x_t's shape, and it is contiguous."""
-    if out is None:
-        out = torch.empty_like(x_t)
-    _same_shape(what, x_t, *operands, out=out)
-    return out
+def _fresh(x_t, out):
+    """``out`` of a step, allocated when absent (step_rec checks it)."""
+    return torch.empty_like(x_t) if out is None else out
 
 
 def q_sample_rec(x0, noise, t, sqrt_ac, sqrt_1mac, xt, v=None):
@@ -448,15 +439,80 @@ def q_sample(x0, noise, t, sqrt_ac, sqrt_1mac, want_v=False):
     return (xt, v) if want_v else xt
 
 
-def p_sample(x_t, model_out, noise, t, ca, cb, coef1, coef2, sigma, mean_type, clip, out=None, x0_out=None):
-    _c(x_t, "x_t"); _c(model_out, "model_out"); _c(noise, "noise"); _dev(t, "t", torch.int64)
-    if out is None:
-        out = torch.empty_like(x_t)
+# The step family, one kernel template (csrc/diffusion.hip: step_kernel<STRIDED, GIVEN, GUIDED>): (strided, given, guided) -> (entry point,
+# its parameters in the order of include/diffuscene_hip.h without the stream).  given: None, "rows" (a ragged row prefix) or "mask";
+# guided completion -- (., "rows", True) -- has no instantiation and no key.
+_POST = "ca cb coef1 coef2 sigma"
+_STRIDED = "step times times_next sqrt_alpha_next c_noise sigma"
+_DDIM = "ca cb sqrt_recip_ac sqrt_recipm1_ac"
+_Q = "sqrt_ac sqrt_1mac"
+_GIVEN = {None: "", "rows": " partial noise_p counts", "mask": " known noise_k mask"}
+
+
+def _step_params(strided, given, guided):
+    return " ".join(("x_t model_out" + (" scale" if guided else "") + " noise" + _GIVEN[given],
+                     _STRIDED + " " + _DDIM if strided else "t " + _POST, _Q if given else "",
+                     "out" + (" x_dup" if guided else "") + ("" if given else " x0_out"),
+                     "mean_type" + ("" if strided else " clip"), "b n pmax c" if given == "rows" else "b inner",
+                     "S T" if strided else "T")).split()
+
+
+STEP_ENTRY = {key: ("dsc_%s_f32" % name, _step_params(*key)) for key, name in {
+    (False, None, False): "p_sample", (True, None, False): "ddim_step",
+    (False, "rows", False): "p_sample_inpaint", (True, "rows", False): "ddim_inpaint_step",
+    (False, "mask", False): "p_sample_masked", (True, "mask", False): "ddim_masked_step",
+    (False, None, True): "p_sample_cfg", (True, None, True): "ddim_cfg_step",
+    (False, "mask", True): "p_sample_masked_cfg", (True, "mask", True): "ddim_masked_cfg_step"}.items()}
+
+
+def step_rec(x_t, model_out, noise, out, mean_type, tables, t=None, clip=False, strided=None, rows=None, mask=None, q=(), scale=None,
+             x_dup=None, x0_out=None):
+    """The launch record of one reverse step, whichever of the ten it is.  The operand groups pick the entry point and STEP_ENTRY lays
+    them out:  the state ``x_t``, ``model_out``, ``noise`` and the outputs ``out``, ``x0_out``;  the time source -- ``t`` (B,) int64 with
+    ``tables`` = (ca, cb, coef1, coef2, sigma) and ``clip``, or ``strided`` = (step, times, times_next, coef) with ``tables`` = (ca, cb,
+    sqrt_recip_ac, sqrt_recipm1_ac);  the given part -- ``rows`` = (partial, noise_p, counts on the device) or ``mask`` = (known, noise_k,
+    mask), either with ``q`` = (sqrt_ac, sqrt_1mac);  guidance -- ``scale`` (B,) f32 under a ``model_out`` of 2 B scenes, and ``x_dup``.
+    The checks are the same for every entry point; ValueError for a combination that has no kernel."""
+    given = None if rows is None and mask is None else "rows" if mask is None else "mask" if rows is None else "rows and mask"
+    key = (strided is not None, given, scale is not None)
+    if key not in STEP_ENTRY:
+        raise ValueError("diffuscene_amd: no step kernel for strided=%s, given=%s, guided=%s" % key)
+    name, params = STEP_ENTRY[key]
+    what = name[4:-4]
+    for operand, o in (("x_dup", x_dup), ("x0_out", x0_out)):
+        if o is not None and operand not in params:
+            raise ValueError("diffuscene_amd: %s takes no %s" % (what, operand))
+    if len(tables) != (4 if strided is not None else 5) or len(q) != (2 if given else 0):
+        raise ValueError("diffuscene_amd: %s takes %s%s" % (what, _DDIM if strided is not None else _POST, " and " + _Q if given else ""))
+    _c(x_t, "x_t"); _c(model_out, "model_out"); _c(noise, "noise")
     b = x_t.shape[0]
-    post, rows = _table_run(ca, cb, coef1, coef2, sigma)
-    _lib.check(_lib.fn("dsc_p_sample_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), t.data_ptr(), *post, out.data_ptr(),
-                                           _opt(x0_out), mean_type, 1 if clip else 0, b, x_t.numel() // b, rows, stream_ptr()),
-               "dsc_p_sample_f32")
+    v = dict(x_t=x_t, model_out=model_out, noise=noise, out=out, x0_out=_opt(x0_out, "x0_out"), mean_type=mean_type,
+             clip=1 if clip else 0, b=b, inner=x_t.numel() // b, T=_table_rows(*tables, *q))
+    _same_shape(what, x_t, None if scale is not None else model_out, noise, x0_out, out=out)
+    v.update(zip((_DDIM if strided is not None else _POST).split() + _Q.split(), tuple(tables) + tuple(q)))
+    if strided is not None:
+        ptrs, v["S"] = _strided_run(*strided)
+        v.update(zip(_STRIDED.split(), ptrs))
+    else:
+        _scene_t(t, b)
+        v["t"] = t
+    if rows is not None:
+        _dev(rows[2], "counts", torch.int64)            # on the device already: a record never allocates (ops.ragged_counts uploads)
+        _, v["n"], v["pmax"], v["c"], _ = _ragged_args(x_t, *rows)
+        v.update(zip(("partial", "noise_p", "counts"), rows))
+    if mask is not None:
+        _masked_args(x_t, *mask)
+        v.update(zip(("known", "noise_k", "mask"), mask))
+    if scale is not None:
+        _cfg_args(x_t, model_out, scale)
+        v.update(scale=scale, x_dup=_cfg_dup(x_dup, x_t, out))
+    args = tuple(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in (v[p] for p in params))
+    return name, args, (x_t, model_out, noise, out, x0_out, tables, q, t, strided, rows, mask, scale, x_dup)
+
+
+def p_sample(x_t, model_out, noise, t, ca, cb, coef1, coef2, sigma, mean_type, clip, out=None, x0_out=None):
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, coef1, coef2, sigma), t=t, clip=clip, x0_out=x0_out))
     return out
 
 
@@ -470,15 +526,9 @@ def ddim_step(x_t, model_out, noise, step, times, times_next, coef, ca, cb, sqrt
               out=None, x0_out=None):
     """One DDIM step (see the C header).  ``step`` is the (1,) int64 device counter, ``times`` / ``times_next`` the (S,) int64 pairs and
     ``coef`` the (3, S) fp32 rows [sqrt(alpha_next), c, sigma]; ``noise`` is not read on the final pair (pass any tensor of x_t's shape)."""
-    _c(x_t, "x_t"); _c(model_out, "model_out"); _c(noise, "noise")
-    strided, S = _strided_run(step, times, times_next, coef)
-    _same_shape("ddim_step", x_t, model_out, noise)
-    if out is None:
-        out = torch.empty_like(x_t)
-    b = x_t.shape[0]
-    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac)
-    _lib.check(_lib.fn("dsc_ddim_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), *strided, *tabs, out.data_ptr(),
-                                            _opt(x0_out), mean_type, b, x_t.numel() // b, S, rows, stream_ptr()), "dsc_ddim_step_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, sqrt_recip_ac, sqrt_recipm1_ac),
+                   strided=(step, times, times_next, coef), x0_out=x0_out))
     return out
 
 
@@ -565,14 +615,9 @@ def p_sample_inpaint(x_t, model_out, noise, partial, noise_p, counts, t, ca, cb,
                      clip, out=None):
     """Fused step of the ragged completion loop: p_sample on rows >= counts[b]; the given rows get the re-noising of step t - 1
     (t > 0) or ``partial`` itself (t == 0).  See the C header."""
-    _c(model_out, "model_out"); _c(noise, "noise")
-    b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
-    _scene_t(t, b)
-    out = _out_like("p_sample_inpaint", x_t, out, model_out, noise)
-    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_p_sample_inpaint_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
-                                                   noise_p.data_ptr(), cnt.data_ptr(), t.data_ptr(), *post, out.data_ptr(), mean_type,
-                                                   1 if clip else 0, b, n, pmax, c, rows, stream_ptr()), "dsc_p_sample_inpaint_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, coef1, coef2, sigma), t=t, clip=clip,
+                   rows=(partial, noise_p, _ragged_args(x_t, partial, noise_p, counts)[4]), q=(sqrt_ac, sqrt_1mac)))
     return out
 
 
@@ -581,14 +626,9 @@ def ddim_inpaint_step(x_t, model_out, noise, partial, noise_p, counts, step, tim
     """Fused step of the strided (DDIM) ragged completion loop: ddim_step on rows >= counts[b]; the given rows get the re-noising at
     ``times_next[step]`` or, on the last pair, ``partial`` itself (``noise`` and ``noise_p`` are not read there).  Tables as ddim_step,
     counts / partial as p_sample_inpaint.  See the C header."""
-    _c(model_out, "model_out"); _c(noise, "noise")
-    b, n, pmax, c, cnt = _ragged_args(x_t, partial, noise_p, counts)
-    strided, S = _strided_run(step, times, times_next, coef)
-    out = _out_like("ddim_inpaint_step", x_t, out, model_out, noise)
-    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_ddim_inpaint_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), partial.data_ptr(),
-                                                    noise_p.data_ptr(), cnt.data_ptr(), *strided, *tabs, out.data_ptr(), mean_type,
-                                                    b, n, pmax, c, S, rows, stream_ptr()), "dsc_ddim_inpaint_step_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), strided=(step, times, times_next, coef),
+                   rows=(partial, noise_p, _ragged_args(x_t, partial, noise_p, counts)[4]), q=(sqrt_ac, sqrt_1mac)))
     return out
 
 
@@ -636,14 +676,9 @@ def p_sample_masked(x_t, model_out, noise, known, noise_k, mask, t, ca, cb, coef
                     out=None):
     """Fused step of the masked loop: p_sample on the free elements; the given ones get the re-noising of step t - 1 (t > 0) or
     ``known`` itself (t == 0; ``noise_k`` is not read there).  See the C header."""
-    _c(model_out, "model_out"); _c(noise, "noise")
-    b, inner = _masked_args(x_t, known, noise_k, mask)
-    _scene_t(t, b)
-    out = _out_like("p_sample_masked", x_t, out, model_out, noise)
-    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_p_sample_masked_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
-                                                  noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(), *post, out.data_ptr(), mean_type,
-                                                  1 if clip else 0, b, inner, rows, stream_ptr()), "dsc_p_sample_masked_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, coef1, coef2, sigma), t=t, clip=clip, mask=(known, noise_k, mask),
+                   q=(sqrt_ac, sqrt_1mac)))
     return out
 
 
@@ -652,14 +687,9 @@ def ddim_masked_step(x_t, model_out, noise, known, noise_k, mask, step, times, t
     """Fused step of the strided (DDIM) masked loop: ddim_step on the free elements; the given ones get the re-noising at
     ``times_next[step]`` or, on the last pair, ``known`` itself (``noise`` and ``noise_k`` are not read there).  Tables as ddim_step.
     See the C header."""
-    _c(model_out, "model_out"); _c(noise, "noise")
-    b, inner = _masked_args(x_t, known, noise_k, mask)
-    strided, S = _strided_run(step, times, times_next, coef)
-    out = _out_like("ddim_masked_step", x_t, out, model_out, noise)
-    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_ddim_masked_step_f32")(x_t.data_ptr(), model_out.data_ptr(), noise.data_ptr(), known.data_ptr(),
-                                                   noise_k.data_ptr(), mask.data_ptr(), *strided, *tabs, out.data_ptr(), mean_type,
-                                                   b, inner, S, rows, stream_ptr()), "dsc_ddim_masked_step_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), strided=(step, times, times_next, coef),
+                   mask=(known, noise_k, mask), q=(sqrt_ac, sqrt_1mac)))
     return out
 
 
@@ -805,15 +835,9 @@ def cfg_combine(model_out, scale, out=None):
 def p_sample_cfg(x_t, model_out, scale, noise, t, ca, cb, coef1, coef2, sigma, mean_type, clip, out=None, x_dup=None, x0_out=None):
     """p_sample on the guided model output, one launch: model_out (2 B, N, C) = [c; u], scale (B,) f32 (ops.guidance_scales); ``x_dup``
     receives a second copy of the result.  Bit-identical to cfg_combine followed by p_sample.  See the C header."""
-    _c(x_t, "x_t"); _c(noise, "noise")
-    b, inner = _cfg_args(x_t, model_out, scale)
-    _scene_t(t, b)
-    out = _out_like("p_sample_cfg", x_t, out, noise, x0_out)
-    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out), _opt(x0_out, "x0_out"))
-    post, rows = _table_run(ca, cb, coef1, coef2, sigma)
-    _lib.check(_lib.fn("dsc_p_sample_cfg_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(), t.data_ptr(),
-                                               *post, *extra, mean_type, 1 if clip else 0, b, inner, rows, stream_ptr()),
-               "dsc_p_sample_cfg_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, coef1, coef2, sigma), t=t, clip=clip, scale=scale, x_dup=x_dup,
+                   x0_out=x0_out))
     return out
 
 
@@ -821,14 +845,9 @@ def ddim_cfg_step(x_t, model_out, scale, noise, step, times, times_next, coef, c
                   out=None, x_dup=None, x0_out=None):
     """ddim_step on the guided model output, one launch; operands as p_sample_cfg, tables as ddim_step (``noise`` is not read on the
     final pair).  Bit-identical to cfg_combine followed by ddim_step.  See the C header."""
-    _c(x_t, "x_t"); _c(noise, "noise")
-    b, inner = _cfg_args(x_t, model_out, scale)
-    strided, S = _strided_run(step, times, times_next, coef)
-    out = _out_like("ddim_cfg_step", x_t, out, noise, x0_out)
-    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out), _opt(x0_out, "x0_out"))
-    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac)
-    _lib.check(_lib.fn("dsc_ddim_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(), *strided, *tabs,
-                                                *extra, mean_type, b, inner, S, rows, stream_ptr()), "dsc_ddim_cfg_step_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), strided=(step, times, times_next, coef),
+                   scale=scale, x_dup=x_dup, x0_out=x0_out))
     return out
 
 
@@ -837,17 +856,9 @@ def p_sample_masked_cfg(x_t, model_out, scale, noise, known, noise_k, mask, t, c
     """p_sample_masked on the guided model output, one launch: model_out (2 B, N, C) = [c; u], scale (B,) f32; known / noise_k / mask
     are (B, N, C); ``x_dup`` receives a second copy of every written element.  Bit-identical to cfg_combine followed by
     p_sample_masked.  See the C header."""
-    _c(noise, "noise")
-    b, inner = _masked_args(x_t, known, noise_k, mask)
-    _cfg_args(x_t, model_out, scale)
-    _scene_t(t, b)
-    out = _out_like("p_sample_masked_cfg", x_t, out, noise)
-    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out))
-    post, rows = _table_run(ca, cb, coef1, coef2, sigma, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_p_sample_masked_cfg_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
-                                                      known.data_ptr(), noise_k.data_ptr(), mask.data_ptr(), t.data_ptr(), *post,
-                                                      *extra, mean_type, 1 if clip else 0, b, inner, rows, stream_ptr()),
-               "dsc_p_sample_masked_cfg_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, coef1, coef2, sigma), t=t, clip=clip, mask=(known, noise_k, mask),
+                   q=(sqrt_ac, sqrt_1mac), scale=scale, x_dup=x_dup))
     return out
 
 
@@ -855,16 +866,9 @@ def ddim_masked_cfg_step(x_t, model_out, scale, noise, known, noise_k, mask, ste
                          sqrt_recipm1_ac, sqrt_ac, sqrt_1mac, mean_type, out=None, x_dup=None):
     """ddim_masked_step on the guided model output, one launch; operands as p_sample_masked_cfg, tables as ddim_masked_step (``noise``
     and ``noise_k`` are not read on the final pair).  Bit-identical to cfg_combine followed by ddim_masked_step.  See the C header."""
-    _c(noise, "noise")
-    b, inner = _masked_args(x_t, known, noise_k, mask)
-    _cfg_args(x_t, model_out, scale)
-    strided, S = _strided_run(step, times, times_next, coef)
-    out = _out_like("ddim_masked_cfg_step", x_t, out, noise)
-    extra = (out.data_ptr(), _cfg_dup(x_dup, x_t, out))
-    tabs, rows = _table_run(ca, cb, sqrt_recip_ac, sqrt_recipm1_ac, sqrt_ac, sqrt_1mac)
-    _lib.check(_lib.fn("dsc_ddim_masked_cfg_step_f32")(x_t.data_ptr(), model_out.data_ptr(), scale.data_ptr(), noise.data_ptr(),
-                                                       known.data_ptr(), noise_k.data_ptr(), mask.data_ptr(), *strided, *tabs, *extra,
-                                                       mean_type, b, inner, S, rows, stream_ptr()), "dsc_ddim_masked_cfg_step_f32")
+    out = _fresh(x_t, out)
+    issue(step_rec(x_t, model_out, noise, out, mean_type, (ca, cb, sqrt_recip_ac, sqrt_recipm1_ac), strided=(step, times, times_next, coef),
+                   mask=(known, noise_k, mask), q=(sqrt_ac, sqrt_1mac), scale=scale, x_dup=x_dup))
     return out
 
 

@@ -11,22 +11,31 @@ Structure:
   _LoopGraph      the core: launch plans, the state (x, t), the main noise stream, the model call, warm-up + capture that costs the
                   caller no random numbers (``graph``: a step that is followed by another, ``final``: the last one where it differs),
                   the stale-pointer check and the replays.
-  _PosteriorLoop  the T-step layer: t counts down by a kernel in the graph; T + 1 main draws (x_T, then one per step, also at t == 0).
-  _DDIMLoop       the strided layer (ddim_sample_loop, :402-444): a device step counter and per-pair tables (t, t_next, coefficients)
-                  owned here and refreshed in place, the advance kernel; S main draws (none on the last pair).  S == 1: no ``graph``.
-  _Ragged, _Masked   the given part of a scene (a row prefix with per-scene counts / a byte mask) in graph-owned buffers, its own
-                  noise stream, shifted by one: draw 0 feeds a standalone overwrite in ``run``, the fused step re-noises for the NEXT
-                  model call, the last step restores -- so a given element costs no posterior step and the draw order stays the eager one.
-What the ten classes add:
-  _StepGraph (p_sample_loop, _complete)     optional sub-batch chains (_chains_for), optional dense overwrite before the model call
-  _DDIMGraph (ddim_sample_loop, strided re-arrangement on the sub-shape)             dsc_ddim_step_f32
-  _RaggedCompleteGraph / _DDIMCompleteGraph  _Ragged + dsc_p_sample_inpaint_f32 / dsc_ddim_inpaint_step_f32; fused=False: unfused kernels
-  _MaskedGraph / _DDIMMaskedGraph            _Masked + dsc_p_sample_masked_f32 / dsc_ddim_masked_step_f32
-  _GuidedStepGraph / _DDIMGuidedGraph        a plan at 2 B (text features | zeros), x kept in both halves of one (2 B, N, C) buffer,
-                                             per-scene scales in a buffer, dsc_p_sample_cfg_f32 / dsc_ddim_cfg_step_f32; fused=False
-  _MaskedGuidedGraph / _DDIMMaskedGuidedGraph   _Masked + _Guided: known, mask and the known-draws at B under a plan at 2 B,
-                                             dsc_p_sample_masked_cfg_f32 / dsc_ddim_masked_cfg_step_f32; fused=False
-The graph_*_loop functions are the front ends behind diffusion_ddpm.py: one cached graph per diffusion object (_cached_loop).
+A loop is three orthogonal parts, the axes of the one step kernel (csrc/diffusion.hip: step_kernel<STRIDED, GIVEN, GUIDED>):
+  the schedule    _PosteriorLoop: T steps, t counts down by a kernel in the graph, T + 1 main draws (x_T, then one per step, also at
+                  t == 0), ``final`` only beside a fused given part.  _DDIMLoop (ddim_sample_loop, :402-444): a device step counter and
+                  per-pair tables (t, t_next, coefficients) owned here and refreshed in place, the advance kernel, S main draws (none on
+                  the last pair), always ``final``, ``graph`` when S > 1.  Each holds the time operands of the step (``sched``), the
+                  in-graph move, _start / _park and what ``run`` does before and after the replays.
+  the given part  _Given (nothing), _Dense (the prefix of p_sample_loop_complete, never fused), _Ragged (a row prefix with per-scene
+                  counts), _Masked (a byte mask): graph-owned buffers refreshed in place, its own noise stream -- shifted by one when
+                  fused: draw 0 feeds a standalone overwrite in ``run``, the fused step re-noises for the NEXT model call, the last step
+                  restores, so a given element costs no posterior step and the draw order stays the eager one --, the operands it adds
+                  to the step, the unfused overwrite and restore.
+  guidance        _Guidance: a plan at 2 B (text features | zeros), x kept in both halves of one (2 B, N, C) buffer (x_dup), the
+                  per-scene scales in a buffer, ``m`` when unfused.
+_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, main draw, given draw unless final, [cfg_combine,] ONE update launch
+laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
+The ten classes are rows:                    schedule   given            guided   fused=False unfuses
+  _StepGraph                                 T steps    - / _Dense       -        (sub-batch chains: _chains_for, this row only)
+  _DDIMGraph                                 strided    -                -
+  _RaggedCompleteGraph / _DDIMCompleteGraph  T / str.   _Ragged          -        the overwrite
+  _MaskedGraph / _DDIMMaskedGraph            T / str.   _Masked          -
+  _GuidedStepGraph / _DDIMGuidedGraph        T / str.   -                yes      the guidance
+  _MaskedGuidedGraph / _DDIMMaskedGuidedGraph  T / str. _Masked (at B)   yes      the guidance
+and the graph_*_loop front ends behind diffusion_ddpm.py are one _front_end over a row: one cached graph per diffusion object
+(_cached_loop).  A new loop is a new row: a class line, a front-end line, a key in ops.STEP_ENTRY if it needs a kernel instantiation of
+its own, and a spec in a public method of GaussianDiffusion.
 """
 import torch
 
@@ -263,36 +272,57 @@ class _LoopGraph:
 
 
 class _PosteriorLoop(_LoopGraph):
-    """The T-step layer: ``post`` / ``tail`` are the argument runs of ops.p_sample*, the graph decrements t."""
+    """The T-step schedule: ``sched`` is the time source of ops.step_rec, the graph decrements t; T + 1 main draws.  ``final`` exists only
+    beside a fused given part (the last step restores instead of re-noising): without one the step at t == 0 is ``graph`` too."""
+    strided = False
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay, mult=1, nch=1):
         super().__init__(diff, model, shape, device, condition, condition_cross, replay, diff.num_timesteps + 1, mult, nch)
-        self.T = diff.num_timesteps
+        self.T = self.given_draws = diff.num_timesteps
         tb = self.tb
-        self.post = (self.ca, self.cb, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], diff._sigma(tb))
-        self.tail = (self.mean_type, clip_denoised)
+        self.sched = dict(t=self.t[:shape[0]], clip=clip_denoised,
+                          tables=(self.ca, self.cb, tb["posterior_mean_coef1"], tb["posterior_mean_coef2"], diff._sigma(tb)))
+
+    def _kinds(self, fused_given):
+        return [False, True] if fused_given else [False]
 
     def _capture(self, kinds):
         self.t.fill_(1)
         super()._capture(kinds)
 
+    def _main_draw(self, final):
+        return self.noise()                     # at t == 0 too
+
+    def _move(self):
+        ops.add_scalar_i64(self.t, -1)
+
+    def _begin(self, total_steps):
+        """-> (the first timestep, the steps of this run)."""
+        self.check_current()
+        return total_steps - 1, total_steps
+
+    _end = _LoopGraph._park                     # t holds -1 after the loop
+
 
 class _DDIMLoop(_LoopGraph):
-    """The strided layer.  The step counter and the per-pair tables (t, t_next; sqrt(alpha_next), c, sigma) are captured by pointer:
+    """The strided schedule.  The step counter and the per-pair tables (t, t_next; sqrt(alpha_next), c, sigma) are captured by pointer:
     this object owns them and ``_load_tables`` refreshes them IN PLACE (eta is not part of the cache key), so a live graph never
     points at a freed table.  ``graph`` (S > 1 only) ends with the advance kernel (step += 1, t = times[step]) and is replayed S - 1
-    times; ``final`` is the draw-free last pair ((t, -1) -> x_start), from a fresh pool when S == 1."""
+    times; ``final`` is the draw-free last pair ((t, -1) -> x_start), from a fresh pool when S == 1.  S main draws."""
+    strided = True
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay, mult=1):
         super().__init__(diff, model, shape, device, condition, condition_cross, replay, S, mult)
-        self.S = S
-        self.kinds = ([False] if S > 1 else []) + [True]
+        self.S = self.given_draws = S
         self.step = torch.zeros((1,), device=device, dtype=torch.int64)
         self.times = torch.zeros((S,), device=device, dtype=torch.int64)
         self.times_next = torch.zeros((S,), device=device, dtype=torch.int64)
         self.coef = torch.zeros((3, S), device=device, dtype=torch.float32)
-        self.tabs = (self.step, self.times, self.times_next, self.coef)                     # the argument runs of ops.ddim_*step
-        self.ddim = (self.ca, self.cb, self.tb["sqrt_recip_alphas_cumprod"], self.tb["sqrt_recipm1_alphas_cumprod"])
+        self.sched = dict(strided=(self.step, self.times, self.times_next, self.coef),
+                          tables=(self.ca, self.cb, self.tb["sqrt_recip_alphas_cumprod"], self.tb["sqrt_recipm1_alphas_cumprod"]))
+
+    def _kinds(self, fused_given):
+        return ([False] if self.S > 1 else []) + [True]
 
     def _park(self):
         super()._park()
@@ -306,81 +336,172 @@ class _DDIMLoop(_LoopGraph):
     def _copy_rows(self, dst, src):
         dst.copy_(src[:self.S])                 # the buffers hold exactly S rows
 
-    def _advance(self, final):
-        if not final:
-            ops.ddim_advance(self.step, self.times, self.t)
+    def _main_draw(self, final):
+        return self.x if final else self.noise()                # not read on the last pair
 
-    def _load_tables(self, dtab):
-        """-> the first timestep."""
+    def _move(self):
+        ops.ddim_advance(self.step, self.times, self.t)
+
+    def _begin(self, dtab):
+        """The tables of this run into the graph's own -> (the first timestep, S)."""
         pairs, times, times_next, coef = dtab
         assert len(pairs) == self.S
         self.check_current()
         self.times.copy_(times)                 # in place: the graphs hold these pointers
         self.times_next.copy_(times_next)
         self.coef.copy_(coef)
-        return pairs[0][0]
+        return pairs[0][0], self.S
+
+    def _end(self):
+        pass
 
 
-class _Ragged:
-    """Given objects as a row prefix: the padded objects (B, Pmax, C) and the (B,) int64 counts (ops.ragged_counts) live in buffers of
-    the graph, captured by pointer and refreshed in place -- one graph serves every mix of counts -- with their own noise stream.
-    ``fused=False`` is the comparison of tools/bench_complete.py / bench_ddim_complete.py: every step begins with the unfused overwrite."""
+class _Given:
+    """The given part of a loop, here: nothing is given.  A part keeps what is given in buffers of the graph, captured by pointer and
+    refreshed in place by ``load`` -- one graph serves every value -- and has its own noise stream ``noise``.  ``fused``: the step
+    kernel handles the part -- the stream is shifted by one: draw 0 feeds the standalone overwrite ``first`` in ``run``, the step re-noises
+    for the NEXT model call (``operands``: what the part adds to ops.step_rec), the last step restores -- so a given element costs no
+    posterior step and the draw order stays the eager one.  Not fused: ``before`` draws and overwrites in front of every model call,
+    ``restore`` puts the clean values into the result.  ``values``: what ``load`` takes, by the names of the front end.
+    Every method is handed the loop ``g`` and no part keeps it: a reference cycle would leave a replaced graph to the cyclic collector,
+    which can run inside a later capture -- and destroying a hipGraph there aborts the process."""
+    values, fused, noise = (), False, None
 
-    def _init_given(self, pmax, rows, fused):          # _Masked._init_given takes ``rows`` alone, on purpose: a class uses one of the two
-        B, N, C = self.shape
-        self.pmax, self.fused = pmax, fused
-        self.partial = torch.zeros((B, pmax, C), device=self.device, dtype=torch.float32)
-        self.counts = torch.zeros((B,), device=self.device, dtype=torch.int64)
-        self.pnoise = self._stream((B, pmax, C), rows, GIVEN)
+    def __init__(self, g, shape):
+        pass
 
-    def _overwrite(self, pn):
-        ops.complete_overwrite_ragged(self.x, self.partial, pn, self.counts, self.t, *self.q)
+    def load(self, g):
+        pass
 
-    def _begin_given(self, partial, counts, noise_buffer, partial_noise):
-        self.partial.copy_(partial)             # in place: the graphs hold these pointers
+    def first(self, g):
+        pass
+
+    def before(self, g):
+        pass
+
+    def operands(self, g, final):
+        return {}
+
+    def restore(self, g, out):
+        return out
+
+
+class _Dense(_Given):
+    """p_sample_loop_complete (:461-466): the first P rows of every scene, re-noised and written over x_t BEFORE the model call at every
+    step.  Never fused; the front end restores the clean objects."""
+    values = ("partial_boxes",)
+
+    def __init__(self, g, shape):
+        self.partial = torch.zeros(shape, device=g.device)
+        self.noise = g._stream(shape, g.given_draws, GIVEN)
+
+    def load(self, g, partial):
+        self.partial.copy_(partial)
+
+    def before(self, g):
+        ops.complete_overwrite(g.x, self.partial, self.noise(), g.t, *g.q)
+
+
+class _Ragged(_Given):
+    """Given objects as a row prefix: the padded objects (B, Pmax, C) and the (B,) int64 counts (ops.ragged_counts).  ``fused=False`` is
+    the comparison of tools/bench_complete.py / bench_ddim_complete.py: every step begins with the unfused overwrite."""
+    values = ("partial_boxes", "counts")
+
+    def __init__(self, g, shape, fused=True):
+        self.fused = fused
+        self.partial = torch.zeros(shape, device=g.device, dtype=torch.float32)
+        self.counts = torch.zeros((shape[0],), device=g.device, dtype=torch.int64)
+        self.noise = g._stream(shape, g.given_draws, GIVEN)
+
+    def load(self, g, partial, counts):
+        self.partial.copy_(partial)
         self.counts.copy_(counts)
-        self._upload((self.noise, noise_buffer, 1), (self.pnoise, partial_noise, 1 if self.fused else 0))
-        if self.fused:
-            self._overwrite(self.pnoise.head())
 
-    def _restore(self, out):
+    def _overwrite(self, g, pn):
+        ops.complete_overwrite_ragged(g.x, self.partial, pn, self.counts, g.t, *g.q)
+
+    def first(self, g):
+        if self.fused:
+            self._overwrite(g, self.noise.head())
+
+    def before(self, g):
+        if not self.fused:
+            self._overwrite(g, self.noise())
+
+    def operands(self, g, final):                  # the partial draw is not read after the last step
+        return dict(rows=(self.partial, self.partial if final else self.noise(), self.counts), q=g.q) if self.fused else {}
+
+    def restore(self, g, out):
         return out if self.fused else restore_given_rows(out, self.partial, self.counts)
 
 
-class _Masked:
-    """Given elements as a byte mask: ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 (ops.known_mask) live in buffers of the
-    graph, captured by pointer and refreshed in place -- one graph per shape serves every mask -- with full-shape known-draws."""
+class _Masked(_Given):
+    """Given elements as a byte mask: ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 (ops.known_mask), with full-shape known-draws;
+    under guidance all three stay at B.  Always fused."""
+    values, fused = ("known", "mask"), True
 
-    def _init_given(self, rows):
-        self.known = torch.zeros(self.shape, device=self.device, dtype=torch.float32)
-        self.mask = torch.zeros(self.shape, device=self.device, dtype=torch.uint8)
-        self.knoise = self._stream(self.shape, rows, GIVEN)
+    def __init__(self, g, shape):
+        self.known = torch.zeros(g.shape, device=g.device, dtype=torch.float32)
+        self.mask = torch.zeros(g.shape, device=g.device, dtype=torch.uint8)
+        self.noise = g._stream(g.shape, g.given_draws, GIVEN)
 
-    def _begin_given(self, known, mask, noise_buffer, known_noise):
-        self.known.copy_(known)                 # in place: the graphs hold these pointers
+    def load(self, g, known, mask):
+        self.known.copy_(known)
         self.mask.copy_(mask)
-        self._upload((self.noise, noise_buffer, 1), (self.knoise, known_noise, 1))
-        ops.masked_overwrite(self.x, self.known, self.knoise.head(), self.mask, self.t[:self.shape[0]], *self.q)
-        if self.x_null is not None:             # guided: both halves of the state stay current
-            self.x_null.copy_(self.x)
+
+    def first(self, g):
+        ops.masked_overwrite(g.x, self.known, self.noise.head(), self.mask, g.t[:g.shape[0]], *g.q)
+
+    def operands(self, g, final):                  # the known-draw is not read after the last step
+        return dict(mask=(self.known, self.known if final else self.noise(), self.mask), q=g.q)
 
 
-class _StepGraph(_PosteriorLoop):
-    """p_sample_loop: model call, draw, dsc_p_sample_f32, decrement; no ``final`` (the draw is made at t == 0 too).  With
-    ``partial_shape`` p_sample_loop_complete (:461-466): the given objects are re-noised and written over the first P rows of x_t at
-    every step, BEFORE the model call."""
+class _Guidance:
+    """Classifier-free guidance: the plan runs at 2 B (``mult`` = 2) -- rows [0, B) fed the text features, rows [B, 2 B) zeros -- on the
+    same x and t in both halves; the fused kernels read both halves of the plan's output and write the new x to BOTH halves of ``x2``
+    (their x_dup pointer).  The (B,) scale vector (ops.guidance_scales) is a buffer of the graph, captured by pointer and refreshed in
+    place: one graph serves every per-scene mix of scales.  ``fused=False`` is the comparison of tools/bench_cfg.py /
+    bench_guided_inpaint.py: cfg_combine into ``m``, the unguided step kernel, a copy into the null half."""
 
-    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False,
-                 partial_shape=None):
-        nch = _chains_for(shape[0])
-        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay, nch=nch)
-        self.side = [torch.cuda.Stream(device=device) for _ in range(nch - 1)]
-        self.model_out = torch.empty(shape, device=device, dtype=torch.float32) if nch > 1 else None
-        self.partial = torch.zeros(partial_shape, device=device) if partial_shape is not None else None
-        self.pnoise = self._stream(partial_shape, self.T, GIVEN) if partial_shape is not None else None
-        self._capture([False])
+    def __init__(self, g, fused):
+        self.fused = fused
+        self.scale = torch.ones((g.shape[0],), device=g.device, dtype=torch.float32)
+        self.m = None if fused else torch.empty(g.shape, device=g.device, dtype=torch.float32)
+
+    def apply(self, g, mo):
+        """-> (the model output of the step, what guidance adds to ops.step_rec)."""
+        if self.fused:
+            return mo, dict(scale=self.scale, x_dup=g.x_null)
+        return ops.cfg_combine(mo, self.scale, out=self.m), {}
+
+    def after(self, g):
+        if not self.fused:
+            g.x_null.copy_(g.x)
+
+
+class _Loop:
+    """One captured loop = a schedule (_PosteriorLoop or _DDIMLoop, by inheritance), a given part and guidance: the row a class below
+    declares.  ``sched``: clip_denoised of a T-step loop, S of a strided one.  ``fused`` unfuses what the row has a kernel for: the
+    overwrite of a ragged part, the guidance of a guided row.  ``partial_shape``: the shape of the given rows."""
+    given, guided, chains, what = _Given, False, False, None
+
+    def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None):
+        nch = (_chains_for(shape[0]),) if self.chains else ()
+        super().__init__(diff, model, shape, device, condition, condition_cross, sched, replay, 2 if self.guided else 1, *nch)
+        self.fused = fused
+        self.side = [torch.cuda.Stream(device=device) for _ in range(len(self.plans) - 1)]
+        self.model_out = torch.empty(shape, device=device, dtype=torch.float32) if self.side else None
+        part = self.given if self.given is not _Dense or partial_shape is not None else _Given
+        self.part = part(self, partial_shape, fused) if part is _Ragged else part(self, partial_shape)
+        self.guide = _Guidance(self, fused) if self.guided else None
+        for owner in (self.part, self.guide):   # the buffers, by the names tests, tools and bench.py read
+            for name in ("partial", "counts", "known", "mask", "scale", "m"):
+                if hasattr(owner, name):
+                    setattr(self, name, getattr(owner, name))
+        self._capture(self._kinds(self.part.fused))
 
     def _model_call(self):
+        """One plan, or the sub-batch chains of _chains_for: chain 0 on the current stream, the others on side streams."""
         nch = len(self.plans)
         if nch == 1:
             return super()._model_call()
@@ -407,291 +528,78 @@ class _StepGraph(_PosteriorLoop):
         return self.model_out
 
     def _step(self, final):
-        if self.partial is not None:
-            ops.complete_overwrite(self.x, self.partial, self.pnoise(), self.t, *self.q)
+        """[the unfused overwrite,] model call, main draw, the given draw of the NEXT step unless final, [cfg_combine,] one update
+        launch, [the copy into the null half,] decrement or advance unless final."""
+        self.part.before(self)
         mo = self._model_call()
-        ops.p_sample(self.x, mo, self.noise(), self.t, *self.post, *self.tail, out=self.x)
-        ops.add_scalar_i64(self.t, -1)
-
-    def run(self, x_T, total_steps, noise_buffer=None, partial=None, partial_noise=None):
-        self.check_current()
-        self._start(x_T, total_steps - 1)
-        if self.partial is not None:
-            self.partial.copy_(partial)
-        self._upload((self.noise, noise_buffer, 1))
-        if self.partial is not None:
-            self._upload((self.pnoise, partial_noise, 0))
-        out = self._replays(total_steps)
-        self._park()
-        return out
-
-
-class _DDIMGraph(_DDIMLoop):
-    """ddim_sample_loop: model call, draw, dsc_ddim_step_f32, advance."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False):
-        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay)
-        self._capture(self.kinds)
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.x if final else self.noise()                # not read on the last pair
-        ops.ddim_step(self.x, mo, noise, *self.tabs, *self.ddim, self.mean_type, out=self.x)
-        self._advance(final)
-
-    def run(self, x_T, dtab, noise_buffer=None):
-        self._start(x_T, self._load_tables(dtab))
-        self._upload((self.noise, noise_buffer, 1))
-        return self._replays(self.S)
-
-
-class _RaggedCompleteGraph(_Ragged, _PosteriorLoop):
-    """p_sample_loop_complete_ragged.  ``graph``: model call, the main draw, the partial draw of the NEXT step, the fused update
-    (posterior step on the free rows, re-noised given objects on the others), decrement; replayed total_steps - 1 times.  ``final``:
-    model call, the main draw and the fused update at t == 0 (given rows restored, no partial draw).  ``fused=False``: partial draw,
-    ragged overwrite, model call, main draw, p_sample, decrement, every step from ``graph``; restore after the loop."""
-
-    def __init__(self, diff, model, shape, pmax, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay)
-        self._init_given(pmax, self.T, fused)
-        self._capture([False, True] if fused else [False])
-
-    def _step(self, final):
-        if not self.fused:
-            self._overwrite(self.pnoise())
-            mo = self._model_call()
-            ops.p_sample(self.x, mo, self.noise(), self.t, *self.post, *self.tail, out=self.x)
-            ops.add_scalar_i64(self.t, -1)
-            return
-        mo = self._model_call()
-        noise = self.noise()
-        pn = self.partial if final else self.pnoise()           # not read at t == 0
-        ops.p_sample_inpaint(self.x, mo, noise, self.partial, pn, self.counts, self.t, *self.post, *self.q, *self.tail, out=self.x)
+        noise = self._main_draw(final)
+        given = self.part.operands(self, final)
+        mo, guided = self.guide.apply(self, mo) if self.guide else (mo, {})
+        ops.issue(ops.step_rec(self.x, mo, noise, self.x, self.mean_type, **self.sched, **given, **guided))
+        if self.guide:
+            self.guide.after(self)
         if not final:
-            ops.add_scalar_i64(self.t, -1)
+            self._move()
 
-    def run(self, x_T, total_steps, partial, counts, noise_buffer=None, partial_noise=None):
-        self.check_current()
-        self._start(x_T, total_steps - 1)
-        self._begin_given(partial, counts, noise_buffer, partial_noise)
-        out = self._restore(self._replays(total_steps))
-        self._park()
-        return out
-
-
-class _DDIMCompleteGraph(_Ragged, _DDIMLoop):
-    """ddim_complete_ragged_loop.  ``graph``: model call, main draw k, the partial draw of pair k + 1, the fused update (DDIM step on
-    the free rows, the given objects re-noised at t_next on the others), advance.  ``final``: model call and the draw-free fused step of
-    the last pair (x_start on the free rows, the given rows restored).  2 S draws: x_T, then per pair a partial draw (B, Pmax, C), the
-    model call and a main draw (B, N, C); the last pair makes the partial draw only.  ``fused=False``: partial draw, ragged overwrite,
-    model call, main draw, ddim_step, advance; restore after the loop."""
-
-    def __init__(self, diff, model, shape, pmax, device, condition, condition_cross, S, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay)
-        self._init_given(pmax, S, fused)
-        self._capture(self.kinds)
-
-    def _step(self, final):
-        if not self.fused:
-            self._overwrite(self.pnoise())
-        mo = self._model_call()
-        noise = self.x if final else self.noise()                # neither is read on the last pair
-        if not self.fused:
-            ops.ddim_step(self.x, mo, noise, *self.tabs, *self.ddim, self.mean_type, out=self.x)
-        else:
-            pn = self.partial if final else self.pnoise()
-            ops.ddim_inpaint_step(self.x, mo, noise, self.partial, pn, self.counts, *self.tabs, *self.ddim, *self.q, self.mean_type,
-                                  out=self.x)
-        self._advance(final)
-
-    def run(self, x_T, dtab, partial, counts, noise_buffer=None, partial_noise=None):
-        self._start(x_T, self._load_tables(dtab))
-        self._begin_given(partial, counts, noise_buffer, partial_noise)
-        return self._restore(self._replays(self.S))
-
-
-class _MaskedGraph(_Masked, _PosteriorLoop):
-    """p_sample_loop_masked: _RaggedCompleteGraph's fused step on a mask -- the main draw of t, the known-draw of t - 1,
-    dsc_p_sample_masked_f32; ``final`` at t == 0 sets the given elements to ``known`` and makes no known-draw."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False):
-        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay)
-        self._init_given(self.T)
-        self._capture([False, True])
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.noise()
-        nk = self.known if final else self.knoise()             # not read at t == 0
-        ops.p_sample_masked(self.x, mo, noise, self.known, nk, self.mask, self.t, *self.post, *self.q, *self.tail, out=self.x)
-        if not final:
-            ops.add_scalar_i64(self.t, -1)
-
-    def run(self, x_T, total_steps, known, mask, noise_buffer=None, known_noise=None):
-        self.check_current()
-        self._start(x_T, total_steps - 1)
-        self._begin_given(known, mask, noise_buffer, known_noise)
-        out = self._replays(total_steps)
-        self._park()
-        return out
-
-
-class _DDIMMaskedGraph(_Masked, _DDIMLoop):
-    """ddim_masked_loop: _DDIMCompleteGraph's fused step on a mask -- main draw k, the known-draw of pair k + 1,
-    dsc_ddim_masked_step_f32; ``final``: x_start on the free elements, ``known`` on the given ones, no draw."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False):
-        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay)
-        self._init_given(S)
-        self._capture(self.kinds)
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.x if final else self.noise()                # neither is read on the last pair
-        nk = self.known if final else self.knoise()
-        ops.ddim_masked_step(self.x, mo, noise, self.known, nk, self.mask, *self.tabs, *self.ddim, *self.q, self.mean_type, out=self.x)
-        self._advance(final)
-
-    def run(self, x_T, dtab, known, mask, noise_buffer=None, known_noise=None):
-        self._start(x_T, self._load_tables(dtab))
-        self._begin_given(known, mask, noise_buffer, known_noise)
-        return self._replays(self.S)
-
-
-class _Guided:
-    """Classifier-free guidance: the plan runs at 2 B -- rows [0, B) fed the text features, rows [B, 2 B) zeros -- on the same x and t
-    in both halves; the fused kernels read both halves of the plan's output and write the new x to BOTH halves of ``x2`` (their x_dup
-    pointer).  The (B,) scale vector (ops.guidance_scales) is a buffer of the graph, captured by pointer and refreshed in place: one
-    graph serves every per-scene mix of scales.  ``fused=False`` is the comparison of tools/bench_cfg.py: cfg_combine into ``m``, the
-    unguided step kernel, a copy into the null half."""
-
-    def _init_guided(self, fused):
-        self.fused = fused
-        self.scale = torch.ones((self.shape[0],), device=self.device, dtype=torch.float32)
-        self.m = None if fused else torch.empty(self.shape, device=self.device, dtype=torch.float32)
-        self.tB = self.t[:self.shape[0]]
-
-
-class _GuidedStepGraph(_Guided, _PosteriorLoop):
-    """p_sample_loop_guided: _StepGraph's step with dsc_p_sample_cfg_f32."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay, mult=2)
-        self._init_guided(fused)
-        self._capture([False])
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.noise()
-        if self.fused:
-            ops.p_sample_cfg(self.x, mo, self.scale, noise, self.tB, *self.post, *self.tail, out=self.x, x_dup=self.x_null)
-        else:
-            ops.cfg_combine(mo, self.scale, out=self.m)
-            ops.p_sample(self.x, self.m, noise, self.tB, *self.post, *self.tail, out=self.x)
-            self.x_null.copy_(self.x)
-        ops.add_scalar_i64(self.t, -1)
-
-    def run(self, x_T, total_steps, scale, noise_buffer=None):
-        self.check_current()
-        self._start(x_T, total_steps - 1)
-        self.scale.copy_(scale)                 # in place: the graph holds this pointer
-        self._upload((self.noise, noise_buffer, 1))
-        out = self._replays(total_steps)
-        self._park()
-        return out
-
-
-class _DDIMGuidedGraph(_Guided, _DDIMLoop):
-    """ddim_guided_loop: _DDIMGraph's step with dsc_ddim_cfg_step_f32."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay, mult=2)
-        self._init_guided(fused)
-        self._capture(self.kinds)
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.x if final else self.noise()                # not read on the last pair
-        if self.fused:
-            ops.ddim_cfg_step(self.x, mo, self.scale, noise, *self.tabs, *self.ddim, self.mean_type, out=self.x, x_dup=self.x_null)
-        else:
-            ops.cfg_combine(mo, self.scale, out=self.m)
-            ops.ddim_step(self.x, self.m, noise, *self.tabs, *self.ddim, self.mean_type, out=self.x)
-            self.x_null.copy_(self.x)
-        self._advance(final)
-
-    def run(self, x_T, dtab, scale, noise_buffer=None):
-        t0 = self._load_tables(dtab)
-        self.scale.copy_(scale)
+    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None):
+        """``sched``: total_steps of a T-step loop, the device tables (GaussianDiffusion.ddim_tables) of a strided one.  ``values``: the
+        (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword)."""
+        t0, steps = self._begin(sched)
         self._start(x_T, t0)
-        self._upload((self.noise, noise_buffer, 1))
-        return self._replays(self.S)
-
-
-class _MaskedGuidedGraph(_Masked, _Guided, _PosteriorLoop):
-    """p_sample_loop_masked_guided: _MaskedGraph's step on a plan at 2 B with dsc_p_sample_masked_cfg_f32; known, mask and the
-    known-draws stay at B.  ``fused=False``: cfg_combine into ``m``, dsc_p_sample_masked_f32, a copy into the null half."""
-
-    def __init__(self, diff, model, shape, device, condition, condition_cross, clip_denoised, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, clip_denoised, replay, mult=2)
-        self._init_given(self.T)
-        self._init_guided(fused)
-        self._capture([False, True])
-
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.noise()
-        nk = self.known if final else self.knoise()             # not read at t == 0
-        if self.fused:
-            ops.p_sample_masked_cfg(self.x, mo, self.scale, noise, self.known, nk, self.mask, self.tB, *self.post, *self.q, *self.tail,
-                                    out=self.x, x_dup=self.x_null)
-        else:
-            ops.cfg_combine(mo, self.scale, out=self.m)
-            ops.p_sample_masked(self.x, self.m, noise, self.known, nk, self.mask, self.tB, *self.post, *self.q, *self.tail, out=self.x)
+        if partial is not None:
+            values += (partial,)
+        if self.guide:
+            self.guide.scale.copy_(values[0])   # in place: the graph holds this pointer
+            values = values[1:]
+        self.part.load(self, *values)
+        self._upload((self.noise, noise_buffer, 1), *([(self.part.noise, given_noise, 1 if self.part.fused else 0)] if self.part.noise else []))
+        self.part.first(self)
+        if self.part.fused and self.x_null is not None:         # guided: both halves of the state stay current
             self.x_null.copy_(self.x)
-        if not final:
-            ops.add_scalar_i64(self.t, -1)
-
-    def run(self, x_T, total_steps, scale, known, mask, noise_buffer=None, known_noise=None):
-        self.check_current()
-        self._start(x_T, total_steps - 1)
-        self.scale.copy_(scale)                 # in place: the graph holds this pointer
-        self._begin_given(known, mask, noise_buffer, known_noise)
-        out = self._replays(total_steps)
-        self._park()
+        out = self.part.restore(self, self._replays(steps))
+        self._end()
         return out
 
 
-class _DDIMMaskedGuidedGraph(_Masked, _Guided, _DDIMLoop):
-    """ddim_masked_guided_loop: _DDIMMaskedGraph's step on a plan at 2 B with dsc_ddim_masked_cfg_step_f32; ``fused=False`` as in
-    _MaskedGuidedGraph, with dsc_ddim_masked_step_f32."""
+# The ten loops: schedule (the base), given part, guidance; ``what`` names the loop in the refusal of a short replay buffer.
+class _StepGraph(_Loop, _PosteriorLoop):        # p_sample_loop; with partial_shape p_sample_loop_complete.  No ``final``.
+    given, chains = _Dense, True
 
-    def __init__(self, diff, model, shape, device, condition, condition_cross, S, replay=False, fused=True):
-        super().__init__(diff, model, shape, device, condition, condition_cross, S, replay, mult=2)
-        self._init_given(S)
-        self._init_guided(fused)
-        self._capture(self.kinds)
 
-    def _step(self, final):
-        mo = self._model_call()
-        noise = self.x if final else self.noise()                # neither is read on the last pair
-        nk = self.known if final else self.knoise()
-        if self.fused:
-            ops.ddim_masked_cfg_step(self.x, mo, self.scale, noise, self.known, nk, self.mask, *self.tabs, *self.ddim, *self.q,
-                                     self.mean_type, out=self.x, x_dup=self.x_null)
-        else:
-            ops.cfg_combine(mo, self.scale, out=self.m)
-            ops.ddim_masked_step(self.x, self.m, noise, self.known, nk, self.mask, *self.tabs, *self.ddim, *self.q, self.mean_type,
-                                 out=self.x)
-            self.x_null.copy_(self.x)
-        self._advance(final)
+class _DDIMGraph(_Loop, _DDIMLoop):             # ddim_sample_loop, strided re-arrangement on the sub-shape
+    what = "DDIM with S = %d"
 
-    def run(self, x_T, dtab, scale, known, mask, noise_buffer=None, known_noise=None):
-        t0 = self._load_tables(dtab)
-        self.scale.copy_(scale)
-        self._start(x_T, t0)
-        self._begin_given(known, mask, noise_buffer, known_noise)
-        return self._replays(self.S)
+
+class _RaggedCompleteGraph(_Loop, _PosteriorLoop):              # p_sample_loop_complete_ragged
+    given, what = _Ragged, "ragged completion"
+
+
+class _DDIMCompleteGraph(_Loop, _DDIMLoop):     # ddim_complete_ragged_loop: 2 S draws, the last pair makes the partial draw only
+    given, what = _Ragged, "strided ragged completion"
+
+
+class _MaskedGraph(_Loop, _PosteriorLoop):      # p_sample_loop_masked
+    given, what = _Masked, "the masked loop"
+
+
+class _DDIMMaskedGraph(_Loop, _DDIMLoop):       # ddim_masked_loop
+    given, what = _Masked, "the strided masked loop"
+
+
+class _GuidedStepGraph(_Loop, _PosteriorLoop):  # p_sample_loop_guided
+    guided, what = True, "the guided loop"
+
+
+class _DDIMGuidedGraph(_Loop, _DDIMLoop):       # ddim_guided_loop
+    guided, what = True, "the guided strided loop"
+
+
+class _MaskedGuidedGraph(_Loop, _PosteriorLoop):                # p_sample_loop_masked_guided
+    given, guided, what = _Masked, True, "the guided masked loop"
+
+
+class _DDIMMaskedGuidedGraph(_Loop, _DDIMLoop):                 # ddim_masked_guided_loop
+    given, guided, what = _Masked, True, "the guided strided masked loop"
 
 
 def _cached_loop(name, diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, tag, make, run, mult=1, check=None,
@@ -737,10 +645,6 @@ def _cached_loop(name, diff, denoise_fn, shape, device, condition, condition_cro
         return out
 
 
-def _head(buffer, n):
-    return None if buffer is None else buffer[:n]
-
-
 def _replay_check(what, n_main, shape=None, n_partial=None, pshape=None):
     """check(noise_fn) of a front end: the NoiseReplay holds ``n_main`` main draws (of ``shape``, where the loop has always checked it)
     and, for a loop with a given part, ``n_partial`` draws of ``pshape`` for it; ValueError otherwise."""
@@ -756,135 +660,58 @@ def _replay_check(what, n_main, shape=None, n_partial=None, pshape=None):
     return check
 
 
-def graph_sample_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps,
-                      noise_fn=torch.randn, partial_boxes=None):
-    pshape = None if partial_boxes is None else tuple(partial_boxes.shape)
-    out = _cached_loop(
-        "graph_sample_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddpm", bool(clip_denoised), pshape),
-        lambda model, dev, replay: _StepGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay, pshape),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, buf, partial_boxes, pbuf))
-    if partial_boxes is not None:
-        out[:, :partial_boxes.shape[1], :] = partial_boxes          # clean objects restored after the last step (:471-473)
-    return out
+def _front_end(name, cls):
+    """graph_*_loop of one row: the loop as replayed hipGraphs, bit-identical to the eager loop (same expressions, same draws in the same
+    order, the same generator state afterwards).  Called as (diff, denoise_fn, shape, device, condition, condition_cross, [scale,]
+    clip_denoised, total_steps -- a strided row: sampling_timesteps, eta --, noise_fn=torch.randn, [the given values,] [fused=True]):
+    ``scale`` the (B,) f32 device vector of ops.guidance_scales under conditions at 2 B (GaussianDiffusion._guided_inputs), ``counts`` the
+    (B,) int64 device tensor of ops.ragged_counts, ``known`` / ``mask`` those of _masked_inputs.  The cache key holds the class,
+    clip_denoised or S, ``fused`` and the shape of the given rows -- never eta, counts, mask or scales, which live in buffers."""
+    names = (("scale",) if cls.guided else ()) + (("sampling_timesteps", "eta") if cls.strided else ("clip_denoised", "total_steps")) \
+        + ("noise_fn",) + cls.given.values + (("fused",) if cls.guided or cls.given is _Ragged else ())
+
+    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, **kw):
+        if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
+            raise TypeError("%s(diff, denoise_fn, shape, device, condition, condition_cross, %s)" % (name, ", ".join(names)))
+        a = dict(dict.fromkeys(names), noise_fn=torch.randn, fused=True)
+        a.update(zip(names, args), **kw)
+        given = [a[v] for v in cls.given.values if a[v] is not None]
+        gshape = None if not given or cls.given is _Masked else (shape[0], given[0].shape[1], shape[2]) if cls.given is _Ragged \
+            else tuple(given[0].shape)
+        if cls.strided:
+            sched = n_main = n_given = int(a["sampling_timesteps"])
+        else:
+            sched, n_main, n_given = bool(a["clip_denoised"]), a["total_steps"] + 1, a["total_steps"]
+        check = cls.what and _replay_check(cls.what % sched if "%" in cls.what else cls.what, n_main,
+                                           shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
+        out = _cached_loop(
+            name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"], (cls.__name__, sched, bool(a["fused"]), gshape),
+            lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape),
+            lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else n_given, *([a["scale"]] if cls.guided else []), *given,
+                                                  noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given)),
+            mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
+        if cls.given is _Dense and given:
+            out[:, :gshape[1], :] = given[0]            # clean objects restored after the last step (:471-473)
+        return out
+    loop.__name__ = loop.__qualname__ = name
+    return loop
 
 
-def graph_ddim_sample_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta,
-                           noise_fn=torch.randn):
-    """ddim_sample_loop as replayed hipGraphs; bit-identical to the eager loop (same kernels, same draws in the same order)."""
-    S = int(sampling_timesteps)
-    return _cached_loop(
-        "graph_ddim_sample_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim", S),
-        lambda model, dev, replay: _DDIMGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, buf), check=_replay_check("DDIM with S = %d" % S, S), ddim=(S, eta))
+def _head(buffer, n):
+    return None if buffer is None else buffer[:n]
 
 
-def graph_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps,
-                               noise_fn=torch.randn, partial_boxes=None, counts=None, fused=True):
-    """p_sample_loop_complete_ragged as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same
-    order, the same generator state afterwards).  ``counts`` is the (B,) int64 device tensor of ops.ragged_counts.  The cache key
-    holds Pmax but not the counts."""
-    B, N, C = shape
-    pmax = partial_boxes.shape[1]
-    return _cached_loop(
-        "graph_complete_ragged_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
-        ("ragged", bool(fused), pmax, bool(clip_denoised)),
-        lambda model, dev, replay: _RaggedCompleteGraph(diff, model, tuple(shape), pmax, dev, condition, condition_cross, clip_denoised,
-                                                        replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, partial_boxes, counts, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
-        check=_replay_check("ragged completion", total_steps + 1, None, total_steps, (B, pmax, C)))
-
-
-def graph_ddim_complete_ragged_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta,
-                                    noise_fn=torch.randn, partial_boxes=None, counts=None, fused=True):
-    """ddim_complete_ragged_loop as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order,
-    the same generator state afterwards).  ``counts`` is the (B,) int64 device tensor of ops.ragged_counts.  The cache key holds S and
-    Pmax; it holds neither eta nor the counts."""
-    B, N, C = shape
-    S = int(sampling_timesteps)
-    pmax = partial_boxes.shape[1]
-    return _cached_loop(
-        "graph_ddim_complete_ragged_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
-        ("ddim_ragged", S, bool(fused), pmax),
-        lambda model, dev, replay: _DDIMCompleteGraph(diff, model, tuple(shape), pmax, dev, condition, condition_cross, S, replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, partial_boxes, counts, buf, pbuf),
-        check=_replay_check("strided ragged completion", S, None, S, (B, pmax, C)), ddim=(S, eta))
-
-
-def graph_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, clip_denoised, total_steps, noise_fn=torch.randn,
-                      known=None, mask=None):
-    """p_sample_loop_masked as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order, the
-    same generator state afterwards).  ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 (ops.known_mask) are copied into the graph's
-    own buffers: the cache key holds the shape, not the mask."""
-    return _cached_loop(
-        "graph_masked_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("masked", bool(clip_denoised)),
-        lambda model, dev, replay: _MaskedGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, known, mask, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
-        check=_replay_check("the masked loop", total_steps + 1, shape, total_steps, shape))
-
-
-def graph_ddim_masked_loop(diff, denoise_fn, shape, device, condition, condition_cross, sampling_timesteps, eta, noise_fn=torch.randn,
-                           known=None, mask=None):
-    """ddim_masked_loop as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same order, the same
-    generator state afterwards).  The cache key holds the shape and S; it holds neither eta nor the mask."""
-    S = int(sampling_timesteps)
-    return _cached_loop(
-        "graph_ddim_masked_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim_masked", S),
-        lambda model, dev, replay: _DDIMMaskedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, known, mask, buf, pbuf),
-        check=_replay_check("the strided masked loop", S, shape, S, shape), ddim=(S, eta))
-
-
-def graph_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, clip_denoised, total_steps,
-                      noise_fn=torch.randn, fused=True):
-    """p_sample_loop_guided as a replayed hipGraph; bit-identical to the eager loop (same expressions, same draws in the same order, the
-    same generator state afterwards).  ``condition`` / ``condition_cross`` arrive at 2 B (GaussianDiffusion._guided_inputs), ``scale`` is
-    the (B,) f32 device vector of ops.guidance_scales: the cache key holds the shape, not the scales."""
-    return _cached_loop(
-        "graph_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
-        ("guided", bool(fused), bool(clip_denoised)),
-        lambda model, dev, replay: _GuidedStepGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay,
-                                                    fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, scale, _head(buf, total_steps + 1)), mult=2,
-        check=_replay_check("the guided loop", total_steps + 1, shape))
-
-
-def graph_ddim_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, sampling_timesteps, eta,
-                           noise_fn=torch.randn, fused=True):
-    """ddim_guided_loop as replayed hipGraphs; bit-identical to the eager loop.  The cache key holds the shape and S; it holds neither
-    eta nor the scales."""
-    S = int(sampling_timesteps)
-    return _cached_loop(
-        "graph_ddim_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn, ("ddim_guided", S, bool(fused)),
-        lambda model, dev, replay: _DDIMGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, buf), mult=2, check=_replay_check("the guided strided loop", S, shape),
-        ddim=(S, eta))
-
-
-def graph_masked_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, clip_denoised, total_steps,
-                             noise_fn=torch.randn, known=None, mask=None, fused=True):
-    """p_sample_loop_masked_guided as replayed hipGraphs; bit-identical to the eager loop (same expressions, same draws in the same
-    order, the same generator state afterwards).  ``condition`` / ``condition_cross`` arrive at 2 B, ``scale`` (B,) f32, ``known`` /
-    ``mask`` (B, N, C) are copied into the graph's own buffers: the cache key holds the shape, neither the mask nor the scales."""
-    return _cached_loop(
-        "graph_masked_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
-        ("masked_guided", bool(fused), bool(clip_denoised)),
-        lambda model, dev, replay: _MaskedGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, clip_denoised, replay,
-                                                      fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, total_steps, scale, known, mask, _head(buf, total_steps + 1), _head(pbuf, total_steps)),
-        mult=2, check=_replay_check("the guided masked loop", total_steps + 1, shape, total_steps, shape))
-
-
-def graph_ddim_masked_guided_loop(diff, denoise_fn, shape, device, condition, condition_cross, scale, sampling_timesteps, eta,
-                                  noise_fn=torch.randn, known=None, mask=None, fused=True):
-    """ddim_masked_guided_loop as replayed hipGraphs; bit-identical to the eager loop.  The cache key holds the shape and S; it holds
-    neither eta, the mask nor the scales."""
-    S = int(sampling_timesteps)
-    return _cached_loop(
-        "graph_ddim_masked_guided_loop", diff, denoise_fn, shape, device, condition, condition_cross, noise_fn,
-        ("ddim_masked_guided", S, bool(fused)),
-        lambda model, dev, replay: _DDIMMaskedGuidedGraph(diff, model, tuple(shape), dev, condition, condition_cross, S, replay, fused),
-        lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab, scale, known, mask, buf, pbuf), mult=2,
-        check=_replay_check("the guided strided masked loop", S, shape, S, shape), ddim=(S, eta))
+# module attributes on purpose: diffusion_ddpm.py looks a front end up by name at call time
+graph_sample_loop = _front_end("graph_sample_loop", _StepGraph)         # (..., partial_boxes=None): with it, p_sample_loop_complete
+graph_ddim_sample_loop = _front_end("graph_ddim_sample_loop", _DDIMGraph)
+graph_complete_ragged_loop = _front_end("graph_complete_ragged_loop", _RaggedCompleteGraph)
+graph_ddim_complete_ragged_loop = _front_end("graph_ddim_complete_ragged_loop", _DDIMCompleteGraph)
+graph_masked_loop = _front_end("graph_masked_loop", _MaskedGraph)
+graph_ddim_masked_loop = _front_end("graph_ddim_masked_loop", _DDIMMaskedGraph)
+graph_guided_loop = _front_end("graph_guided_loop", _GuidedStepGraph)
+graph_ddim_guided_loop = _front_end("graph_ddim_guided_loop", _DDIMGuidedGraph)
+graph_masked_guided_loop = _front_end("graph_masked_guided_loop", _MaskedGuidedGraph)
+graph_ddim_masked_guided_loop = _front_end("graph_ddim_masked_guided_loop", _DDIMMaskedGuidedGraph)
 
 
 def _plan_key(g):

@@ -47,18 +47,28 @@ LOOPS = {"gen_samples": ("_StepGraph", False),
          "inpaint_samples": ("_MaskedGraph", False),
          "inpaint_samples_ddim": ("_DDIMMaskedGraph", True),
          "gen_samples_guided": ("_GuidedStepGraph", False),
-         "gen_samples_guided_ddim": ("_DDIMGuidedGraph", True)}
+         "gen_samples_guided_ddim": ("_DDIMGuidedGraph", True),
+         "inpaint_samples_guided": ("_MaskedGuidedGraph", False),
+         "inpaint_samples_guided_ddim": ("_DDIMMaskedGuidedGraph", True),
+         "complete_samples": ("_StepGraph", False),                             # the dense prefix: the unfused overwrite in the step
+         "complete_samples_ragged/Pmax5": ("_RaggedCompleteGraph", False),      # Pmax < N: the given stream's shape is not the state's
+         "complete_samples_ragged_ddim/Pmax5": ("_DDIMCompleteGraph", True)}
+PMAX = 5
 
 
 def _loop_kwargs(loop, strided, steps, shape):
     _, N, C = shape
     kw = dict(sampling_timesteps=steps, ddim_sampling_eta=0.5) if strided else dict(clip_denoised=True, keep_running=steps == 2)
     given = rnd(*shape, seed=501).clamp(-1, 1).to(dev())
-    if loop.startswith("complete"):
+    if loop == "complete_samples":
+        kw.update(partial_boxes=given[:, :PMAX].contiguous())
+    elif loop.endswith("/Pmax5"):
+        kw.update(partial_boxes=given[:, :PMAX].contiguous(), num_partial=[0, PMAX])
+    elif loop.startswith("complete"):
         kw.update(partial_boxes=given, num_partial=[0, 5])                      # Pmax == N; a scene without and one with given objects
     elif loop.startswith("inpaint"):
         kw.update(known=given, mask=(rnd(*shape, seed=502) > 0.3).to(dev()))
-    elif "guided" in loop:
+    if "guided" in loop:
         kw.update(guidance_scale=(0.0, 3.0))
     return kw
 
@@ -84,7 +94,7 @@ def test_every_loop_at_one_and_two_steps_is_the_eager_loop_and_capture_draws_not
     for graph in (False, True, True):                                           # eager, graph (this call captures), graph (cached)
         torch.manual_seed(2468)
         with torch.no_grad(), QUIET():
-            outs.append(getattr(diff, loop)(shape, dev(), condition=cond, condition_cross=cross, graph=graph, **kw))
+            outs.append(getattr(diff, loop.split("/")[0])(shape, dev(), condition=cond, condition_cross=cross, graph=graph, **kw))
         states.append(torch.cuda.get_rng_state(dev()))
         if graph:
             assert len(gd._graphs) == 1                                         # the one-live-graph rule
@@ -97,6 +107,61 @@ def test_every_loop_at_one_and_two_steps_is_the_eager_loop_and_capture_draws_not
     if strided:
         assert graphs[0].S == steps and (graphs[0].graph is None) == (steps == 1) and graphs[0].final is not None
     assert _lib.device_error_count(reset=True) == 0                             # the warm-up of the capture included
+
+
+# the rows that take ``fused=``: entry point -> (front end, class, strided).  fused=False unfuses the overwrite of the ragged rows and the
+# guidance of the guided rows; outside this test only tools/bench_*.py run those captured paths (the two guided in-painting rows also
+# in tests/test_gpu_guided_inpaint.py, through the replay buffers)
+UNFUSED = {"complete_samples_ragged": ("graph_complete_ragged_loop", "_RaggedCompleteGraph", False),
+           "complete_samples_ragged_ddim": ("graph_ddim_complete_ragged_loop", "_DDIMCompleteGraph", True),
+           "complete_samples_ragged/Pmax5": ("graph_complete_ragged_loop", "_RaggedCompleteGraph", False),
+           "complete_samples_ragged_ddim/Pmax5": ("graph_ddim_complete_ragged_loop", "_DDIMCompleteGraph", True),
+           "gen_samples_guided": ("graph_guided_loop", "_GuidedStepGraph", False),
+           "gen_samples_guided_ddim": ("graph_ddim_guided_loop", "_DDIMGuidedGraph", True),
+           "inpaint_samples_guided": ("graph_masked_guided_loop", "_MaskedGuidedGraph", False),
+           "inpaint_samples_guided_ddim": ("graph_ddim_masked_guided_loop", "_DDIMMaskedGuidedGraph", True)}
+
+
+def _front_end(gd, diff, loop, strided, shape, cond, cross, kw, fused):
+    """The captured loop behind entry point ``loop`` called as GaussianDiffusion calls it, with ``fused`` passed on."""
+    from diffuscene_amd import sampler
+    sched = (kw["sampling_timesteps"], kw["ddim_sampling_eta"]) if strided else (kw["clip_denoised"], 2)
+    head, given = (cond, cross), {}
+    if "guided" in loop:
+        head = gd._guided_inputs(shape, dev(), cond, cross, kw["guidance_scale"], loop)
+    if loop.startswith("complete"):
+        given = dict(zip(("partial_boxes", "counts"), gd._ragged_inputs(shape, dev(), kw["partial_boxes"], kw["num_partial"], loop)))
+    elif loop.startswith("inpaint"):
+        given = dict(zip(("known", "mask"), gd._masked_inputs(shape, dev(), kw["known"], kw["mask"], loop)))
+    return getattr(sampler, UNFUSED[loop][0])(gd, diff._denoise, shape, dev(), *head, *sched, noise_fn=torch.randn, fused=fused, **given)
+
+
+@pytest.mark.parametrize("loop", list(UNFUSED))
+def test_the_unfused_captured_loop_is_the_fused_one_and_the_eager_loop(loop, tmp_path):
+    _, cls, strided = UNFUSED[loop]
+    m = build_model("v", T_STRIDED, tmp_path) if strided else build_model("v", 2, tmp_path, tag="sampler_core_unfused")
+    diff, gd = m.diffusion, m.diffusion.diffusion
+    cond, cross = _conditions(m, B, case_texts()[:B])
+    shape = (B, GN, GC)
+    kw = _loop_kwargs(loop, strided, 2, shape)                                  # two steps / S = 2
+    outs, states, graphs = [], [], []
+    for fused in (None, True, False):                                           # eager, captured fused, captured unfused
+        torch.manual_seed(1357)
+        with torch.no_grad(), QUIET():
+            if fused is None:
+                outs.append(getattr(diff, loop.split("/")[0])(shape, dev(), condition=cond, condition_cross=cross, graph=False, **kw))
+            else:
+                outs.append(_front_end(gd, diff, loop, strided, shape, cond, cross, kw, fused))
+                (g,) = gd._graphs.values()
+                assert g.fused is fused and type(g).__name__ == cls
+                if "guided" in loop:
+                    assert (g.m is None) == fused
+                graphs.append(g)
+        states.append(torch.cuda.get_rng_state(dev()))
+    assert graphs[0] is not graphs[1]                                           # ``fused`` is part of the key
+    assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0]), (loop, float((outs[2] - outs[0]).abs().max()))
+    assert torch.equal(states[1], states[0]) and torch.equal(states[2], states[0])
+    assert bool(torch.isfinite(outs[0]).all())
 
 
 # ------------------------------------------------------------------------------------------------------------------- the step kernels

@@ -37,8 +37,8 @@ def test_header_declares_and_library_exports_the_new_symbols():
         assert name in _lib.SIGNATURES and hasattr(lib, name), "%s not exported / bound" % name
     assert callable(ops.p_sample_masked_cfg) and callable(ops.ddim_masked_cfg_step)
     assert callable(sampler.graph_masked_guided_loop) and callable(sampler.graph_ddim_masked_guided_loop)
-    assert issubclass(sampler._MaskedGuidedGraph, (sampler._Masked, sampler._Guided, sampler._PosteriorLoop))
-    assert issubclass(sampler._DDIMMaskedGuidedGraph, (sampler._Masked, sampler._Guided, sampler._DDIMLoop))
+    for cls, schedule in ((sampler._MaskedGuidedGraph, sampler._PosteriorLoop), (sampler._DDIMMaskedGuidedGraph, sampler._DDIMLoop)):
+        assert issubclass(cls, schedule) and cls.given is sampler._Masked and cls.guided is True      # the row: all three parts
     assert callable(GaussianDiffusion.p_sample_loop_masked_guided) and callable(GaussianDiffusion.ddim_masked_guided_loop)
     assert callable(DiffusionPoint.inpaint_samples_guided) and callable(DiffusionPoint.inpaint_samples_guided_ddim)
 
