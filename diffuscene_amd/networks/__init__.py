@@ -13,15 +13,47 @@ def optimizer_factory(config, parameters):
     optimizer = config.get("optimizer", "Adam")
     lr = config.get("lr", 1e-3)
     momentum = config.get("momentum", 0.9)
+    # weight EMA (not in the reference): ``ema_decay`` (float in [0, 1)) and ``ema_warmup``; absent keys leave the objects below as
+    # they were.  Adam keeps the average inside its fused sweep; SGD / RAdam get a ParamEMA updated after every step().
+    ema_decay, ema_warmup = config.get("ema_decay"), config.get("ema_warmup", False)
+    if ema_warmup and ema_decay is None:
+        raise ValueError("ema_warmup needs an ema_decay")
     if optimizer == "SGD":
-        return torch.optim.SGD(parameters, lr=lr, momentum=momentum, weight_decay=0.0)
+        if ema_decay is not None:
+            parameters = list(parameters)
+        return _with_param_ema(torch.optim.SGD(parameters, lr=lr, momentum=momentum, weight_decay=0.0), parameters, ema_decay,
+                               ema_warmup)
     elif optimizer == "Adam":
         # a torch.optim.Adam whose step() is the fused HIP clip+Adam sweep (diffuscene_amd/optim.py)
         from ..optim import FusedAdam
-        return FusedAdam(parameters, lr=lr, weight_decay=0.0)
+        if ema_decay is None:
+            return FusedAdam(parameters, lr=lr, weight_decay=0.0)
+        return FusedAdam(parameters, lr=lr, weight_decay=0.0, ema_decay=ema_decay, ema_warmup=ema_warmup)
     elif optimizer == "RAdam":
-        return torch.optim.RAdam(parameters, lr=lr, weight_decay=0.0)
+        if ema_decay is not None:
+            parameters = list(parameters)
+        return _with_param_ema(torch.optim.RAdam(parameters, lr=lr, weight_decay=0.0), parameters, ema_decay, ema_warmup)
     raise NotImplementedError()
+
+
+def _with_param_ema(optimizer, parameters, ema_decay, ema_warmup):
+    """``optimizer`` with a ParamEMA of its parameters as ``optimizer.ema``, updated after every ``step()``; unchanged without a decay."""
+    if ema_decay is None:
+        return optimizer
+    from ..optim import ParamEMA
+    ema = ParamEMA(parameters, ema_decay, ema_warmup)
+    inner = optimizer.step
+
+    def step(closure=None):
+        if ema.swapped:             # before the optimizer moves anything: it would train the average
+            raise RuntimeError("optimizer.step() while the EMA weights are swapped in (optimizer.ema.swap / weights): swap back first")
+        out = inner() if closure is None else inner(closure)
+        ema.update()
+        return out
+
+    optimizer.ema = ema
+    optimizer.step = step
+    return optimizer
 
 
 def build_network(input_dims, n_classes, config, weight_file=None, device="cpu"):

@@ -710,6 +710,27 @@ int dsc_clip_coef_f32(const double* partial, int32_t nchunks, float max_norm, fl
 int dsc_adam_step_f32(const dsc_optim_chunk* chunks, int32_t nchunks, float step_size, float beta1, float beta2,
                       float bias_correction2_sqrt, float eps, float weight_decay, const float* grad_scale,
                       dsc_stream_t stream);
+
+/* Weight EMA (the exponential moving average of the parameters that DDPM recipes sample from), over the same work list.
+ * dsc_optim_chunk is unchanged: the average's addresses travel in a parallel DEVICE array `ema` of nchunks entries,
+ * ema[i] = address of the average of the elements chunks[i] covers.  One expression everywhere, three float32
+ * statements with one rounding each (1 - ema_decay is formed in float32 from the argument):
+ *   d = p - e;  d = d * (1 - ema_decay);  e = e + d.
+ * The f32x4 path of a chunk needs ema[i] 16-byte aligned like the chunk's other pointers and count % 4 == 0; any other
+ * chunk takes the scalar path, with the same results.  ema == NULL or !(0 <= ema_decay < 1) -> DSC_EINVAL, no launch.
+ *
+ * dsc_adam_ema_step_f32: the sweep of dsc_adam_step_f32 (same code: param, exp_avg, exp_avg_sq come out bit-identical)
+ *   followed per element, in registers, by the EMA expression on the NEW parameter value.  36 B/parameter.
+ * dsc_ema_update_f32: the EMA expression alone (reads chunks[i].param and .count only) -- for optimizers other than
+ *   the fused Adam; bit-identical to the EMA half of dsc_adam_ema_step_f32.  12 B/parameter.
+ * dsc_ema_swap_f32: exchanges param and ema element for element, in place, as bit patterns (NaN payloads and signed
+ *   zeros survive); reads chunks[i].param and .count only.  16 B/parameter. */
+int dsc_adam_ema_step_f32(const dsc_optim_chunk* chunks, float* const* ema, int32_t nchunks, float step_size, float beta1,
+                          float beta2, float bias_correction2_sqrt, float eps, float weight_decay, const float* grad_scale,
+                          float ema_decay, dsc_stream_t stream);
+int dsc_ema_update_f32(const dsc_optim_chunk* chunks, float* const* ema, int32_t nchunks, float ema_decay,
+                       dsc_stream_t stream);
+int dsc_ema_swap_f32(const dsc_optim_chunk* chunks, float* const* ema, int32_t nchunks, dsc_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * FoldingNet KL auto-encoder (scene_synthesis/networks/foldingnet_autoencoder.py:56-390), the pieces around its 1x1
  * convolutions (which are dsc_gemm_f32 calls).  Point features are token-major [cloud * n + point][channel].
