@@ -238,6 +238,8 @@ SIGNATURES = {
                                     [C.c_int64, C.c_int32, C.c_void_p]),
     "dsc_ddim_masked_cfg_step_f32": (C.c_int, [c_f32p] * 6 + [C.c_void_p] + [c_i64p] * 3 + [c_f32p] * 11 + [C.c_int32] * 2 +
                                      [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "dsc_steer_boxes_f32": (C.c_int, [c_f32p, c_f32p] + [c_i64p] * 3 + [c_f32p] * 3 + [c_i64p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_i64p,
+                                      C.POINTER(C.c_float), c_f32p, c_f32p] + [C.c_int32] * 9 + [C.c_void_p]),
     "dsc_scene_gate_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int32, C.c_int64, C.c_void_p]),
 }
 

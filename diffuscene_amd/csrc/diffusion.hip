@@ -148,6 +148,166 @@ __global__ __launch_bounds__(256) void cfg_combine_kernel(const float* __restric
         out[base + i] = cfg_mix(mo[base + i], mo[half + base + i], w);
 }
 
+// Collision steering: one launch between the model call and the unchanged step.  One 256-thread block per scene,
+// n <= 160, three phases:
+//   1. thread i < n forms row i of the clamped x0 estimate -- the 8 box channels and the 'empty' logit; a given element (ragged rows or
+//      mask) takes its given value, a free one clamp(predict_x0(x_t, m)), the float32 value the step will form, with m the guidance
+//      mix where scale is set -- and from it the axis-aligned bounds of the box rotated about y (half extents hx = |c| sx + |s| sz,
+//      hy = sy, hz = |s| sx + |c| sz, (c, s) the (cos, sin) channels over their hypot; a zero pair counts as angle 0), staged in LDS
+//      with the validity flag (empty logit < 0);
+//   2. a valid thread walks j = 0 .. n - 1 in index order over the other valid boxes: IoU(i, j) with union floor 1e-6 (the expressions
+//      of networks/loss.py) where all three overlaps are positive -- boxes that only touch do not interact --, the energy terms j > i
+//      and d IoU / d centre_i (sizes and angle carry no gradient; a face shared exactly by both boxes takes half the derivative);
+//   3. the energy is summed in a fixed order (butterfly per wave, then the four partials: scene b's result does not depend on the
+//      batch), the gradient goes to normalised units (* span / 2), and on an active step -- t < *t_below and weight[b] != 0 -- every
+//      free translation element of a valid box whose weight * g is non-zero has its model output moved so that the step's
+//      x0 = clamp(x0) - weight * g:  d = weight * g + (raw - clamp(raw));  mean type x0: m -= d;  eps / v: m += d / Bc (Bc == 0: no
+//      change);  guided: the same delta goes to both halves of the 2 b output, which moves u + w (c - u) by it.
+// From the float32 x0 on, the geometry is float64: an overlap is a small difference of box faces, so in float32 the sum over the pairs
+// loses five to six digits and lands within a few ulp of the exact value only by the luck of its order; in float64 the energy and the
+// gradient are the float32 numbers nearest to the exact ones, whatever the order, and the new model output is rounded once.  The
+// work is n^2 pairs of ~40 operations per scene, far below a microsecond of the float64 rate: the launch is latency, not arithmetic.
+// An inactive launch without optional outputs returns before it reads the scene and stores nothing.  Bad indices: t[b] / counts[b]
+// once per scene by thread 0, step[0] and times[k] once per launch.
+constexpr int STEER_MAXN = 160;
+
+struct SteerArgs {
+    const float* xt; float* mo;
+    const int64_t *t, *step, *times;
+    const float *ca, *cb, *partial;
+    const int64_t* counts;
+    const float* known;
+    const uint8_t* mask;
+    const float *scale, *weight;
+    const int64_t* t_below;
+    float *energy, *grad;
+    int mean_type, b, n, pmax, c, empty_col, S, T;
+    double c_lo[3], c_span[3], s_lo[3], s_span[3];
+};
+
+// Fixed-order block sum of four waves (the form of train.hip's block_sum_loss), in float64.
+__device__ __forceinline__ double block_sum_steer(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ __launch_bounds__(256) void steer_boxes_kernel(const SteerArgs p) {
+    __shared__ double red[4];
+    __shared__ double lo[STEER_MAXN][3], hi[STEER_MAXN][3];                                   // 7.5 KB
+    __shared__ float valid[STEER_MAXN];
+    const int b = blockIdx.x, tid = threadIdx.x, N = p.n, C = p.c;
+    const bool first = tid == 0;
+    const bool is_x0 = p.mean_type == DSC_MEAN_X0;
+    int64_t tv;
+    if (p.t) tv = dsc_checked_index(p.t[b], p.T, first);
+    else tv = dsc_checked_index(p.times[dsc_checked_index(p.step[0], p.S, first && b == 0)], p.T, first && b == 0);
+    int64_t cnt = 0;
+    if (p.counts) cnt = dsc_checked_index(p.counts[b], (int64_t)p.pmax + 1, first);
+    const float w = p.weight[b];
+    const bool active = w != 0.f && tv < p.t_below[0];
+    if (!active && !p.energy && !p.grad) return;                                             // the whole block: nothing is stored
+    const float A = is_x0 ? 0.f : p.ca[tv], Bc = is_x0 ? 0.f : p.cb[tv];
+    const float s = p.scale ? p.scale[b] : 0.f;
+    const int64_t base = (int64_t)b * N * C, half = (int64_t)p.b * N * C;
+    const int64_t row = base + (int64_t)tid * C;
+    double li[3] = {0., 0., 0.}, hi_i[3] = {0., 0., 0.};
+    float raw[3] = {0.f, 0.f, 0.f}, x0c[3] = {0.f, 0.f, 0.f};
+    bool is_free[3] = {false, false, false}, ok = false;
+    if (tid < N) {
+        const bool row_given = p.counts && tid < cnt;
+        const int64_t grow = ((int64_t)b * p.pmax + tid) * C;
+        float v[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int ch = k < 8 ? k : p.empty_col;
+            const bool given = row_given || (p.mask && p.mask[row + ch] != 0);
+            if (given) {
+                v[k] = row_given ? p.partial[grow + ch] : p.known[row + ch];
+            } else {
+                float m = p.mo[row + ch];
+                if (p.scale) m = cfg_mix(m, p.mo[half + row + ch], s);
+                const float r = predict_x0(is_x0 ? 0.f : p.xt[row + ch], m, A, Bc, p.mean_type, false);
+                v[k] = fminf(fmaxf(r, -1.0f), 1.0f);
+                if (k < 3) raw[k] = r, x0c[k] = v[k];
+            }
+            if (k < 3) is_free[k] = !given;
+        }
+        double ctr[3], sz[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ctr[k] = ((double)v[k] + 1.0) * 0.5 * p.c_span[k] + p.c_lo[k];
+            sz[k] = ((double)v[3 + k] + 1.0) * 0.5 * p.s_span[k] + p.s_lo[k];
+        }
+        const double cs = (double)v[6], sn = (double)v[7];
+        const double hyp = sqrt(cs * cs + sn * sn);
+        double ac = 1.0, as = 0.0;
+        if (hyp > 0.) ac = fabs(cs) / hyp, as = fabs(sn) / hyp;
+        const double h[3] = {ac * sz[0] + as * sz[2], sz[1], as * sz[0] + ac * sz[2]};
+        ok = v[8] < 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            li[k] = ctr[k] - h[k], hi_i[k] = ctr[k] + h[k];
+            lo[tid][k] = li[k], hi[tid][k] = hi_i[k];
+        }
+        valid[tid] = ok ? 1.f : 0.f;
+    }
+    __syncthreads();
+    double g[3] = {0., 0., 0.}, e = 0.;
+    if (ok) {
+        const double vi = (hi_i[0] - li[0]) * (hi_i[1] - li[1]) * (hi_i[2] - li[2]);
+        for (int j = 0; j < N; ++j) {
+            if (j == tid || valid[j] <= 0.f) continue;
+            double wh[3], sgn[3], ej[3];
+            bool hit = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double hj = hi[j][k], lj = lo[j][k];
+                ej[k] = hj - lj;
+                wh[k] = fmin(hi_i[k], hj) - fmax(li[k], lj);
+                hit = hit && wh[k] > 0.;
+                const double wr = hi_i[k] < hj ? 1. : (hi_i[k] == hj ? 0.5 : 0.);              // is the inner upper face box i's
+                const double wl = li[k] > lj ? 1. : (li[k] == lj ? 0.5 : 0.);                  // the inner lower face
+                sgn[k] = wr - wl;
+            }
+            if (!hit) continue;
+            const double vj = ej[0] * ej[1] * ej[2];
+            const double o = wh[0] * wh[1] * wh[2];
+            const double uraw = (vi + vj) - o;
+            const bool ucl = !(uraw > 1e-6);                                                  // the union at its floor
+            const double u = ucl ? 1e-6 : uraw;
+            const double iou = o / u;
+            if (j > tid) e += iou;
+            const double dio = ucl ? 1.0 / u : (1.0 + iou) / u;                               // d IoU / d overlap (d union / d overlap = -1)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) g[k] += dio * (wh[(k + 1) % 3] * wh[(k + 2) % 3]) * sgn[k];
+        }
+    }
+    const double E = block_sum_steer(e, red);
+    if (p.energy && first) p.energy[b] = (float)E;
+    if (tid >= N) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double gn = g[k] * p.c_span[k] * 0.5;                                           // d centre / d x0 = span / 2
+        if (p.grad) p.grad[((int64_t)b * N + tid) * 3 + k] = (float)gn;
+        if (!active || !ok || !is_free[k]) continue;
+        const double wg = (double)w * gn;
+        if (wg == 0. || (!is_x0 && Bc == 0.f)) continue;
+        const double d = wg + ((double)raw[k] - (double)x0c[k]);
+        const double delta = is_x0 ? -d : d / (double)Bc;
+        if (p.scale) {
+            const float c0 = p.mo[row + k], u0 = p.mo[half + row + k];
+            p.mo[row + k] = (float)((double)c0 + delta);
+            p.mo[half + row + k] = (float)((double)u0 + delta);
+        } else {
+            p.mo[row + k] = (float)((double)p.mo[row + k] + delta);
+        }
+    }
+}
+
 // Which elements of a scene are given (completion, in-painting) instead of sampled: none, the first counts[b] rows, or a byte mask.
 enum { GIVEN_NONE = 0, GIVEN_ROWS = 1, GIVEN_MASK = 2 };
 
@@ -690,6 +850,35 @@ extern "C" int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model
     a.ca = ca, a.cb = cb, a.ra = sqrt_recip_ac, a.rm = sqrt_recipm1_ac;
     a.mean_type = mean_type, a.b = b, a.inner = inner, a.S = num_steps, a.T = num_timesteps;
     return launch_step<true, GIVEN_MASK, true>(a, stream);
+}
+
+extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                                   const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                                   const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
+                                   const float* bounds, float* energy_out, float* grad_out, int32_t mean_type, int32_t b, int32_t n,
+                                   int32_t pmax, int32_t c, int32_t bbox_dim, int32_t class_dim, int32_t num_steps,
+                                   int32_t num_timesteps, dsc_stream_t stream) {
+    if (!model_out || !weight || !t_below || !bounds || b < 1 || n < 1 || c < 1 || num_timesteps < 1) return DSC_EINVAL;
+    if (t ? step || times : !step || !times || num_steps < 1) return DSC_EINVAL;            // one time source
+    if (bad_mean_args(mean_type, ca, cb) || (mean_type != DSC_MEAN_X0 && !x_t)) return DSC_EINVAL;
+    if ((partial != nullptr) != (counts != nullptr) || (known != nullptr) != (mask != nullptr) || (partial && known)) return DSC_EINVAL;
+    if (partial && (pmax < 1 || pmax > n)) return DSC_EINVAL;
+    if (class_dim < 1 || bbox_dim < 1 || bbox_dim + class_dim > c) return DSC_EINVAL;        // a re-arrangement sub-shape has no such layout
+    if (bbox_dim != 8 || n > STEER_MAXN) return DSC_ERANGE;                                  // [translation 3 | size 3 | cos, sin]
+    SteerArgs p{};
+    p.xt = x_t, p.mo = model_out, p.t = t, p.step = step, p.times = times, p.ca = ca, p.cb = cb;
+    p.partial = partial, p.counts = counts, p.known = known, p.mask = mask, p.scale = cfg_scale, p.weight = weight, p.t_below = t_below;
+    p.energy = energy_out, p.grad = grad_out;
+    p.mean_type = mean_type, p.b = b, p.n = n, p.pmax = partial ? pmax : 0, p.c = c, p.empty_col = bbox_dim + class_dim - 1;
+    p.S = t ? 0 : num_steps, p.T = num_timesteps;
+    for (int k = 0; k < 3; ++k) {
+        p.c_lo[k] = bounds[k], p.c_span[k] = (double)bounds[3 + k] - (double)bounds[k];
+        p.s_lo[k] = bounds[6 + k], p.s_span[k] = (double)bounds[9 + k] - (double)bounds[6 + k];
+    }
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(steer_boxes_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    DSC_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int dsc_scene_gate_f32(const float* x, const uint8_t* keep, float* y, int32_t b, int64_t inner, dsc_stream_t stream) {

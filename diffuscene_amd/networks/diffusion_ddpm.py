@@ -18,7 +18,8 @@ each a generator of states (x_T, then the state after every step), and two indep
   the given part   _FREE (nothing), _GivenRows / _GivenRagged (a dense / ragged row prefix), _GivenMask (a byte mask): drawn for and
                    written over the state in place BEFORE every model call, restored in the last state; x_T is cloned only if it is
                    written
-  the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine)
+  the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine); under ``collision_scale`` _steered wraps either:
+                   the model call, collision steering of its output in place (dsc_steer_boxes_f32), then the guidance mix
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
 part -- and then numbers its own draws: main stream x_T = 0, 1, 2, ..., given stream 0, 1, 2, ... (scene_noise.py).
 The public loops state their spec -- strided (S, eta) or not, the given part, the guidance scale -- and GaussianDiffusion._loop does the
@@ -86,6 +87,10 @@ class _Free:
     def finish(self, x):
         return x
 
+    def steer_operands(self):
+        """What the part adds to ops.steer_rec: a given element enters the boxes with its given value and is never moved."""
+        return {}
+
 
 _FREE = _Free()
 
@@ -114,6 +119,10 @@ class _GivenRows(_Given):
         x[:, :self.boxes.shape[1], :] = self.boxes
         return x
 
+    def steer_operands(self):
+        b, p = self.boxes.shape[:2]
+        return dict(rows=(self.boxes, None, torch.full((b,), p, device=self.boxes.device, dtype=torch.int64)))
+
 
 class _GivenRagged(_GivenRows):
     """Rows [0, counts[b]) of scene b are given by ``boxes`` (B, Pmax, C); ``counts``: (B,) int64 on the device (ops.ragged_counts)."""
@@ -128,6 +137,9 @@ class _GivenRagged(_GivenRows):
     def finish(self, x):
         return restore_given_rows(x, self.boxes, self.counts)
 
+    def steer_operands(self):
+        return dict(rows=(self.boxes, None, self.counts))
+
 
 class _GivenMask(_Given):
     """The elements marked by ``mask`` (B, N, C) uint8 (ops.known_mask) are given by ``known``.  One draw of the full shape per step."""
@@ -141,6 +153,9 @@ class _GivenMask(_Given):
 
     def finish(self, x):
         return torch.where(self.mask != 0, self.known, x)
+
+    def steer_operands(self):
+        return dict(mask=(self.known, None, self.mask))
 
 
 def restore_given_rows(x, boxes, counts):
@@ -160,6 +175,25 @@ def _guided_model(denoise_fn, cond2, cross2, scale):
     """The guided model call: the denoiser at 2 B on the same x and t in both halves (conditions of _guided_inputs), then
     m = u + scale[b] * (c - u) (dsc_cfg_combine_f32)."""
     return lambda x, t_: ops.cfg_combine(denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), cond2, cross2).contiguous(), scale)
+
+
+def _steered(model, diff, device, steer, part, scale=None):
+    """The model call of a steered loop: ``model`` -- under guidance the denoiser at 2 B, ``scale`` its (B,) scales --, then collision
+    steering of its output in place (dsc_steer_boxes_f32), then the guidance mix: the launches of the captured loop, in its order."""
+    weight, k, bounds, bbox_dim, class_dim = steer
+    ca, cb = diff._coeffs(diff.tables(device))
+    spec = (weight, torch.full((1,), k, device=device, dtype=torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim)
+
+    def call(x, t_):
+        mo = model(x, t_).contiguous()
+        ops.issue(ops.steer_rec(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale, **part.steer_operands()))
+        return mo if scale is None else ops.cfg_combine(mo, scale)
+    return call
+
+
+def _steer_kw(collision_scale, collision_steps):
+    """The steering keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
+    return {} if collision_scale is None and collision_steps is None else dict(steer=(collision_scale, collision_steps))
 
 
 def _arm(noise_fn, given):
@@ -187,6 +221,7 @@ class GaussianDiffusion:
         self.objfeat_dim = config.get("objfeat_dim", 0)
         self.loss_separate = loss_separate
         self.loss_iou = loss_iou
+        self.train_stats_file = train_stats_file
         if self.loss_iou:
             with open(train_stats_file, "r") as f:
                 train_stats = json.load(f)
@@ -458,19 +493,22 @@ class GaussianDiffusion:
             yield given.finish(x) if last else x        # not a copy, as in _t_states
 
     def p_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
-                      clip_denoised=True, keep_running=False, graph=None):
+                      clip_denoised=True, keep_running=False, graph=None,
+                      collision_scale=None, collision_steps=None):
         """Generate samples, reference :355-371 (draw order: x_T, then one draw per step)."""
         return self._loop("p_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          clip_denoised=clip_denoised, keep_running=keep_running)
+                          clip_denoised=clip_denoised, keep_running=keep_running,
+                          **_steer_kw(collision_scale, collision_steps))
 
     def _loop(self, what, denoise_fn, shape, device, condition, condition_cross, noise_fn, graph, strided=None, given=None, scale=None,
-              clip_denoised=True, keep_running=False, say_last=False, all_states=False):
+              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None):
         """What every public loop does behind its signature.  The spec: ``strided`` = (sampling_timesteps, ddim_sampling_eta) or None for
         T steps; ``given`` = None, ("dense", partial_boxes), ("ragged", partial_boxes, num_partial) or ("mask", known, mask); ``scale`` =
         the guidance scale or None.  Validates (ValueError names ``what``), keeps (eta, S) on the instance as the reference does (:404-405),
         hands over to the captured loop under _use_graph -- the front end front_end_name(spec) of sampler.py, looked up when called -- and
         otherwise runs the eager core on the given part and the model call of the spec.  ``say_last``: the reference's print, after the
-        eager loop / before the captured one; ``all_states``: the list of states (eager)."""
+        eager loop / before the captured one; ``all_states``: the list of states (eager).  ``steer`` = (collision_scale, collision_steps)
+        or None: collision steering after every model call (_steer_inputs), on either path."""
         assert isinstance(shape, (tuple, list))
         if strided is not None:
             S, eta = _check_ddim(self.num_timesteps, *strided)
@@ -481,6 +519,8 @@ class GaussianDiffusion:
             values = self._ragged_inputs(shape, device, *values, what)
         elif kind == "mask":
             values = self._masked_inputs(shape, device, *values, what)
+        if steer is not None:
+            steer = self._steer_inputs(shape, device, *steer, what)
         if scale is not None:
             condition, condition_cross, scale = self._guided_inputs(shape, device, condition, condition_cross, scale, what)
         if strided is not None:
@@ -494,10 +534,16 @@ class GaussianDiffusion:
                 self._say_last()
             front = getattr(sampler, front_end_name(strided is not None, kind, scale is not None))
             return front(self, denoise_fn, tuple(shape), device, condition, condition_cross, *(() if scale is None else (scale,)), *sched,
-                         noise_fn, *values)
-        model = _model(denoise_fn, condition, condition_cross) if scale is None else _guided_model(denoise_fn, condition, condition_cross, scale)
+                         noise_fn, *values, **({} if steer is None else dict(steer=steer)))
         part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
             self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
+        if steer is None:
+            model = _model(denoise_fn, condition, condition_cross) if scale is None else _guided_model(denoise_fn, condition, condition_cross, scale)
+        elif scale is None:
+            model = _steered(_model(denoise_fn, condition, condition_cross), self, device, steer, part)
+        else:                                   # the denoiser at 2 B, steered with the scales, then mixed
+            model = _steered(lambda x, t_: denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), condition, condition_cross),
+                             self, device, steer, part, scale)
         if strided is not None:
             states = self._strided_states(model, shape, device, noise_fn, S, eta, part)
         elif scale is not None and kind is None:        # p_sample_loop_guided: the device check before the first draw, its own draw keywords
@@ -578,14 +624,16 @@ class GaussianDiffusion:
 
     @torch.no_grad()
     def ddim_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
-                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None):
+                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None,
+                         collision_scale=None, collision_steps=None):
         """DDIM sampling, reference :402-444 (its two call-site slips bridged: model_predictions gets ``denoise_fn``, and there is no
         self-conditioning).  Draw order: x_T, then one draw per pair except the last ((t, -1) takes x_start): S draws in all.
         x_start is always clamped to [-1, 1], as in the reference, whatever ``clip_denoised`` says.  The network runs on the static
         plan, each update is one HIP kernel (dsc_ddim_step_f32); by default (``graph=None``, the rules of p_sample_loop) the loop is a
         replayed hipGraph step.  ``return_all_timesteps=True`` returns the S + 1 states (eager loop)."""
         return self._loop("ddim_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          strided=(sampling_timesteps, ddim_sampling_eta), all_states=return_all_timesteps)
+                          strided=(sampling_timesteps, ddim_sampling_eta), all_states=return_all_timesteps,
+                          **_steer_kw(collision_scale, collision_steps))
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
@@ -603,9 +651,49 @@ class GaussianDiffusion:
             cond2 = condition[:1].expand(2 * B, -1, -1) if condition.stride(0) == 0 else torch.cat([condition, condition], dim=0).contiguous()
         return cond2, cross2, scale
 
+    # ------------------------------------------------------------------ collision steering
+    def box_bounds(self):
+        """The de-normalisation bounds of the boxes, 12 floats (translation lo[3], hi[3], size lo[3], hi[3]), from the train-stats file
+        (``bounds_translations`` / ``bounds_sizes``); loaded on first use whether or not ``loss_iou`` is set."""
+        hit = getattr(self, "_box_bounds", None)
+        if hit is None:
+            if self.loss_iou:
+                c, s = np.concatenate(self._centroids), np.concatenate(self._sizes)
+            else:
+                if not self.train_stats_file:
+                    raise ValueError("collision_scale needs the de-normalisation bounds of the boxes: set train_stats_file "
+                                     "(diffusion_kwargs) to the dataset's statistics file")
+                with open(self.train_stats_file, "r") as f:
+                    train_stats = json.load(f)
+                c, s = train_stats["bounds_translations"], train_stats["bounds_sizes"]
+            hit = self._box_bounds = tuple(float(v) for v in np.float32(list(c) + list(s)))
+            if len(hit) != 12:
+                raise ValueError("train_stats_file: bounds_translations and bounds_sizes must hold 6 numbers each")
+        return hit
+
+    def _steer_inputs(self, shape, device, collision_scale, collision_steps, what):
+        """(weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim) of a steered loop (ops.steer_rec), or ValueError -- before
+        anything is drawn.  At every step whose t < K the clamped x0 estimate of scene b moves by -weight[b] * d E / d x0[:, 0:3], E the
+        pairwise IoU of its non-empty boxes; ``collision_steps`` None steers every step."""
+        B, N, C = shape
+        if collision_scale is None:
+            raise ValueError("%s: collision_steps goes with collision_scale" % what)
+        if (self.translation_dim, self.size_dim, self.angle_dim) != (3, 3, 2):
+            raise ValueError("%s: collision steering needs translation_dim = 3, size_dim = 3 and angle_dim = 2 (cos, sin), got %d / %d / %d"
+                             % (what, self.translation_dim, self.size_dim, self.angle_dim))
+        if self.class_dim < 1 or C < self.bbox_dim + self.class_dim:
+            raise ValueError("%s: collision steering needs the full object layout, at least %d channels, got %d"
+                             % (what, self.bbox_dim + max(self.class_dim, 1), C))
+        if N > ops.STEER_MAX_OBJECTS:
+            raise ValueError("%s: collision steering handles at most %d objects per scene, got %d" % (what, ops.STEER_MAX_OBJECTS, N))
+        weight = ops.collision_scales(collision_scale, B, "cpu")
+        k = ops.collision_steps(collision_steps, self.num_timesteps)
+        return weight.to(device), k, self.box_bounds(), self.bbox_dim, self.class_dim
+
     @torch.no_grad()
     def p_sample_loop_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
-                             clip_denoised=True, keep_running=False, graph=None):
+                             clip_denoised=True, keep_running=False, graph=None,
+                             collision_scale=None, collision_steps=None):
         """Classifier-free guidance in T steps.  Scene b is the reference's p_sample_loop (:355-371) with
         m = u + w[b] * (c - u) in place of the model output inside p_mean_variance: c the denoiser on (x, t, condition, condition_cross),
         u the denoiser on (x, t, condition, 0) -- the null condition is condition_cross == 0, the features AFTER fc_text_f --, the
@@ -616,30 +704,36 @@ class GaussianDiffusion:
         unfused pieces -- the denoiser at 2 B, cfg_combine, p_sample; the graph path (the default, by the rules of p_sample_loop)
         replays one captured step whose update is the fused dsc_p_sample_cfg_f32, bit-identical."""
         return self._loop("p_sample_loop_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running)
+                          scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
-                         sampling_timesteps=50, ddim_sampling_eta=0., graph=None):
+                         sampling_timesteps=50, ddim_sampling_eta=0., graph=None,
+                         collision_scale=None, collision_steps=None):
         """Classifier-free guidance in S strided (DDIM) steps: scene b is the reference's ddim_sample_loop (:402-444) with the guided
         output m of p_sample_loop_guided in place of the model output inside model_predictions.  x_start is always clamped to [-1, 1].
         Draws: exactly those of ddim_sample_loop at batch B (x_T, then one per pair except the last).  The eager loop is built from the
         unfused pieces (the denoiser at 2 B, cfg_combine, ddim_step); the graph path replays one captured step whose update is the fused
         dsc_ddim_cfg_step_f32, bit-identical."""
         return self._loop("ddim_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          strided=(sampling_timesteps, ddim_sampling_eta), scale=guidance_scale)
+                          strided=(sampling_timesteps, ddim_sampling_eta), scale=guidance_scale,
+                          **_steer_kw(collision_scale, collision_steps))
 
     # ------------------------------------------------------------------ completion, in-painting, re-arrangement
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
-                               clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
+                               clip_denoised=True, keep_running=False, partial_boxes=None, graph=None,
+                               collision_scale=None, collision_steps=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
         model call) and overwrites the first P rows of x_t in place; at t == 0 the clean objects are restored."""
         return self._loop("p_sample_loop_complete", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          given=("dense", partial_boxes), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True)
+                          given=("dense", partial_boxes), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def p_sample_loop_complete_ragged(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
-                                      clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None):
+                                      clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None,
+                                      collision_scale=None, collision_steps=None):
         """Scene completion of a batch whose scenes are given DIFFERENT numbers of objects.  ``partial_boxes`` is (B, Pmax, C) with
         1 <= Pmax <= N, ``num_partial`` the (B,) integer counts, 0 <= num_partial[b] <= Pmax; rows >= num_partial[b] of scene b are
         padding and never read.  Scene b is the reference's p_sample_loop_complete (:447-476) run on that scene alone with
@@ -648,11 +742,13 @@ class GaussianDiffusion:
         This eager loop is built from the unfused pieces -- ragged overwrite, p_sample, restore; the graph path (the default, by the
         rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
         return self._loop("p_sample_loop_complete_ragged", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          given=("ragged", partial_boxes, num_partial), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True)
+                          given=("ragged", partial_boxes, num_partial), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
-                                  sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None):
+                                  sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None,
+                                  collision_scale=None, collision_steps=None):
         """Strided (DDIM) scene completion of a batch with per-scene numbers of given objects.  Scene b is ddim_sample_loop (reference
         :402-444) run on that scene alone with ONE addition taken from p_sample_loop_complete (:447-476): before every model call at pair
         (t, t_next) the first num_partial[b] rows of the state are overwritten in place with q_sample(partial_boxes[b], t, fresh noise);
@@ -667,7 +763,8 @@ class GaussianDiffusion:
         restore; the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
         dsc_ddim_inpaint_step_f32, bit-identical."""
         return self._loop("ddim_complete_ragged_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial))
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial),
+                          **_steer_kw(collision_scale, collision_steps))
 
     def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
         """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
@@ -689,7 +786,8 @@ class GaussianDiffusion:
 
     @torch.no_grad()
     def p_sample_loop_masked(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
-                             keep_running=False, known=None, mask=None, graph=None):
+                             keep_running=False, known=None, mask=None, graph=None,
+                             collision_scale=None, collision_steps=None):
         """Element-wise in-painting in T steps.  ``known`` is (B, N, C) f32 in the network's encoding, ``mask`` (B, N, C) or (B, N) bool /
         uint8 (ops.known_mask), non-zero = this element is given.  Scene b is the reference's p_sample_loop_complete (:447-476) on that
         scene alone with its two torch.cat's replaced by a select: before the model call at step t,
@@ -700,11 +798,13 @@ class GaussianDiffusion:
         ``known``.  This eager loop is built from the unfused pieces -- masked overwrite, p_sample, select; the graph path (the default,
         by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
         return self._loop("p_sample_loop_masked", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          given=("mask", known, mask), clip_denoised=clip_denoised, keep_running=keep_running)
+                          given=("mask", known, mask), clip_denoised=clip_denoised, keep_running=keep_running,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
-                         ddim_sampling_eta=0., known=None, mask=None, graph=None):
+                         ddim_sampling_eta=0., known=None, mask=None, graph=None,
+                         collision_scale=None, collision_steps=None):
         """Element-wise in-painting in S strided (DDIM) steps; ``known`` / ``mask`` as in p_sample_loop_masked.  Scene b is ddim_sample_loop
         (reference :402-444) on that scene alone: before every model call at pair (t, t_next),
         x = where(mask, q_sample(known, t, fresh noise), x); after the last pair, x = where(mask, known, x).  x_start is always clamped
@@ -713,11 +813,13 @@ class GaussianDiffusion:
         whole rows [0, counts[b]) returns what that loop returns, bit for bit.  The eager loop is built from the unfused pieces; the
         graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
         return self._loop("ddim_masked_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask))
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask),
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
-                                    clip_denoised=True, keep_running=False, known=None, mask=None, graph=None):
+                                    clip_denoised=True, keep_running=False, known=None, mask=None, graph=None,
+                                    collision_scale=None, collision_steps=None):
         """Text-guided element-wise in-painting in T steps: scene b is p_sample_loop_masked with m = u + w[b] * (c - u) in place of the
         model output (c, u and ``guidance_scale`` as in p_sample_loop_guided; ``known`` / ``mask`` as in p_sample_loop_masked).  Both
         halves of the 2 B model call see the same overwritten x_t.  Draws: exactly those of p_sample_loop_masked at batch B, in its
@@ -725,17 +827,20 @@ class GaussianDiffusion:
         the graph path (the default, by the rules of p_sample_loop) replays one captured step whose update is the fused
         dsc_p_sample_masked_cfg_f32, bit-identical."""
         return self._loop("p_sample_loop_masked_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          given=("mask", known, mask), scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running)
+                          given=("mask", known, mask), scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
-                                sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None):
+                                sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None,
+                                collision_scale=None, collision_steps=None):
         """Text-guided element-wise in-painting in S strided (DDIM) steps: scene b is ddim_masked_loop with the guided output m of
         p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
         ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
         step whose update is the fused dsc_ddim_masked_cfg_step_f32, bit-identical."""
         return self._loop("ddim_masked_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
-                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale)
+                          strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale,
+                          **_steer_kw(collision_scale, collision_steps))
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
@@ -938,10 +1043,10 @@ class DiffusionPoint(nn.Module):
         return losses.mean(), loss_dict
 
     def gen_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
-                    clip_denoised=True, keep_running=False, graph=None):
+                    clip_denoised=True, keep_running=False, graph=None, **steer):
         return self.diffusion.p_sample_loop(self._denoise, shape=shape, device=device, condition=condition,
                                             condition_cross=condition_cross, noise_fn=noise_fn,
-                                            clip_denoised=clip_denoised, keep_running=keep_running, graph=graph)
+                                            clip_denoised=clip_denoised, keep_running=keep_running, graph=graph, **steer)
 
     def gen_sample_traj(self, shape, device, freq, condition=None, condition_cross=None, noise_fn=torch.randn,
                         clip_denoised=True, keep_running=False):
@@ -950,79 +1055,79 @@ class DiffusionPoint(nn.Module):
                                                        clip_denoised=clip_denoised, keep_running=keep_running)
 
     def gen_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, clip_denoised=True,
-                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None):
+                         sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None, **steer):
         return self.diffusion.ddim_sample_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                condition_cross=condition_cross, noise_fn=noise_fn, clip_denoised=clip_denoised,
                                                sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                               return_all_timesteps=return_all_timesteps, graph=graph)
+                                               return_all_timesteps=return_all_timesteps, graph=graph, **steer)
 
     def gen_samples_guided(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
-                           clip_denoised=True, keep_running=False, graph=None):
+                           clip_denoised=True, keep_running=False, graph=None, **steer):
         """gen_samples under classifier-free guidance (p_sample_loop_guided)."""
         return self.diffusion.p_sample_loop_guided(self._denoise, shape=shape, device=device, condition=condition,
                                                    condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
-                                                   clip_denoised=clip_denoised, keep_running=keep_running, graph=graph)
+                                                   clip_denoised=clip_denoised, keep_running=keep_running, graph=graph, **steer)
 
     def gen_samples_guided_ddim(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
-                                sampling_timesteps=50, ddim_sampling_eta=0., graph=None):
+                                sampling_timesteps=50, ddim_sampling_eta=0., graph=None, **steer):
         """gen_samples_guided in S strided steps (ddim_guided_loop)."""
         return self.diffusion.ddim_guided_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
-                                               sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph)
+                                               sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph, **steer)
 
     def complete_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
-                         clip_denoised=True, keep_running=False, partial_boxes=None, graph=None):
+                         clip_denoised=True, keep_running=False, partial_boxes=None, graph=None, **steer):
         return self.diffusion.p_sample_loop_complete(self._denoise, shape=shape, device=device, condition=condition,
                                                      condition_cross=condition_cross, noise_fn=noise_fn,
                                                      clip_denoised=clip_denoised, keep_running=keep_running,
-                                                     partial_boxes=partial_boxes, graph=graph)
+                                                     partial_boxes=partial_boxes, graph=graph, **steer)
 
     def complete_samples_ragged(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
-                                clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None):
+                                clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None, **steer):
         """complete_samples for a batch with per-scene numbers of given objects (p_sample_loop_complete_ragged)."""
         return self.diffusion.p_sample_loop_complete_ragged(self._denoise, shape=shape, device=device, condition=condition,
                                                             condition_cross=condition_cross, noise_fn=noise_fn,
                                                             clip_denoised=clip_denoised, keep_running=keep_running,
-                                                            partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
+                                                            partial_boxes=partial_boxes, num_partial=num_partial, graph=graph, **steer)
 
     def complete_samples_ragged_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
-                                     sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None):
+                                     sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None, **steer):
         """complete_samples_ragged in S strided steps (ddim_complete_ragged_loop)."""
         return self.diffusion.ddim_complete_ragged_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                         condition_cross=condition_cross, noise_fn=noise_fn,
                                                         sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                        partial_boxes=partial_boxes, num_partial=num_partial, graph=graph)
+                                                        partial_boxes=partial_boxes, num_partial=num_partial, graph=graph, **steer)
 
     def inpaint_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, clip_denoised=True,
-                        keep_running=False, known=None, mask=None, graph=None):
+                        keep_running=False, known=None, mask=None, graph=None, **steer):
         """Element-wise in-painting: the elements marked by ``mask`` are held at ``known`` (p_sample_loop_masked)."""
         return self.diffusion.p_sample_loop_masked(self._denoise, shape=shape, device=device, condition=condition,
                                                    condition_cross=condition_cross, noise_fn=noise_fn, clip_denoised=clip_denoised,
-                                                   keep_running=keep_running, known=known, mask=mask, graph=graph)
+                                                   keep_running=keep_running, known=known, mask=mask, graph=graph, **steer)
 
     def inpaint_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn, sampling_timesteps=50,
-                             ddim_sampling_eta=0., known=None, mask=None, graph=None):
+                             ddim_sampling_eta=0., known=None, mask=None, graph=None, **steer):
         """inpaint_samples in S strided steps (ddim_masked_loop)."""
         return self.diffusion.ddim_masked_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                condition_cross=condition_cross, noise_fn=noise_fn,
                                                sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                               known=known, mask=mask, graph=graph)
+                                               known=known, mask=mask, graph=graph, **steer)
 
     def inpaint_samples_guided(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
-                               clip_denoised=True, keep_running=False, known=None, mask=None, graph=None):
+                               clip_denoised=True, keep_running=False, known=None, mask=None, graph=None, **steer):
         """inpaint_samples under classifier-free guidance (p_sample_loop_masked_guided)."""
         return self.diffusion.p_sample_loop_masked_guided(self._denoise, shape=shape, device=device, condition=condition,
                                                           condition_cross=condition_cross, guidance_scale=guidance_scale,
                                                           noise_fn=noise_fn, clip_denoised=clip_denoised, keep_running=keep_running,
-                                                          known=known, mask=mask, graph=graph)
+                                                          known=known, mask=mask, graph=graph, **steer)
 
     def inpaint_samples_guided_ddim(self, shape, device, condition=None, condition_cross=None, guidance_scale=1.0, noise_fn=torch.randn,
-                                    sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None):
+                                    sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None, **steer):
         """inpaint_samples_guided in S strided steps (ddim_masked_guided_loop)."""
         return self.diffusion.ddim_masked_guided_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                       condition_cross=condition_cross, guidance_scale=guidance_scale, noise_fn=noise_fn,
                                                       sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                      known=known, mask=mask, graph=graph)
+                                                      known=known, mask=mask, graph=graph, **steer)
 
     def arrange_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                              sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None):

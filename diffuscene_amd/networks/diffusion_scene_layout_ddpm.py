@@ -288,7 +288,8 @@ class DiffusionSceneLayout_DDPM(Module):
 
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
                input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
-               sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None):
+               sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None,
+               collision_steps=None):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
@@ -300,9 +301,15 @@ class DiffusionSceneLayout_DDPM(Module):
         and u the denoiser on the null condition (condition_cross == 0) (``gen_samples_guided`` / ``gen_samples_guided_ddim`` with
         ``sampling_timesteps``).  Generation only; needs ``text``.
         ``scene_seeds`` (None: the device generator, this method as it was): one seed per scene, see ``_seeded``; combines with every
-        other keyword.  ``batch_seeds`` stays accepted and ignored (``honour_batch_seeds``)."""
+        other keyword.  ``batch_seeds`` stays accepted and ignored (``honour_batch_seeds``).
+        ``collision_scale`` (None: this method as it was): a float or ``batch_size`` per-scene weights w >= 0 of collision steering --
+        after every model call whose timestep is below ``collision_steps`` (None: every step; an integer K: the last K timesteps) the
+        clamped x0 estimate of scene b moves by -w[b] * dE/d(translations), E the summed pairwise IoU of its non-empty boxes
+        (GaussianDiffusion._steer_inputs).  Generation and completion, T-step and strided, guided or not, seeded or
+        not; re-arrangement and ``ret_traj`` refuse it.  Needs the train-stats file for the de-normalisation bounds."""
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
+        steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, ret_traj)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
                                       "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
@@ -327,7 +334,7 @@ class DiffusionSceneLayout_DDPM(Module):
             print('scene completion sampling')
             return self.diffusion.complete_samples(noise.shape, device, condition=condition,
                                                    condition_cross=condition_cross, clip_denoised=clip_denoised,
-                                                   partial_boxes=partial_boxes, **seeded)
+                                                   partial_boxes=partial_boxes, **seeded, **steer)
         print('unconditional / conditional generation sampling')
         if guidance_scale is not None:
             if condition_cross is None or condition_cross.dim() != 3:
@@ -339,18 +346,31 @@ class DiffusionSceneLayout_DDPM(Module):
             if sampling_timesteps is not None:
                 return self.diffusion.gen_samples_guided_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                               guidance_scale=scale, sampling_timesteps=sampling_timesteps,
-                                                              ddim_sampling_eta=ddim_sampling_eta, **seeded)
+                                                              ddim_sampling_eta=ddim_sampling_eta, **seeded, **steer)
             return self.diffusion.gen_samples_guided(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                                     guidance_scale=scale, clip_denoised=clip_denoised, **seeded)
+                                                     guidance_scale=scale, clip_denoised=clip_denoised, **seeded, **steer)
         if sampling_timesteps is not None:
             return self.diffusion.gen_samples_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                    clip_denoised=clip_denoised, sampling_timesteps=sampling_timesteps,
-                                                   ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj), **seeded)
+                                                   ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj), **seeded,
+                                                   **steer)
         if ret_traj:
             return self.diffusion.gen_sample_traj(noise.shape, device, freq=freq, condition=condition,
                                                   condition_cross=condition_cross, clip_denoised=clip_denoised, **seeded)
         return self.diffusion.gen_samples(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                          clip_denoised=clip_denoised, **seeded)
+                                          clip_denoised=clip_denoised, **seeded, **steer)
+
+    def _check_steer(self, collision_scale, collision_steps, shape, input_boxes=None, ret_traj=False, what="sample"):
+        """The refusals of ``collision_scale`` / ``collision_steps``, before anything is computed or drawn -> the keywords the loop
+        receives: none at all without steering, so that call stays what it was."""
+        if collision_scale is None and collision_steps is None:
+            return {}
+        if input_boxes is not None or self.room_arrange_condition:
+            raise ValueError("collision_scale: re-arrangement diffuses [translation | angle] only, the boxes are not steered there")
+        if ret_traj:
+            raise ValueError("collision_scale: the steered loops return the final scenes only (ret_traj is not supported)")
+        self.diffusion.diffusion._steer_inputs(tuple(int(v) for v in shape), "cpu", collision_scale, collision_steps, what)
+        return dict(collision_scale=collision_scale, collision_steps=collision_steps)
 
     def _check_guidance(self, text, partial_boxes=None, input_boxes=None, ret_traj=False):
         """The refusals of ``guidance_scale``, before anything is computed or drawn."""
@@ -367,10 +387,11 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
                         clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                        ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None):
+                        ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
                               clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
-                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds))
+                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
+                              **_steer_kwargs(collision_scale, collision_steps))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -395,7 +416,7 @@ class DiffusionSceneLayout_DDPM(Module):
         return _check_ddim(int(self.config["diffusion_kwargs"].get("time_num", 1000)), sampling_timesteps, ddim_sampling_eta)
 
     def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta,
-                          seeded={}):
+                          seeded={}, steer={}):
         """The strided completion call behind complete_scene / complete_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``complete_samples_ragged_ddim``."""
         device = room_mask.device
@@ -407,7 +428,7 @@ class DiffusionSceneLayout_DDPM(Module):
         return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                            condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
                                                            sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                           **seeded)
+                                                           **seeded, **steer)
 
     def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta,
                          seeded={}):
@@ -426,26 +447,30 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                       ddim_sampling_eta=0.0, scene_seeds=None):
+                       ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
         """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
         every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
-        x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part."""
+        x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part.  ``collision_scale`` / ``collision_steps``:
+        collision steering (see ``sample``); the given objects repel the free ones and are never moved."""
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
+            steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
                               ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds,
-                              **_seed_kwargs(scene_seeds))
+                              **_seed_kwargs(scene_seeds), **_steer_kwargs(collision_scale, collision_steps))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene(self, room_mask, num_points, point_dim, input_boxes, batch_size=1, ret_traj=False, ddim=False,
                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                      ddim_sampling_eta=0.0, scene_seeds=None):
-        """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop."""
+                      ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
+        """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop.
+        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only."""
+        self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
@@ -510,13 +535,15 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
                                 batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                                guidance_scale=None, scene_seeds=None):
+                                guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None):
         """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own.
         ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``).  ``scene_seeds``: one seed per
-        scene (``_seeded``): scene b can then be regenerated alone, or the batch split over calls and devices."""
+        scene (``_seeded``): scene b can then be regenerated alone, or the batch split over calls and devices.  ``collision_scale`` /
+        ``collision_steps``: collision steering, a weight per scene (see ``sample``)."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
-                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds))
+                              **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
+                              **_steer_kwargs(collision_scale, collision_steps))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
@@ -565,7 +592,7 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
                                clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
-                               ddim_sampling_eta=0.0, scene_seeds=None):
+                               ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
@@ -574,15 +601,18 @@ class DiffusionSceneLayout_DDPM(Module):
         reference's cat([partial, zeros]) of each scene.  Returns a list of B dicts; given rows are filtered like any other row.
         ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim``: S DDIM steps at ``ddim_sampling_eta``, the
         given rows re-noised with fresh noise before every model call -- so at eta = 0 the free rows are deterministic given x_T and
-        those draws, not given x_T alone; x_start always clamped, ``clip_denoised`` ignored) instead of the T-step one."""
+        those draws, not given x_T alone; x_start always clamped, ``clip_denoised`` ignored) instead of the T-step one.
+        ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); the given objects repel the
+        free ones and are never moved."""
         device = room_mask.device
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
         seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
@@ -591,14 +621,18 @@ class DiffusionSceneLayout_DDPM(Module):
         condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
         print('scene completion sampling')
         samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded)
+                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded,
+                                                         **steer)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
-                              batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0, scene_seeds=None):
+                              batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0, scene_seeds=None,
+                              collision_scale=None, collision_steps=None):
         """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
-        each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead."""
+        each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead.
+        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only."""
+        self._check_steer(collision_scale, collision_steps, (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
             raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
         if batch_size is None:
@@ -677,7 +711,7 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                              scene_seeds=None, guidance_scale=None):
+                              scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -689,7 +723,9 @@ class DiffusionSceneLayout_DDPM(Module):
         ``guidance_scale`` (None: this method as it was, same code path, same draws): a float or B per-scene classifier-free guidance
         scales of a text-conditioned model, as in ``sample`` -- the fixed elements pull the sample away from the prompt, the scale pulls
         it back (``inpaint_samples_guided`` / ``inpaint_samples_guided_ddim``).  Needs ``text``; refused, before anything is drawn, on a
-        model without ``text_condition`` and on a text encoder that does not give (B, L, text_embed_dim) features."""
+        model without ``text_condition`` and on a text encoder that does not give (B, L, text_embed_dim) features.
+        ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); a known element enters the
+        boxes with its known value and is never moved."""
         from .. import ops
         if self.room_partial_condition or self.room_arrange_condition:
             raise ValueError("inpaint_scene_batched: a room_partial_condition / room_arrange_condition model conditions on a prefix / a "
@@ -701,6 +737,7 @@ class DiffusionSceneLayout_DDPM(Module):
             batch_size = len(boxes) if isinstance(boxes, (list, tuple)) else int(boxes.shape[0])
         B, N, C = int(batch_size), int(num_points), int(point_dim)
         scale = None if guidance_scale is None else ops.guidance_scales(guidance_scale, B, "cpu")   # checked on the host; the loop uploads it
+        steer = self._check_steer(collision_scale, collision_steps, (B, N, C), what="inpaint_scene_batched")
         seeded = self._seeded(scene_seeds, batch_seeds, B, device)
         if isinstance(boxes, (list, tuple)):
             if len(boxes) != B:
@@ -737,7 +774,8 @@ class DiffusionSceneLayout_DDPM(Module):
             condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
         print('scene in-painting sampling')
         if scale is not None:
-            guided = dict(condition=condition, condition_cross=condition_cross, guidance_scale=scale, known=known, mask=mask, **seeded)
+            guided = dict(condition=condition, condition_cross=condition_cross, guidance_scale=scale, known=known, mask=mask, **seeded,
+                          **steer)
             if sampling_timesteps is not None:
                 samples = self.diffusion.inpaint_samples_guided_ddim((B, N, C), device, sampling_timesteps=S, ddim_sampling_eta=eta,
                                                                      **guided)
@@ -745,10 +783,11 @@ class DiffusionSceneLayout_DDPM(Module):
                 samples = self.diffusion.inpaint_samples_guided((B, N, C), device, clip_denoised=clip_denoised, **guided)
         elif sampling_timesteps is not None:
             samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
-                                                          known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded)
+                                                          known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded,
+                                                          **steer)
         else:
             samples = self.diffusion.inpaint_samples((B, N, C), device, condition=condition, condition_cross=condition_cross,
-                                                     clip_denoised=clip_denoised, known=known, mask=mask, **seeded)
+                                                     clip_denoised=clip_denoised, known=known, mask=mask, **seeded, **steer)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -771,6 +810,13 @@ def _ddim_kwargs(sampling_timesteps, ddim_sampling_eta):
 def _seed_kwargs(scene_seeds):
     """The seed keyword ``sample`` receives: none at all without seeds, so that call stays what it was."""
     return {} if scene_seeds is None else dict(scene_seeds=scene_seeds)
+
+
+def _steer_kwargs(collision_scale, collision_steps):
+    """The steering keywords ``sample`` receives: none at all without steering, so that call stays what it was."""
+    if collision_scale is None and collision_steps is None:
+        return {}
+    return dict(collision_scale=collision_scale, collision_steps=collision_steps)
 
 
 def _guidance_kwargs(guidance_scale):

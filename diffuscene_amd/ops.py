@@ -872,6 +872,140 @@ def ddim_masked_cfg_step(x_t, model_out, scale, noise, known, noise_k, mask, ste
     return out
 
 
+# ---------------------------------------------------------------------------------- collision steering
+
+STEER_MAX_OBJECTS = 160            # one block per scene, one thread per box (csrc/diffusion.hip: STEER_MAXN)
+
+
+def collision_scales(scale, b, device):
+    """The per-scene steering weights of dsc_steer_boxes_f32 as a contiguous (b,) f32 tensor on ``device``.  ``scale``: a float (every
+    scene) or b values, as guidance_scales takes them, each finite and >= 0; 0 leaves that scene unsteered.  ValueError otherwise."""
+    try:
+        w = guidance_scales(scale, b, "cpu")
+    except ValueError as e:
+        raise ValueError(str(e).replace("guidance_scale", "collision_scale")) from None
+    for i, v in enumerate(w.tolist()):
+        if v < 0:
+            raise ValueError("collision_scale: scene %d: %r is negative" % (i, v))
+    return w.to(device).contiguous()
+
+
+def collision_steps(steps, num_timesteps):
+    """K of dsc_steer_boxes_f32: a step at timestep t is steered iff t < K.  ``steps``: None (every step, K = num_timesteps) or an
+    integer in [0, num_timesteps] -- the last K timesteps of the schedule; a strided loop steers the pairs whose t is below K."""
+    if steps is None:
+        return int(num_timesteps)
+    if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or not 0 <= int(steps) <= num_timesteps:
+        raise ValueError("collision_steps must be None or an integer in [0, %d], got %r" % (num_timesteps, steps))
+    return int(steps)
+
+
+def steer_bounds(bounds):
+    """The 12 host floats of dsc_steer_boxes_f32 / dsc_ddpm_loss_f32 -- translation lo[3], hi[3], size lo[3], hi[3] -- as a ctypes array;
+    ValueError unless there are 12 finite numbers."""
+    if isinstance(bounds, C.c_float * 12):
+        return bounds
+    try:
+        host = [float(v) for v in (bounds.tolist() if isinstance(bounds, torch.Tensor) else bounds)]
+    except (TypeError, ValueError):
+        raise ValueError("bounds must be 12 numbers (translation lo, hi, size lo, hi), got %r" % (bounds,)) from None
+    if len(host) != 12 or any(v != v or v in (float("inf"), float("-inf")) for v in host):
+        raise ValueError("bounds must be 12 finite numbers (translation lo, hi, size lo, hi), got %r" % (host,))
+    return (C.c_float * 12)(*host)
+
+
+def steer_rec(x_t, model_out, mean_type, tables, steer, t=None, clip=None, strided=None, rows=None, mask=None, q=(), scale=None,
+              x_dup=None, energy_out=None, grad_out=None):
+    """The launch record of collision steering (dsc_steer_boxes_f32): ``model_out`` (B, N, C) -- (2 B, N, C) under ``scale`` -- is
+    corrected in place between the model call and the step.  It takes the operand groups of step_rec under the same keywords, so a loop
+    hands both records the same dictionaries: the time source ``t`` or ``strided`` (its step counter and times), ``tables`` (ca, cb
+    first; the rest, ``clip``, ``q`` and ``x_dup`` belong to the step and are not read here), the given part ``rows`` = (partial, _,
+    counts) or ``mask`` = (known, _, mask), guidance ``scale``.  ``steer`` = (weight (B,) f32, t_below (1,) int64 -- both on the device,
+    read at launch --, bounds (steer_bounds), bbox_dim, class_dim).  ``x_t`` may be None for mean type x0.  ``energy_out`` (B,) /
+    ``grad_out`` (B, N, 3): the optional outputs."""
+    weight, t_below, bounds, bbox_dim, class_dim = steer
+    if rows is not None and mask is not None:
+        raise ValueError("diffuscene_amd: steer_boxes takes one given part, rows or mask")
+    if (t is None) == (strided is None):
+        raise ValueError("diffuscene_amd: steer_boxes takes one time source, t or strided")
+    _c(model_out, "model_out"); _c(weight, "weight"); _dev(t_below, "t_below", torch.int64)
+    if model_out.dim() != 3:
+        raise RuntimeError("diffuscene_amd: model_out must be (B, N, C), got %s" % (tuple(model_out.shape),))
+    mult = 1 if scale is None else 2
+    b, n, c = model_out.shape[0] // mult, model_out.shape[1], model_out.shape[2]
+    shape = (b, n, c)
+    if x_t is not None:
+        _c(x_t, "x_t")
+    elif mean_type != MEAN_X0:
+        raise RuntimeError("diffuscene_amd: steer_boxes needs x_t unless the model predicts x0")
+    if model_out.shape[0] != mult * b or b < 1 or (x_t is not None and tuple(x_t.shape) != shape):
+        raise RuntimeError("diffuscene_amd: steer_boxes: x_t %s and model_out %s do not go together"
+                           % (None if x_t is None else tuple(x_t.shape), tuple(model_out.shape)))
+    if tuple(weight.shape) != (b,) or t_below.numel() != 1:
+        raise RuntimeError("diffuscene_amd: weight must be (%d,) f32 and t_below hold one int64" % b)
+    if n > STEER_MAX_OBJECTS:
+        raise ValueError("diffuscene_amd: collision steering handles at most %d objects per scene, got %d" % (STEER_MAX_OBJECTS, n))
+    if bbox_dim != 8 or class_dim < 1 or bbox_dim + class_dim > c:
+        raise ValueError("diffuscene_amd: collision steering needs the layout [translation 3 | size 3 | cos, sin | classes ...], got "
+                         "bbox_dim=%d, class_dim=%d, %d channels" % (bbox_dim, class_dim, c))
+    bounds = steer_bounds(bounds)
+    ca, cb = tables[0], tables[1]
+    # the timestep is held to the rows of the schedule tables; a model that predicts x0 indexes none here, and without any table of the
+    # step at hand only a negative timestep is out of range
+    T = _table_rows(*tables) if any(tb is not None for tb in tables) else 2 ** 31 - 1
+    tp = sp = tmp = None
+    S = 0
+    if strided is not None:
+        (sp, tmp, _, _, _, _), S = _strided_run(*strided)
+    else:
+        _scene_t(t, b)
+        tp = t.data_ptr()
+    partial = counts = known = mk = None
+    pmax = 0
+    if rows is not None:
+        partial, counts = _c(rows[0], "partial"), _dev(rows[2], "counts", torch.int64)
+        pmax = partial.shape[1]
+        if tuple(partial.shape) != (b, pmax, c) or not 1 <= pmax <= n or tuple(counts.shape) != (b,) or not counts.is_contiguous():
+            raise RuntimeError("diffuscene_amd: partial must be (%d, Pmax <= %d, %d) with (%d,) counts, got %s / %s"
+                               % (b, n, c, b, tuple(partial.shape), tuple(counts.shape)))
+    if mask is not None:
+        known, mk = _c(mask[0], "known"), _dev(mask[2], "mask", torch.uint8)
+        if tuple(known.shape) != shape or tuple(mk.shape) != shape or not mk.is_contiguous():
+            raise RuntimeError("diffuscene_amd: known / mask must be %s, got %s / %s" % (shape, tuple(known.shape), tuple(mk.shape)))
+    if scale is not None and (tuple(_c(scale, "scale").shape) != (b,)):
+        raise RuntimeError("diffuscene_amd: scale must be a (%d,) f32 tensor (ops.guidance_scales), got %s" % (b, tuple(scale.shape)))
+    for o, want, name in ((energy_out, (b,), "energy_out"), (grad_out, (b, n, 3), "grad_out")):
+        if o is not None and tuple(_c(o, name).shape) != want:
+            raise RuntimeError("diffuscene_amd: %s must be %s, got %s" % (name, want, tuple(o.shape)))
+    args = (_opt(x_t), model_out.data_ptr(), tp, sp, tmp, _opt(ca), _opt(cb), _opt(partial), _opt(counts), _opt(known), _opt(mk),
+            _opt(scale), weight.data_ptr(), t_below.data_ptr(), bounds, _opt(energy_out), _opt(grad_out), mean_type, b, n, pmax, c,
+            bbox_dim, class_dim, S, T)
+    return "dsc_steer_boxes_f32", args, (x_t, model_out, tables, steer, bounds, t, strided, rows, mask, scale, energy_out, grad_out)
+
+
+def steer_boxes(x_t, model_out, weight, t_below, bounds, mean_type, ca=None, cb=None, bbox_dim=8, class_dim=1, energy_out=None,
+                grad_out=None, **operands):
+    """Collision steering of ``model_out`` in place, eagerly; ``operands``: the time source and the optional groups of steer_rec.
+    Returns ``model_out``."""
+    issue(steer_rec(x_t, model_out, mean_type, (ca, cb), (weight, t_below, bounds, bbox_dim, class_dim), energy_out=energy_out,
+                    grad_out=grad_out, **operands))
+    return model_out
+
+
+def box_repulsion(x0, bounds, bbox_dim=8, class_dim=1):
+    """The overlap energy of collision steering and its gradient, standalone: ``x0`` (B, N, C) scenes in the network's encoding (clamped
+    to [-1, 1] first, as the steering does) -> (energy (B,), grad (B, N, 3) = d energy / d x0[:, :, 0:3]).  The same entry point with
+    mean type x0, weight 0 and both optional outputs: nothing is written to ``x0``.  See the C header."""
+    _c(x0, "x0")
+    b, n = x0.shape[0], x0.shape[1]
+    dev = x0.device
+    energy = torch.empty((b,), device=dev, dtype=torch.float32)
+    grad = torch.empty((b, n, 3), device=dev, dtype=torch.float32)
+    steer_boxes(None, x0, torch.zeros((b,), device=dev), torch.zeros((1,), device=dev, dtype=torch.int64), bounds, MEAN_X0,
+                bbox_dim=bbox_dim, class_dim=class_dim, energy_out=energy, grad_out=grad, t=torch.zeros((b,), device=dev, dtype=torch.int64))
+    return energy, grad
+
+
 def scene_gate(x, keep, out=None):
     """y[b] = keep[b] ? x[b] : 0 for a (B, ...) f32 tensor and a (B,) bool / uint8 device tensor; a dropped scene is not read.  See the C
     header."""

@@ -24,7 +24,10 @@ A loop is three orthogonal parts, the axes of the one step kernel (csrc/diffusio
                   to the step, the unfused overwrite and restore.
   guidance        _Guidance: a plan at 2 B (text features | zeros), x kept in both halves of one (2 B, N, C) buffer (x_dup), the
                   per-scene scales in a buffer, ``m`` when unfused.
-_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, main draw, given draw unless final, [cfg_combine,] ONE update launch
+  steering        _Steer (optional, ``steer=``): the per-scene weights and the step bound K in buffers of the graph, ONE launch
+                  (dsc_steer_boxes_f32) after the model call that corrects its output in place; the step kernel is the unchanged one, and
+                  without it the graph is what it is today.
+_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] main draw, given draw unless final, [cfg_combine,] ONE update launch
 laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
 The ten classes are rows:                    schedule   given            guided   fused=False unfuses
   _StepGraph                                 T steps    - / _Dense       -        (sub-batch chains: _chains_for, this row only)
@@ -385,6 +388,10 @@ class _Given:
     def restore(self, g, out):
         return out
 
+    def steer_operands(self, g):
+        """What the part adds to ops.steer_rec: a given element enters the boxes with its given value and is never moved."""
+        return {}
+
 
 class _Dense(_Given):
     """p_sample_loop_complete (:461-466): the first P rows of every scene, re-noised and written over x_t BEFORE the model call at every
@@ -393,10 +400,14 @@ class _Dense(_Given):
 
     def __init__(self, g, shape):
         self.partial = torch.zeros(shape, device=g.device)
+        self.full = torch.full((shape[0],), shape[1], device=g.device, dtype=torch.int64)      # every scene is given all P rows
         self.noise = g._stream(shape, g.given_draws, GIVEN)
 
     def load(self, g, partial):
         self.partial.copy_(partial)
+
+    def steer_operands(self, g):
+        return dict(rows=(self.partial, None, self.full))
 
     def before(self, g):
         ops.complete_overwrite(g.x, self.partial, self.noise(), g.t, *g.q)
@@ -434,6 +445,9 @@ class _Ragged(_Given):
     def restore(self, g, out):
         return out if self.fused else restore_given_rows(out, self.partial, self.counts)
 
+    def steer_operands(self, g):
+        return dict(rows=(self.partial, None, self.counts))
+
 
 class _Masked(_Given):
     """Given elements as a byte mask: ``known`` (B, N, C) f32 and ``mask`` (B, N, C) uint8 (ops.known_mask), with full-shape known-draws;
@@ -454,6 +468,9 @@ class _Masked(_Given):
 
     def operands(self, g, final):                  # the known-draw is not read after the last step
         return dict(mask=(self.known, self.known if final else self.noise(), self.mask), q=g.q)
+
+    def steer_operands(self, g):
+        return dict(mask=(self.known, None, self.mask))
 
 
 class _Guidance:
@@ -479,13 +496,36 @@ class _Guidance:
             g.x_null.copy_(g.x)
 
 
+class _Steer:
+    """Collision steering (dsc_steer_boxes_f32): one launch between the model call and the step that corrects the model output in place,
+    on what the model call returned -- under guidance the 2 B output, with the scales, so the fused and the unfused guidance see the same
+    corrected halves.  ``weight`` (B,) f32 and ``t_below`` (1,) int64 are buffers of the graph, captured by pointer and refreshed in
+    place: one graph serves every per-scene weight and every number of steered steps, and a weight of 0 or a timestep at or above
+    t_below stores nothing.  ``layout`` = (bounds, bbox_dim, class_dim) is baked into the launch and part of the cache key."""
+
+    def __init__(self, g, layout):
+        bounds, bbox_dim, class_dim = layout
+        self.weight = torch.zeros((g.shape[0],), device=g.device, dtype=torch.float32)
+        self.t_below = torch.zeros((1,), device=g.device, dtype=torch.int64)
+        self.spec = (self.weight, self.t_below, ops.steer_bounds(bounds), bbox_dim, class_dim)
+
+    def load(self, weight, t_below):
+        self.weight.copy_(weight)               # in place: the graph holds these pointers
+        self.t_below.fill_(int(t_below))
+
+    def apply(self, g, mo):
+        scale = dict(scale=g.guide.scale) if g.guide else {}
+        ops.issue(ops.steer_rec(g.x, mo, g.mean_type, steer=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
+
+
 class _Loop:
     """One captured loop = a schedule (_PosteriorLoop or _DDIMLoop, by inheritance), a given part and guidance: the row a class below
     declares.  ``sched``: clip_denoised of a T-step loop, S of a strided one.  ``fused`` unfuses what the row has a kernel for: the
     overwrite of a ragged part, the guidance of a guided row.  ``partial_shape``: the shape of the given rows."""
     given, guided, chains, what = _Given, False, False, None
 
-    def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None):
+    def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None,
+                 steer=None):
         nch = (_chains_for(shape[0]),) if self.chains else ()
         super().__init__(diff, model, shape, device, condition, condition_cross, sched, replay, 2 if self.guided else 1, *nch)
         self.fused = fused
@@ -494,6 +534,7 @@ class _Loop:
         part = self.given if self.given is not _Dense or partial_shape is not None else _Given
         self.part = part(self, partial_shape, fused) if part is _Ragged else part(self, partial_shape)
         self.guide = _Guidance(self, fused) if self.guided else None
+        self.steer = _Steer(self, steer) if steer is not None else None
         for owner in (self.part, self.guide):   # the buffers, by the names tests, tools and bench.py read
             for name in ("partial", "counts", "known", "mask", "scale", "m"):
                 if hasattr(owner, name):
@@ -528,10 +569,12 @@ class _Loop:
         return self.model_out
 
     def _step(self, final):
-        """[the unfused overwrite,] model call, main draw, the given draw of the NEXT step unless final, [cfg_combine,] one update
-        launch, [the copy into the null half,] decrement or advance unless final."""
+        """[the unfused overwrite,] model call, [collision steering,] main draw, the given draw of the NEXT step unless final,
+        [cfg_combine,] one update launch, [the copy into the null half,] decrement or advance unless final."""
         self.part.before(self)
         mo = self._model_call()
+        if self.steer:
+            self.steer.apply(self, mo)
         noise = self._main_draw(final)
         given = self.part.operands(self, final)
         mo, guided = self.guide.apply(self, mo) if self.guide else (mo, {})
@@ -541,7 +584,7 @@ class _Loop:
         if not final:
             self._move()
 
-    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None):
+    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None):
         """``sched``: total_steps of a T-step loop, the device tables (GaussianDiffusion.ddim_tables) of a strided one.  ``values``: the
         (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword)."""
         t0, steps = self._begin(sched)
@@ -552,6 +595,8 @@ class _Loop:
             self.guide.scale.copy_(values[0])   # in place: the graph holds this pointer
             values = values[1:]
         self.part.load(self, *values)
+        if self.steer:
+            self.steer.load(*steer)             # (weight (B,), K): steered while t < K
         self._upload((self.noise, noise_buffer, 1), *([(self.part.noise, given_noise, 1 if self.part.fused else 0)] if self.part.noise else []))
         self.part.first(self)
         if self.part.fused and self.x_null is not None:         # guided: both halves of the state stay current
@@ -666,11 +711,14 @@ def _front_end(name, cls):
     clip_denoised, total_steps -- a strided row: sampling_timesteps, eta --, noise_fn=torch.randn, [the given values,] [fused=True]):
     ``scale`` the (B,) f32 device vector of ops.guidance_scales under conditions at 2 B (GaussianDiffusion._guided_inputs), ``counts`` the
     (B,) int64 device tensor of ops.ragged_counts, ``known`` / ``mask`` those of _masked_inputs.  The cache key holds the class,
-    clip_denoised or S, ``fused`` and the shape of the given rows -- never eta, counts, mask or scales, which live in buffers."""
+    clip_denoised or S, ``fused`` and the shape of the given rows -- never eta, counts, mask or scales, which live in buffers.
+    ``steer`` (keyword; None: the loop and its graph as they are without it) = (weight (B,) f32 on the device, K, bounds, bbox_dim,
+    class_dim) of GaussianDiffusion._steer_inputs: collision steering (_Steer) after every model call; the key gains the layout -- the
+    bounds and the two dims --, never the weights or K."""
     names = (("scale",) if cls.guided else ()) + (("sampling_timesteps", "eta") if cls.strided else ("clip_denoised", "total_steps")) \
         + ("noise_fn",) + cls.given.values + (("fused",) if cls.guided or cls.given is _Ragged else ())
 
-    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, **kw):
+    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, **kw):
         if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
             raise TypeError("%s(diff, denoise_fn, shape, device, condition, condition_cross, %s)" % (name, ", ".join(names)))
         a = dict(dict.fromkeys(names), noise_fn=torch.randn, fused=True)
@@ -682,13 +730,18 @@ def _front_end(name, cls):
             sched = n_main = n_given = int(a["sampling_timesteps"])
         else:
             sched, n_main, n_given = bool(a["clip_denoised"]), a["total_steps"] + 1, a["total_steps"]
+        # steer = (weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim): the first two live in buffers, the rest is the key
+        layout = None if steer is None else (tuple(float(v) for v in steer[2]), int(steer[3]), int(steer[4]))
         check = cls.what and _replay_check(cls.what % sched if "%" in cls.what else cls.what, n_main,
                                            shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
         out = _cached_loop(
-            name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"], (cls.__name__, sched, bool(a["fused"]), gshape),
-            lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape),
+            name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"],
+            (cls.__name__, sched, bool(a["fused"]), gshape) + (() if steer is None else (layout,)),
+            lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape,
+                                           layout),
             lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else n_given, *([a["scale"]] if cls.guided else []), *given,
-                                                  noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given)),
+                                                  noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given),
+                                                  steer=None if steer is None else steer[:2]),
             mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
         if cls.given is _Dense and given:
             out[:, :gshape[1], :] = given[0]            # clean objects restored after the last step (:471-473)

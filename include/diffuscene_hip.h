@@ -462,6 +462,33 @@ int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model_out, const
                                  int32_t mean_type, int32_t b, int64_t inner, int32_t num_steps, int32_t num_timesteps,
                                  dsc_stream_t stream);
 
+/* Collision steering: one launch between the model call and the unchanged step kernel, correcting model_out IN PLACE so that the step's
+ * x0 estimate moves down the gradient of the pairwise box-overlap energy (INTEGRATION.md 9 states the definition).  Scene i of b:
+ *   x0     = clamp(predict_x0(x_t, m), -1, 1) per element (always clamped); a given element takes its given value.  m = model_out, or
+ *            u + cfg_scale[i] * (c - u) from the two halves of a (2 b, n, c) model_out when cfg_scale is set.
+ *   boxes  : centre = descale(x0[0:3]), half sizes = descale(x0[3:6]) with bounds[12] = c_lo[3] c_hi[3] s_lo[3] s_hi[3] (HOST, as in
+ *            dsc_ddpm_loss_f32), rotated about y by the (cos, sin) channels 6, 7 over their hypot (both zero: angle 0) and bounded
+ *            axis-aligned: hx = |c| sx + |s| sz, hy = sy, hz = |s| sx + |c| sz.  Box j is valid iff x0[j, bbox_dim + class_dim - 1] < 0.
+ *   energy : E = sum over valid pairs j < k of the axis-aligned 3-D IoU with union floor 1e-6; boxes that only touch do not interact.
+ *   g      = dE / d x0[:, 0:3] (through the centres only; it includes span / 2).
+ *   store  : only when t < t_below[0] and weight[i] != 0, and only to free translation elements of valid boxes with weight * g != 0:
+ *            d = weight[i] * g + (raw - clamp(raw));  mean type x0: m -= d;  eps / v: m += d / cb[t] (cb[t] == 0: no store), so the step
+ *            sees x0 = clamp(x0) - weight[i] * g.  With cfg_scale the same delta is added to both halves.
+ * Operand groups that may be NULL: the time source is t (b,) or step (1,) / times (num_steps,) (exactly one); ca / cb / x_t for mean
+ * type x0; the given part is none, (partial (b, pmax, c), counts (b,)) -- rows [0, counts[i]) -- or (known, mask) of x_t's shape;
+ * cfg_scale; energy_out (b,) and grad_out (b, n, 3), written whether or not the step is active.  weight (b,) f32 and t_below (1,) int64
+ * are DEVICE buffers read through their pointers: one captured graph serves every weight and every number of steered steps.
+ * One 256-thread block per scene, n <= 160 (else DSC_ERANGE); x0 is the float32 value the step forms, the geometry after it is
+ * float64 (energy_out / grad_out are the float32 numbers nearest to it); the energy is summed in a fixed order, no atomics, and scene
+ * i's result does not depend on b.  bbox_dim != 8: DSC_ERANGE; bbox_dim + class_dim > c, class_dim < 1, two time sources or two given parts:
+ * DSC_EINVAL.  t[i], counts[i], step[0] and times[k] are clamped and counted (dsc_device_error_count). */
+int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                        const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                        const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
+                        const float* bounds, float* energy_out, float* grad_out, int32_t mean_type, int32_t b, int32_t n,
+                        int32_t pmax, int32_t c, int32_t bbox_dim, int32_t class_dim, int32_t num_steps, int32_t num_timesteps,
+                        dsc_stream_t stream);
+
 /* Per-scene gate of the text-condition dropout (text_drop_prob): y[i, :] = keep[i] ? x[i, :] : 0 for b scenes of `inner` elements;
  * keep holds one byte per scene.  A select: the elements of a dropped scene are not read (NaN there does not propagate).  Used forward
  * on the text features and backward on their incoming gradient.  y may alias x. */
