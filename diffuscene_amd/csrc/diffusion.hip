@@ -311,6 +311,75 @@ __global__ __launch_bounds__(256) void steer_boxes_kernel(const SteerArgs p) {
 // Which elements of a scene are given (completion, in-painting) instead of sampled: none, the first counts[b] rows, or a byte mask.
 enum { GIVEN_NONE = 0, GIVEN_ROWS = 1, GIVEN_MASK = 2 };
 
+// Multistep DPM-Solver++(2M): one launch between the model call (after collision steering, if any) and the unchanged
+// strided step.  The solver is a data-prediction one: its first-order form is DDIM at eta = 0, its second-order form the same step on
+// an extrapolated x0 estimate.  With the pairs (t_k, t'_k) of ddim_schedule(S, 0), lambda(t) = 1/2 ln(abar_t / (1 - abar_t)) and
+// h_k = lambda(t'_k) - lambda(t_k), the history weights are e_0 = 0, e_k = h_k / (2 h_{k-1}) for 1 <= k <= S - 2 and e_{S-1} = 0 (the
+// last pair takes x0: "lower order final"); the host computes them in float64 and hands over an (S,) float32 table.  At pair
+// k = step[0], for every free element:
+//   m     = mo, or cfg_mix(c, u, scale[b]) from the two halves of a 2 b output, in float32 exactly as the step forms it;
+//   x0raw = predict_x0(x_t, m) in float32, the step's own expressions and rounding;  x0c = clamp(x0raw, -1, 1);
+//   from here float64 with one final rounding:  D = x0c + e_k (x0c - hist);  d = x0raw - D;
+//   mean type x0: m' = m - d;  eps / v: m' = m + d / Bc (Bc == 0: no change);  guided: the same delta goes to both halves;
+//   hist  = x0c -- the float32 x0 of this pair, steered but not extrapolated.
+// The step then runs on m': where D lies inside [-1, 1] its x0 is D, the DPM-Solver++(2M) update; outside, the step's clamp applies as
+// it does to DDIM here.  What the kernel keeps:
+// * e[k] == 0: hist is not read and mo is not written -- a stale or NaN history can never leak in, and S <= 2 is DDIM at eta = 0 bit
+//   for bit.  hist is written on every pair except the last (k == S - 1), where the launch returns before it reads anything else.
+// * A given element (ragged row prefix or mask) is neither read nor written: x_t, mo and hist alike.
+// * Every scene is at the same pair; step[0] and times[k] are clamped and counted once per launch, counts[b] once per scene.
+// * HBM traffic per free element: at most three reads (x_t, mo, hist; two of mo if guided) and two writes (mo, hist).  Every product,
+//   sum and difference is a statement of its own (-ffp-contract=off).
+template <int GIVEN, bool GUIDED>
+__global__ __launch_bounds__(256) void multistep_x0_kernel(const float* __restrict__ xt, float* __restrict__ mo, float* __restrict__ hist,
+                                                          const float* __restrict__ weights, const int64_t* __restrict__ step,
+                                                          const int64_t* __restrict__ times, const float* __restrict__ ca,
+                                                          const float* __restrict__ cb, const float* __restrict__ scale,
+                                                          const int64_t* __restrict__ counts, const uint8_t* __restrict__ mask,
+                                                          int mean_type, int64_t inner, int pmax, int c, int S, int T) {
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const bool is_x0 = mean_type == DSC_MEAN_X0;
+    const int64_t k = dsc_checked_index(step[0], S, first && b == 0);
+    const int64_t tv = dsc_checked_index(times[k], T, first && b == 0);
+    int64_t cnt = 0;
+    if constexpr (GIVEN == GIVEN_ROWS) cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    if (k == S - 1) return;                                                                  // the last pair: nothing is read or stored
+    const float e = weights[k];
+    const float A = is_x0 ? 0.f : ca[tv], Bc = is_x0 ? 0.f : cb[tv];
+    const bool move = e != 0.f && (is_x0 || Bc != 0.f);
+    float w = 0.f;
+    if constexpr (GUIDED) w = scale[b];
+    const int64_t base = (int64_t)b * inner, half = (int64_t)gridDim.y * inner;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        if constexpr (GIVEN == GIVEN_ROWS) {
+            if (i < cnt) continue;
+        }
+        if constexpr (GIVEN == GIVEN_MASK) {
+            if (mask[base + i] != 0) continue;
+        }
+        const float c0 = mo[base + i];
+        float u0 = 0.f, m = c0;
+        if constexpr (GUIDED) {
+            u0 = mo[half + base + i];
+            m = cfg_mix(c0, u0, w);
+        }
+        const float raw = predict_x0(is_x0 ? 0.f : xt[base + i], m, A, Bc, mean_type, false);
+        const float x0c = fminf(fmaxf(raw, -1.0f), 1.0f);
+        if (move) {
+            const double x0d = (double)x0c;
+            const double diff = x0d - (double)hist[base + i];
+            const double ext = (double)e * diff;
+            const double D = x0d + ext;
+            const double d = (double)raw - D;
+            const double delta = is_x0 ? -d : d / (double)Bc;
+            mo[base + i] = (float)((double)c0 + delta);
+            if constexpr (GUIDED) mo[half + base + i] = (float)((double)u0 + delta);
+        }
+        hist[base + i] = x0c;
+    }
+}
+
 // The reverse step, one launch after the model call: every dsc_*p_sample*_f32 and dsc_ddim_*step_f32 is one instantiation.
 //
 //   STRIDED  false: the posterior step of p_sample (diffusion_ddpm.py:305-352) at the scene's own row tv = t[b]:
@@ -877,6 +946,33 @@ extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int
     }
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(steer_boxes_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_multistep_x0_f32(const float* x_t, float* model_out, float* hist, const float* weights, const int64_t* step,
+                                    const int64_t* times, const float* ca, const float* cb, const float* cfg_scale,
+                                    const int64_t* counts, const uint8_t* mask, int32_t mean_type, int32_t b, int64_t inner,
+                                    int32_t pmax, int32_t c, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream) {
+    if (!model_out || !hist || !weights || !step || !times || b < 1 || inner < 1 || num_steps < 1 || num_timesteps < 1) return DSC_EINVAL;
+    if (bad_mean_args(mean_type, ca, cb) || (mean_type != DSC_MEAN_X0 && !x_t)) return DSC_EINVAL;
+    if (counts && mask) return DSC_EINVAL;                                                   // one given part
+    if (counts && (c < 1 || pmax < 1 || inner % c != 0 || (int64_t)pmax * c > inner)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;                                                        // blockIdx.y carries the scene
+    const dim3 grid(grid_x(inner), b), block(256);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DSC_CLEAR_STALE_ERROR();
+#define DSC_MULTISTEP_LAUNCH(GIVEN, GUIDED)                                                                                       \
+    hipLaunchKernelGGL((multistep_x0_kernel<GIVEN, GUIDED>), grid, block, 0, s, x_t, model_out, hist, weights, step, times, ca, cb, \
+                       cfg_scale, counts, mask, mean_type, inner, pmax, c, num_steps, num_timesteps)
+    if (counts) {
+        if (cfg_scale) DSC_MULTISTEP_LAUNCH(GIVEN_ROWS, true); else DSC_MULTISTEP_LAUNCH(GIVEN_ROWS, false);
+    } else if (mask) {
+        if (cfg_scale) DSC_MULTISTEP_LAUNCH(GIVEN_MASK, true); else DSC_MULTISTEP_LAUNCH(GIVEN_MASK, false);
+    } else {
+        if (cfg_scale) DSC_MULTISTEP_LAUNCH(GIVEN_NONE, true); else DSC_MULTISTEP_LAUNCH(GIVEN_NONE, false);
+    }
+#undef DSC_MULTISTEP_LAUNCH
     DSC_LAUNCH_CHECK();
     return 0;
 }

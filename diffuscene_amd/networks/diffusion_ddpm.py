@@ -20,6 +20,8 @@ each a generator of states (x_T, then the state after every step), and two indep
                    written
   the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine); under ``collision_scale`` _steered wraps either:
                    the model call, collision steering of its output in place (dsc_steer_boxes_f32), then the guidance mix
+  the solver       ``sampling_solver="dpmpp_2m"`` (strided loops): _strided_states hands the model call a ``post`` hook that issues
+                   dsc_multistep_x0_f32 on the (steered) output, before the guidance mix, on every pair but the last; the step is unchanged
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
 part -- and then numbers its own draws: main stream x_T = 0, 1, 2, ..., given stream 0, 1, 2, ... (scene_noise.py).
 The public loops state their spec -- strided (S, eta) or not, the given part, the guidance scale -- and GaussianDiffusion._loop does the
@@ -167,26 +169,41 @@ def restore_given_rows(x, boxes, counts):
 
 
 def _model(denoise_fn, condition, condition_cross):
-    """The model call of a loop: (x, t_) -> model output."""
-    return lambda x, t_: denoise_fn(x, t_, condition, condition_cross)
+    """The model call of a loop: (x, t_) -> model output.  ``post`` (x, model output), where a loop passes one, corrects the output in
+    place before it is returned (the multistep solver of _strided_states)."""
+    def call(x, t_, post=None):
+        mo = denoise_fn(x, t_, condition, condition_cross)
+        if post is not None:
+            mo = mo.contiguous()
+            post(x, mo)
+        return mo
+    return call
 
 
 def _guided_model(denoise_fn, cond2, cross2, scale):
     """The guided model call: the denoiser at 2 B on the same x and t in both halves (conditions of _guided_inputs), then
-    m = u + scale[b] * (c - u) (dsc_cfg_combine_f32)."""
-    return lambda x, t_: ops.cfg_combine(denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), cond2, cross2).contiguous(), scale)
+    m = u + scale[b] * (c - u) (dsc_cfg_combine_f32).  ``post`` sees the 2 B output, before the mix."""
+    def call(x, t_, post=None):
+        mo = denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), cond2, cross2).contiguous()
+        if post is not None:
+            post(x, mo)
+        return ops.cfg_combine(mo, scale)
+    return call
 
 
 def _steered(model, diff, device, steer, part, scale=None):
     """The model call of a steered loop: ``model`` -- under guidance the denoiser at 2 B, ``scale`` its (B,) scales --, then collision
-    steering of its output in place (dsc_steer_boxes_f32), then the guidance mix: the launches of the captured loop, in its order."""
+    steering of its output in place (dsc_steer_boxes_f32), [``post`` on the steered output,] then the guidance mix: the launches of the
+    captured loop, in its order."""
     weight, k, bounds, bbox_dim, class_dim = steer
     ca, cb = diff._coeffs(diff.tables(device))
     spec = (weight, torch.full((1,), k, device=device, dtype=torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim)
 
-    def call(x, t_):
+    def call(x, t_, post=None):
         mo = model(x, t_).contiguous()
         ops.issue(ops.steer_rec(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale, **part.steer_operands()))
+        if post is not None:
+            post(x, mo)
         return mo if scale is None else ops.cfg_combine(mo, scale)
     return call
 
@@ -194,6 +211,24 @@ def _steered(model, diff, device, steer, part, scale=None):
 def _steer_kw(collision_scale, collision_steps):
     """The steering keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
     return {} if collision_scale is None and collision_steps is None else dict(steer=(collision_scale, collision_steps))
+
+
+def _solver_kw(sampling_solver):
+    """The solver keyword a public strided loop hands to _loop: none at all without it, so that call stays what it was."""
+    return {} if sampling_solver is None else dict(multistep=sampling_solver)
+
+
+def _check_solver(solver, strided, what):
+    """The refusals of ``sampling_solver``, before anything is drawn or computed: an unknown name, a loop that is not strided, eta != 0
+    (the solver is the deterministic ODE form)."""
+    if not isinstance(solver, str) or solver not in ops.SOLVERS:
+        raise ValueError("%s: sampling_solver must be None or one of %s, got %r" % (what, ops.SOLVERS, solver))
+    if strided is None or strided[0] is None:
+        raise ValueError("%s: sampling_solver=%r goes with sampling_timesteps: the solver rides on the strided loops" % (what, solver))
+    if float(strided[1]) != 0.0:
+        raise ValueError("%s: sampling_solver=%r needs ddim_sampling_eta = 0 (the deterministic ODE form), got %r"
+                         % (what, solver, strided[1]))
+    return solver
 
 
 def _arm(noise_fn, given):
@@ -470,12 +505,23 @@ class GaussianDiffusion:
             x = self._posterior_step(x, model(x, t_), t_, noise_fn, clip_denoised, draw=draw)
             yield given.finish(x) if t == 0 else x      # not a copy: ``given.before`` of the next step writes into it (keep a clone)
 
-    def _strided_states(self, model, shape, device, noise_fn, S, eta, given=_FREE):
+    def _strided_states(self, model, shape, device, noise_fn, S, eta, given=_FREE, multistep=None):
         """The strided (DDIM) loop, reference :402-444: a device step counter, [overwrite the given part], model call, a draw except on
-        the last pair ((t, -1) takes x_start), ddim_step, ddim_advance."""
+        the last pair ((t, -1) takes x_start), ddim_step, ddim_advance.  ``multistep`` = (the (B,) guidance scales or None,): the
+        DPM-Solver++(2M) launch (dsc_multistep_x0_f32) on the (steered) model output of every pair but the last, before ddim_step; the
+        x0 history and the weight table live here."""
         dtab = self.ddim_tables(S, eta, device)
         pairs = dtab[0]
         step = torch.zeros((1,), dtype=torch.int64, device=device)
+        solve = None
+        if multistep is not None:
+            hist = torch.empty(tuple(shape), dtype=torch.float32, device=device)
+            weights = self.multistep_table(S, device)
+            coeffs = self._coeffs(self.tables(device))
+
+            def solve(x, mo):
+                ops.issue(ops.multistep_rec(x.contiguous(), mo, hist, weights, _MEAN[self.model_mean_type], coeffs,
+                                            strided=(step,) + tuple(dtab[1:]), scale=multistep[0], **given.steer_operands()))
         t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(pairs[0][0])
         _arm(noise_fn, given)
         x = noise_fn(size=shape, dtype=torch.float, device=device)
@@ -484,8 +530,8 @@ class GaussianDiffusion:
         yield x
         for time, time_next in pairs:
             given.before(x, t_)
-            model_output = model(x, t_)
             last = time_next < 0
+            model_output = model(x, t_) if solve is None or last else model(x, t_, solve)
             noise = x if last else noise_fn(size=shape, dtype=torch.float, device=device)      # not read on the last pair
             x = self.ddim_step(x.contiguous(), model_output.contiguous(), noise.contiguous(), step, dtab)
             if not last:
@@ -501,17 +547,20 @@ class GaussianDiffusion:
                           **_steer_kw(collision_scale, collision_steps))
 
     def _loop(self, what, denoise_fn, shape, device, condition, condition_cross, noise_fn, graph, strided=None, given=None, scale=None,
-              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None):
+              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None, multistep=None):
         """What every public loop does behind its signature.  The spec: ``strided`` = (sampling_timesteps, ddim_sampling_eta) or None for
         T steps; ``given`` = None, ("dense", partial_boxes), ("ragged", partial_boxes, num_partial) or ("mask", known, mask); ``scale`` =
         the guidance scale or None.  Validates (ValueError names ``what``), keeps (eta, S) on the instance as the reference does (:404-405),
         hands over to the captured loop under _use_graph -- the front end front_end_name(spec) of sampler.py, looked up when called -- and
         otherwise runs the eager core on the given part and the model call of the spec.  ``say_last``: the reference's print, after the
         eager loop / before the captured one; ``all_states``: the list of states (eager).  ``steer`` = (collision_scale, collision_steps)
-        or None: collision steering after every model call (_steer_inputs), on either path."""
+        or None: collision steering after every model call (_steer_inputs), on either path.  ``multistep`` = the name of a multistep
+        solver (ops.SOLVERS) or None: the strided loop takes its steps on the solver's extrapolated x0 (_check_solver)."""
         assert isinstance(shape, (tuple, list))
         if strided is not None:
             S, eta = _check_ddim(self.num_timesteps, *strided)
+        if multistep is not None:
+            _check_solver(multistep, strided, what)
         kind, values = (None, ()) if given is None else (given[0], given[1:])
         if kind == "dense":
             values = (values[0].contiguous(),)
@@ -534,7 +583,8 @@ class GaussianDiffusion:
                 self._say_last()
             front = getattr(sampler, front_end_name(strided is not None, kind, scale is not None))
             return front(self, denoise_fn, tuple(shape), device, condition, condition_cross, *(() if scale is None else (scale,)), *sched,
-                         noise_fn, *values, **({} if steer is None else dict(steer=steer)))
+                         noise_fn, *values, **({} if steer is None else dict(steer=steer)),
+                         **({} if multistep is None else dict(multistep=self.multistep_table(S, device))))
         part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
             self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
         if steer is None:
@@ -545,7 +595,8 @@ class GaussianDiffusion:
             model = _steered(lambda x, t_: denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), condition, condition_cross),
                              self, device, steer, part, scale)
         if strided is not None:
-            states = self._strided_states(model, shape, device, noise_fn, S, eta, part)
+            states = self._strided_states(model, shape, device, noise_fn, S, eta, part,
+                                          *(() if multistep is None else ((scale,),)))
         elif scale is not None and kind is None:        # p_sample_loop_guided: the device check before the first draw, its own draw keywords
             self.tables(device)
             states = self._t_states(model, shape, device, noise_fn, *sched, part, draw=dict(size=shape, dtype=torch.float, device=device))
@@ -614,6 +665,18 @@ class GaussianDiffusion:
             self._ddim_dev[key] = hit
         return hit
 
+    def multistep_table(self, sampling_timesteps, device):
+        """The (S,) float32 history weights of DPM-Solver++(2M) on the pairs of ddim_schedule(S, 0) (ops.multistep_weights, from the
+        float64 alphas_cumprod), on ``device``; once per (S, device)."""
+        device = torch.device(device)
+        key = ("multistep", int(sampling_timesteps), device)
+        hit = self._ddim_dev.get(key)
+        if hit is None:
+            pairs, _ = self.ddim_schedule(sampling_timesteps, 0.0)
+            hit = ops.multistep_weights(pairs, np.cumprod(1. - self.np_betas, axis=0)).to(device)
+            self._ddim_dev[key] = hit
+        return hit
+
     def ddim_step(self, x_t, model_output, noise, step, dtab, out=None, x0_out=None):
         """One DDIM update at the step held by the device counter ``step`` (dtab = ddim_tables(...)): the fused HIP kernel."""
         _, times, times_next, coef = dtab
@@ -625,15 +688,18 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
                          sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None,
-                         collision_scale=None, collision_steps=None):
+                         collision_scale=None, collision_steps=None, sampling_solver=None):
         """DDIM sampling, reference :402-444 (its two call-site slips bridged: model_predictions gets ``denoise_fn``, and there is no
         self-conditioning).  Draw order: x_T, then one draw per pair except the last ((t, -1) takes x_start): S draws in all.
         x_start is always clamped to [-1, 1], as in the reference, whatever ``clip_denoised`` says.  The network runs on the static
         plan, each update is one HIP kernel (dsc_ddim_step_f32); by default (``graph=None``, the rules of p_sample_loop) the loop is a
-        replayed hipGraph step.  ``return_all_timesteps=True`` returns the S + 1 states (eager loop)."""
+        replayed hipGraph step.  ``return_all_timesteps=True`` returns the S + 1 states (eager loop).
+        ``sampling_solver`` (None: this loop as it was; "dpmpp_2m", on every strided loop): the multistep DPM-Solver++(2M) -- one more
+        launch per pair (dsc_multistep_x0_f32) moves the model output so that the unchanged step runs on the extrapolated x0 estimate
+        D = x0 + e_k (x0 - x0_prev); same draws, needs ddim_sampling_eta == 0, S <= 2 is DDIM bit for bit."""
         return self._loop("ddim_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), all_states=return_all_timesteps,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
@@ -710,7 +776,7 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                          sampling_timesteps=50, ddim_sampling_eta=0., graph=None,
-                         collision_scale=None, collision_steps=None):
+                         collision_scale=None, collision_steps=None, sampling_solver=None):
         """Classifier-free guidance in S strided (DDIM) steps: scene b is the reference's ddim_sample_loop (:402-444) with the guided
         output m of p_sample_loop_guided in place of the model output inside model_predictions.  x_start is always clamped to [-1, 1].
         Draws: exactly those of ddim_sample_loop at batch B (x_T, then one per pair except the last).  The eager loop is built from the
@@ -718,7 +784,7 @@ class GaussianDiffusion:
         dsc_ddim_cfg_step_f32, bit-identical."""
         return self._loop("ddim_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), scale=guidance_scale,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
 
     # ------------------------------------------------------------------ completion, in-painting, re-arrangement
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
@@ -748,7 +814,7 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                   sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None,
-                                  collision_scale=None, collision_steps=None):
+                                  collision_scale=None, collision_steps=None, sampling_solver=None):
         """Strided (DDIM) scene completion of a batch with per-scene numbers of given objects.  Scene b is ddim_sample_loop (reference
         :402-444) run on that scene alone with ONE addition taken from p_sample_loop_complete (:447-476): before every model call at pair
         (t, t_next) the first num_partial[b] rows of the state are overwritten in place with q_sample(partial_boxes[b], t, fresh noise);
@@ -764,7 +830,7 @@ class GaussianDiffusion:
         dsc_ddim_inpaint_step_f32, bit-identical."""
         return self._loop("ddim_complete_ragged_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial),
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
 
     def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
         """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
@@ -804,7 +870,7 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
                          ddim_sampling_eta=0., known=None, mask=None, graph=None,
-                         collision_scale=None, collision_steps=None):
+                         collision_scale=None, collision_steps=None, sampling_solver=None):
         """Element-wise in-painting in S strided (DDIM) steps; ``known`` / ``mask`` as in p_sample_loop_masked.  Scene b is ddim_sample_loop
         (reference :402-444) on that scene alone: before every model call at pair (t, t_next),
         x = where(mask, q_sample(known, t, fresh noise), x); after the last pair, x = where(mask, known, x).  x_start is always clamped
@@ -814,7 +880,7 @@ class GaussianDiffusion:
         graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
         return self._loop("ddim_masked_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask),
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
 
     @torch.no_grad()
     def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
@@ -833,28 +899,31 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                                 sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None,
-                                collision_scale=None, collision_steps=None):
+                                collision_scale=None, collision_steps=None, sampling_solver=None):
         """Text-guided element-wise in-painting in S strided (DDIM) steps: scene b is ddim_masked_loop with the guided output m of
         p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
         ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
         step whose update is the fused dsc_ddim_masked_cfg_step_f32, bit-identical."""
         return self._loop("ddim_masked_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
-                          ddim_sampling_eta=0., input_boxes=None, graph=None):
+                          ddim_sampling_eta=0., input_boxes=None, graph=None, sampling_solver=None):
         """Strided (DDIM) re-arrangement: ddim_sample_loop on the sub-shape (B, N, translation_dim + angle_dim) under the arrange
         condition, then the re-assembly of p_sample_loop_arrange (reference :496-503).  Draws: those of ddim_sample_loop on the
-        sub-shape (S in all)."""
+        sub-shape (S in all).  ``sampling_solver``: as in ddim_sample_loop."""
         assert isinstance(shape, (tuple, list))
         _check_ddim(self.num_timesteps, sampling_timesteps, ddim_sampling_eta)
+        if sampling_solver is not None:
+            _check_solver(sampling_solver, (sampling_timesteps, ddim_sampling_eta), "ddim_arrange_loop")
         if input_boxes is None or tuple(input_boxes.shape) != tuple(shape):
             raise ValueError("ddim_arrange_loop needs input_boxes of shape %s" % (tuple(shape),))
         sub = (shape[0], shape[1], self.translation_dim + self.angle_dim)
         img = self.ddim_sample_loop(denoise_fn, sub, device, condition, condition_cross, noise_fn=noise_fn,
-                                    sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph)
+                                    sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, graph=graph,
+                                    **({} if sampling_solver is None else dict(sampling_solver=sampling_solver)))
         img = self._arranged(img, input_boxes)
         assert img.shape == tuple(shape)
         return img
@@ -1130,12 +1199,12 @@ class DiffusionPoint(nn.Module):
                                                       known=known, mask=mask, graph=graph, **steer)
 
     def arrange_samples_ddim(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
-                             sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None):
-        """arrange_samples in S strided steps (ddim_arrange_loop)."""
+                             sampling_timesteps=50, ddim_sampling_eta=0., input_boxes=None, graph=None, **solver):
+        """arrange_samples in S strided steps (ddim_arrange_loop); ``solver``: sampling_solver=, where the caller passes one."""
         return self.diffusion.ddim_arrange_loop(self._denoise, shape=shape, device=device, condition=condition,
                                                 condition_cross=condition_cross, noise_fn=noise_fn,
                                                 sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                input_boxes=input_boxes, graph=graph)
+                                                input_boxes=input_boxes, graph=graph, **solver)
 
     def arrange_samples(self, shape, device, condition=None, condition_cross=None, noise_fn=torch.randn,
                         clip_denoised=True, keep_running=False, input_boxes=None, graph=None):

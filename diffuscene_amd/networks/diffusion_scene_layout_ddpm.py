@@ -289,7 +289,7 @@ class DiffusionSceneLayout_DDPM(Module):
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
                input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
                sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None,
-               collision_steps=None):
+               collision_steps=None, sampling_solver=None):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
@@ -306,10 +306,15 @@ class DiffusionSceneLayout_DDPM(Module):
         after every model call whose timestep is below ``collision_steps`` (None: every step; an integer K: the last K timesteps) the
         clamped x0 estimate of scene b moves by -w[b] * dE/d(translations), E the summed pairwise IoU of its non-empty boxes
         (GaussianDiffusion._steer_inputs).  Generation and completion, T-step and strided, guided or not, seeded or
-        not; re-arrangement and ``ret_traj`` refuse it.  Needs the train-stats file for the de-normalisation bounds."""
+        not; re-arrangement and ``ret_traj`` refuse it.  Needs the train-stats file for the de-normalisation bounds.
+        ``sampling_solver`` (None: this method as it was; "dpmpp_2m"): the multistep DPM-Solver++(2M) on the strided loop -- the S
+        steps are taken on the extrapolated x0 estimate D = x0 + e_k (x0 - x0_prev) (``_check_solver``), one model
+        call per step as before; combines with guidance, steering and seeds.  Needs ``sampling_timesteps`` and
+        ``ddim_sampling_eta == 0``."""
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, ret_traj)
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
                                       "re-arrangement run the full DDPM loop (call them with sampling_timesteps=None)")
@@ -346,14 +351,14 @@ class DiffusionSceneLayout_DDPM(Module):
             if sampling_timesteps is not None:
                 return self.diffusion.gen_samples_guided_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                               guidance_scale=scale, sampling_timesteps=sampling_timesteps,
-                                                              ddim_sampling_eta=ddim_sampling_eta, **seeded, **steer)
+                                                              ddim_sampling_eta=ddim_sampling_eta, **seeded, **steer, **solver)
             return self.diffusion.gen_samples_guided(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                      guidance_scale=scale, clip_denoised=clip_denoised, **seeded, **steer)
         if sampling_timesteps is not None:
             return self.diffusion.gen_samples_ddim(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                    clip_denoised=clip_denoised, sampling_timesteps=sampling_timesteps,
                                                    ddim_sampling_eta=ddim_sampling_eta, return_all_timesteps=bool(ret_traj), **seeded,
-                                                   **steer)
+                                                   **steer, **solver)
         if ret_traj:
             return self.diffusion.gen_sample_traj(noise.shape, device, freq=freq, condition=condition,
                                                   condition_cross=condition_cross, clip_denoised=clip_denoised, **seeded)
@@ -372,6 +377,16 @@ class DiffusionSceneLayout_DDPM(Module):
         self.diffusion.diffusion._steer_inputs(tuple(int(v) for v in shape), "cpu", collision_scale, collision_steps, what)
         return dict(collision_scale=collision_scale, collision_steps=collision_steps)
 
+    def _check_solver(self, sampling_solver, sampling_timesteps, ddim_sampling_eta, what="sample"):
+        """The refusals of ``sampling_solver``, before anything is computed or drawn -- an unknown name, no ``sampling_timesteps``,
+        ``ddim_sampling_eta != 0`` -> the keyword the strided loop receives: none at all without a solver, so that call stays what it
+        was."""
+        if sampling_solver is None:
+            return {}
+        from .diffusion_ddpm import _check_solver
+        strided = None if sampling_timesteps is None else self._check_strided(sampling_timesteps, ddim_sampling_eta)
+        return dict(sampling_solver=_check_solver(sampling_solver, strided, what))
+
     def _check_guidance(self, text, partial_boxes=None, input_boxes=None, ret_traj=False):
         """The refusals of ``guidance_scale``, before anything is computed or drawn."""
         if not self.text_condition:
@@ -387,11 +402,12 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
                         clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                        ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None):
+                        ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None,
+                        sampling_solver=None):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
                               clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
                               **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
-                              **_steer_kwargs(collision_scale, collision_steps))
+                              **_steer_kwargs(collision_scale, collision_steps), **_solver_kwargs(sampling_solver))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -416,7 +432,7 @@ class DiffusionSceneLayout_DDPM(Module):
         return _check_ddim(int(self.config["diffusion_kwargs"].get("time_num", 1000)), sampling_timesteps, ddim_sampling_eta)
 
     def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta,
-                          seeded={}, steer={}):
+                          seeded={}, steer={}, solver={}):
         """The strided completion call behind complete_scene / complete_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``complete_samples_ragged_ddim``."""
         device = room_mask.device
@@ -428,10 +444,10 @@ class DiffusionSceneLayout_DDPM(Module):
         return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                            condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
                                                            sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                           **seeded, **steer)
+                                                           **seeded, **steer, **solver)
 
     def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta,
-                         seeded={}):
+                         seeded={}, solver={}):
         """The strided re-arrangement call behind arrange_scene / arrange_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``arrange_samples_ddim``."""
         device = room_mask.device
@@ -442,22 +458,25 @@ class DiffusionSceneLayout_DDPM(Module):
         print('scene arrangement sampling')
         return self.diffusion.arrange_samples_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                    condition_cross=condition_cross, input_boxes=input_boxes,
-                                                   sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, **seeded)
+                                                   sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta, **seeded,
+                                                   **solver)
 
     @torch.no_grad()
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                       ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
+                       ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None):
         """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
         every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
         x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part.  ``collision_scale`` / ``collision_steps``:
-        collision steering (see ``sample``); the given objects repel the free ones and are never moved."""
+        collision steering (see ``sample``); the given objects repel the free ones and are never moved.  ``sampling_solver``:
+        "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
                               ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds,
@@ -467,14 +486,16 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def arrange_scene(self, room_mask, num_points, point_dim, input_boxes, batch_size=1, ret_traj=False, ddim=False,
                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                      ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
+                      ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None):
         """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop.
-        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only."""
+        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
+        ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
-            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded, solver)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, ret_traj=ret_traj,
                               ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_seed_kwargs(scene_seeds))
@@ -535,15 +556,17 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
                                 batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                                guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None):
+                                guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None,
+                                sampling_solver=None):
         """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own.
         ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``).  ``scene_seeds``: one seed per
         scene (``_seeded``): scene b can then be regenerated alone, or the batch split over calls and devices.  ``collision_scale`` /
-        ``collision_steps``: collision steering, a weight per scene (see ``sample``)."""
+        ``collision_steps``: collision steering, a weight per scene (see ``sample``).  ``sampling_solver``: "dpmpp_2m" with
+        ``sampling_timesteps`` (see ``sample``)."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
                               **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
-                              **_steer_kwargs(collision_scale, collision_steps))
+                              **_steer_kwargs(collision_scale, collision_steps), **_solver_kwargs(sampling_solver))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
@@ -592,7 +615,8 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
                                clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
-                               ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None):
+                               ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None,
+                               sampling_solver=None):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
@@ -603,16 +627,17 @@ class DiffusionSceneLayout_DDPM(Module):
         given rows re-noised with fresh noise before every model call -- so at eta = 0 the free rows are deterministic given x_T and
         those draws, not given x_T alone; x_start always clamped, ``clip_denoised`` ignored) instead of the T-step one.
         ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); the given objects repel the
-        free ones and are never moved."""
+        free ones and are never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         device = room_mask.device
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene_batched")
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
         seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
@@ -628,11 +653,13 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
                               batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0, scene_seeds=None,
-                              collision_scale=None, collision_steps=None):
+                              collision_scale=None, collision_steps=None, sampling_solver=None):
         """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
         each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead.
-        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only."""
+        ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
+        ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         self._check_steer(collision_scale, collision_steps, (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene_batched")
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
             raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
         if batch_size is None:
@@ -644,7 +671,7 @@ class DiffusionSceneLayout_DDPM(Module):
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
-            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded)
+            samples = self._arrange_strided(room_mask, num_points, point_dim, input_boxes, batch_size, S, eta, seeded, solver)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, input_boxes=input_boxes, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds, **_seed_kwargs(scene_seeds))
@@ -711,7 +738,7 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                              scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None):
+                              scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None, sampling_solver=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -725,8 +752,9 @@ class DiffusionSceneLayout_DDPM(Module):
         it back (``inpaint_samples_guided`` / ``inpaint_samples_guided_ddim``).  Needs ``text``; refused, before anything is drawn, on a
         model without ``text_condition`` and on a text encoder that does not give (B, L, text_embed_dim) features.
         ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); a known element enters the
-        boxes with its known value and is never moved."""
+        boxes with its known value and is never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         from .. import ops
+        solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "inpaint_scene_batched")
         if self.room_partial_condition or self.room_arrange_condition:
             raise ValueError("inpaint_scene_batched: a room_partial_condition / room_arrange_condition model conditions on a prefix / a "
                              "sub-shape of the scene (complete_scene_batched, arrange_scene_batched)")
@@ -778,13 +806,13 @@ class DiffusionSceneLayout_DDPM(Module):
                           **steer)
             if sampling_timesteps is not None:
                 samples = self.diffusion.inpaint_samples_guided_ddim((B, N, C), device, sampling_timesteps=S, ddim_sampling_eta=eta,
-                                                                     **guided)
+                                                                     **guided, **solver)
             else:
                 samples = self.diffusion.inpaint_samples_guided((B, N, C), device, clip_denoised=clip_denoised, **guided)
         elif sampling_timesteps is not None:
             samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
                                                           known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded,
-                                                          **steer)
+                                                          **steer, **solver)
         else:
             samples = self.diffusion.inpaint_samples((B, N, C), device, condition=condition, condition_cross=condition_cross,
                                                      clip_denoised=clip_denoised, known=known, mask=mask, **seeded, **steer)
@@ -817,6 +845,11 @@ def _steer_kwargs(collision_scale, collision_steps):
     if collision_scale is None and collision_steps is None:
         return {}
     return dict(collision_scale=collision_scale, collision_steps=collision_steps)
+
+
+def _solver_kwargs(sampling_solver):
+    """The solver keyword ``sample`` receives: none at all without a solver, so that call stays what it was."""
+    return {} if sampling_solver is None else dict(sampling_solver=sampling_solver)
 
 
 def _guidance_kwargs(guidance_scale):

@@ -1006,6 +1006,77 @@ def box_repulsion(x0, bounds, bbox_dim=8, class_dim=1):
     return energy, grad
 
 
+# ---------------------------------------------------------------------------------- multistep solver
+
+SOLVERS = ("dpmpp_2m",)            # sampling_solver= of the strided loops
+
+
+def multistep_weights(pairs, alphas_cumprod):
+    """The (S,) float32 history weights of dsc_multistep_x0_f32 for the (t, t_next) ``pairs`` of ddim_schedule and
+    the float64 ``alphas_cumprod`` (T,): with lambda(t) = 1/2 ln(abar_t / (1 - abar_t)) and h_k = lambda(t_next_k) - lambda(t_k),
+    e_0 = 0, e_k = h_k / (2 h_{k-1}) for 1 <= k <= S - 2, e_{S-1} = 0 (the last pair, t_next = -1, takes x0).  Float64 on the host, one
+    rounding; a CPU tensor."""
+    ac = torch.as_tensor(alphas_cumprod, dtype=torch.float64).to("cpu")
+    if ac.dim() != 1 or ac.dtype != torch.float64:
+        raise ValueError("alphas_cumprod must be a (T,) float64 table")
+    lam = 0.5 * torch.log(ac / (1.0 - ac))
+    S = len(pairs)
+    e = torch.zeros((S,), dtype=torch.float64)
+    h = [float(lam[tn] - lam[t]) if tn >= 0 else 0.0 for t, tn in pairs]
+    for k in range(1, S - 1):
+        e[k] = h[k] / (2.0 * h[k - 1])
+    return e.to(torch.float32)
+
+
+def multistep_rec(x_t, model_out, hist, weights, mean_type, tables, strided=None, rows=None, mask=None, q=(), scale=None, x_dup=None,
+                  t=None, clip=None):
+    """The launch record of the multistep solver (dsc_multistep_x0_f32): ``model_out`` (B, ...) -- (2 B, ...) under ``scale`` -- is
+    corrected in place between the (steered) model call and the strided step, ``hist`` (x_t's shape) keeps the clamped x0 of the pair.
+    It takes the operand groups of step_rec under the same keywords, as steer_rec does: ``strided`` (its step counter and times -- the
+    solver rides on the strided loops only), ``tables`` (ca, cb first; the rest, ``q`` and ``x_dup`` belong to the step), the given part
+    ``rows`` = (partial, _, counts) or ``mask`` = (known, _, mask), guidance ``scale``.  ``weights``: the (S,) f32 table of
+    multistep_weights on the device.  ``x_t`` may be None for mean type x0."""
+    if rows is not None and mask is not None:
+        raise ValueError("diffuscene_amd: multistep_x0 takes one given part, rows or mask")
+    if strided is None or t is not None:
+        raise ValueError("diffuscene_amd: multistep_x0 rides on a strided loop: strided=(step, times, times_next, coef)")
+    _c(model_out, "model_out"); _c(hist, "hist"); _c(weights, "weights")
+    mult = 1 if scale is None else 2
+    b = model_out.shape[0] // mult
+    shape = (b,) + tuple(model_out.shape[1:])
+    if x_t is not None:
+        _c(x_t, "x_t")
+    elif mean_type != MEAN_X0:
+        raise RuntimeError("diffuscene_amd: multistep_x0 needs x_t unless the model predicts x0")
+    if model_out.dim() < 2 or model_out.shape[0] != mult * b or b < 1 or tuple(hist.shape) != shape \
+            or (x_t is not None and tuple(x_t.shape) != shape):
+        raise RuntimeError("diffuscene_amd: multistep_x0: x_t %s, model_out %s and hist %s do not go together"
+                           % (None if x_t is None else tuple(x_t.shape), tuple(model_out.shape), tuple(hist.shape)))
+    ca, cb = tables[0], tables[1]
+    T = _table_rows(*tables) if any(tb is not None for tb in tables) else 2 ** 31 - 1
+    (sp, tmp, _, _, _, _), S = _strided_run(*strided)
+    if tuple(weights.shape) != (S,):
+        raise RuntimeError("diffuscene_amd: weights must be (%d,) f32 (ops.multistep_weights), got %s" % (S, tuple(weights.shape)))
+    counts = mk = None
+    pmax = c = 0
+    if rows is not None:
+        partial, counts = rows[0], _dev(rows[2], "counts", torch.int64)
+        if len(shape) != 3 or partial.dim() != 3 or partial.shape[0] != b or partial.shape[2] != shape[2] \
+                or not 1 <= partial.shape[1] <= shape[1] or tuple(counts.shape) != (b,) or not counts.is_contiguous():
+            raise RuntimeError("diffuscene_amd: partial must be (%d, Pmax <= N, C) of a (B, N, C) state with (%d,) counts, got %s / %s"
+                               % (b, b, tuple(partial.shape), tuple(counts.shape)))
+        pmax, c = partial.shape[1], shape[2]
+    if mask is not None:
+        mk = _dev(mask[2], "mask", torch.uint8)
+        if tuple(mk.shape) != shape or not mk.is_contiguous():
+            raise RuntimeError("diffuscene_amd: mask must be contiguous %s, got %s" % (shape, tuple(mk.shape)))
+    if scale is not None and tuple(_c(scale, "scale").shape) != (b,):
+        raise RuntimeError("diffuscene_amd: scale must be a (%d,) f32 tensor (ops.guidance_scales), got %s" % (b, tuple(scale.shape)))
+    args = (_opt(x_t), model_out.data_ptr(), hist.data_ptr(), weights.data_ptr(), sp, tmp, _opt(ca), _opt(cb), _opt(scale), _opt(counts),
+            _opt(mk), mean_type, b, hist.numel() // b, pmax, c, S, T)
+    return "dsc_multistep_x0_f32", args, (x_t, model_out, hist, weights, tables, strided, rows, mask, scale)
+
+
 def scene_gate(x, keep, out=None):
     """y[b] = keep[b] ? x[b] : 0 for a (B, ...) f32 tensor and a (B,) bool / uint8 device tensor; a dropped scene is not read.  See the C
     header."""

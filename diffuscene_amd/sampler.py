@@ -27,8 +27,11 @@ A loop is three orthogonal parts, the axes of the one step kernel (csrc/diffusio
   steering        _Steer (optional, ``steer=``): the per-scene weights and the step bound K in buffers of the graph, ONE launch
                   (dsc_steer_boxes_f32) after the model call that corrects its output in place; the step kernel is the unchanged one, and
                   without it the graph is what it is today.
-_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] main draw, given draw unless final, [cfg_combine,] ONE update launch
-laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
+  multistep       _Multistep (optional, ``multistep=``, strided rows only): the x0 history and the (S,) history weights of
+                  DPM-Solver++(2M) in buffers of the graph, ONE launch (dsc_multistep_x0_f32) after the steering in the replayed
+                  non-final graph -- the last pair has weight 0 and needs none; the step kernel is the unchanged one.
+_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] [multistep unless final,] main draw, given draw unless
+final, [cfg_combine,] ONE update launch laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
 The ten classes are rows:                    schedule   given            guided   fused=False unfuses
   _StepGraph                                 T steps    - / _Dense       -        (sub-batch chains: _chains_for, this row only)
   _DDIMGraph                                 strided    -                -
@@ -345,14 +348,17 @@ class _DDIMLoop(_LoopGraph):
     def _move(self):
         ops.ddim_advance(self.step, self.times, self.t)
 
-    def _begin(self, dtab):
-        """The tables of this run into the graph's own -> (the first timestep, S)."""
+    def _begin(self, dtab, weights=None):
+        """The tables of this run into the graph's own -> (the first timestep, S).  ``weights``: the (S,) history weights of a loop
+        with a multistep part."""
         pairs, times, times_next, coef = dtab
         assert len(pairs) == self.S
         self.check_current()
         self.times.copy_(times)                 # in place: the graphs hold these pointers
         self.times_next.copy_(times_next)
         self.coef.copy_(coef)
+        if self.multistep:
+            self.multistep.load(weights)
         return pairs[0][0], self.S
 
     def _end(self):
@@ -518,14 +524,33 @@ class _Steer:
         ops.issue(ops.steer_rec(g.x, mo, g.mean_type, steer=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
 
 
+class _Multistep:
+    """DPM-Solver++(2M) (dsc_multistep_x0_f32): one launch after the model call and the steering that moves the model output -- under
+    guidance the 2 B output, with the scales -- so that the unchanged strided step runs on the extrapolated x0 estimate, and keeps the
+    clamped x0 of the pair in ``hist``.  ``hist`` (B, N, C) and ``weights`` (S,) f32 are buffers of the graph, captured by pointer; the
+    weights are refreshed in place by _DDIMLoop._begin.  The first pair has weight 0 and does not read ``hist``, so nothing carries
+    over from one run to the next; the last pair has weight 0 and writes no history: ``final`` holds no launch."""
+
+    def __init__(self, g):
+        self.hist = torch.zeros(g.shape, device=g.device, dtype=torch.float32)
+        self.weights = torch.zeros((g.S,), device=g.device, dtype=torch.float32)
+
+    def load(self, weights):
+        self.weights.copy_(weights)             # in place: the graph holds this pointer
+
+    def apply(self, g, mo):
+        scale = dict(scale=g.guide.scale) if g.guide else {}
+        ops.issue(ops.multistep_rec(g.x, mo, self.hist, self.weights, g.mean_type, **g.sched, **g.part.steer_operands(g), **scale))
+
+
 class _Loop:
     """One captured loop = a schedule (_PosteriorLoop or _DDIMLoop, by inheritance), a given part and guidance: the row a class below
     declares.  ``sched``: clip_denoised of a T-step loop, S of a strided one.  ``fused`` unfuses what the row has a kernel for: the
     overwrite of a ragged part, the guidance of a guided row.  ``partial_shape``: the shape of the given rows."""
-    given, guided, chains, what = _Given, False, False, None
+    given, guided, chains, what, multistep = _Given, False, False, None, None
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None,
-                 steer=None):
+                 steer=None, multistep=False):
         nch = (_chains_for(shape[0]),) if self.chains else ()
         super().__init__(diff, model, shape, device, condition, condition_cross, sched, replay, 2 if self.guided else 1, *nch)
         self.fused = fused
@@ -535,6 +560,9 @@ class _Loop:
         self.part = part(self, partial_shape, fused) if part is _Ragged else part(self, partial_shape)
         self.guide = _Guidance(self, fused) if self.guided else None
         self.steer = _Steer(self, steer) if steer is not None else None
+        if multistep and not self.strided:
+            raise ValueError("a multistep solver rides on the strided loops")
+        self.multistep = _Multistep(self) if multistep else None
         for owner in (self.part, self.guide):   # the buffers, by the names tests, tools and bench.py read
             for name in ("partial", "counts", "known", "mask", "scale", "m"):
                 if hasattr(owner, name):
@@ -569,12 +597,15 @@ class _Loop:
         return self.model_out
 
     def _step(self, final):
-        """[the unfused overwrite,] model call, [collision steering,] main draw, the given draw of the NEXT step unless final,
+        """[the unfused overwrite,] model call, [collision steering,] [the multistep launch unless final,] main draw, the given draw of
+        the NEXT step unless final,
         [cfg_combine,] one update launch, [the copy into the null half,] decrement or advance unless final."""
         self.part.before(self)
         mo = self._model_call()
         if self.steer:
             self.steer.apply(self, mo)
+        if self.multistep and not final:
+            self.multistep.apply(self, mo)
         noise = self._main_draw(final)
         given = self.part.operands(self, final)
         mo, guided = self.guide.apply(self, mo) if self.guide else (mo, {})
@@ -584,10 +615,11 @@ class _Loop:
         if not final:
             self._move()
 
-    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None):
+    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None, multistep=None):
         """``sched``: total_steps of a T-step loop, the device tables (GaussianDiffusion.ddim_tables) of a strided one.  ``values``: the
-        (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword)."""
-        t0, steps = self._begin(sched)
+        (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword).  ``multistep``: the
+        (S,) history weights of a loop with a multistep part."""
+        t0, steps = self._begin(sched, *(() if self.multistep is None else (multistep,)))
         self._start(x_T, t0)
         if partial is not None:
             values += (partial,)
@@ -714,11 +746,16 @@ def _front_end(name, cls):
     clip_denoised or S, ``fused`` and the shape of the given rows -- never eta, counts, mask or scales, which live in buffers.
     ``steer`` (keyword; None: the loop and its graph as they are without it) = (weight (B,) f32 on the device, K, bounds, bbox_dim,
     class_dim) of GaussianDiffusion._steer_inputs: collision steering (_Steer) after every model call; the key gains the layout -- the
-    bounds and the two dims --, never the weights or K."""
+    bounds and the two dims --, never the weights or K.
+    ``multistep`` (keyword, strided rows; None: the loop and its graph as they are without it) = the (S,) f32 history weights of
+    GaussianDiffusion.multistep_table on the device: DPM-Solver++(2M) (_Multistep) after the steering of every pair but the last; the key
+    gains the flag, never the weights."""
     names = (("scale",) if cls.guided else ()) + (("sampling_timesteps", "eta") if cls.strided else ("clip_denoised", "total_steps")) \
         + ("noise_fn",) + cls.given.values + (("fused",) if cls.guided or cls.given is _Ragged else ())
 
-    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, **kw):
+    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, multistep=None, **kw):
+        if multistep is not None and not cls.strided:
+            raise ValueError("%s: a multistep solver rides on the strided loops" % name)
         if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
             raise TypeError("%s(diff, denoise_fn, shape, device, condition, condition_cross, %s)" % (name, ", ".join(names)))
         a = dict(dict.fromkeys(names), noise_fn=torch.randn, fused=True)
@@ -736,12 +773,13 @@ def _front_end(name, cls):
                                            shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
         out = _cached_loop(
             name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"],
-            (cls.__name__, sched, bool(a["fused"]), gshape) + (() if steer is None else (layout,)),
+            (cls.__name__, sched, bool(a["fused"]), gshape) + (() if steer is None else (layout,))
+            + (() if multistep is None else ("multistep",)),
             lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape,
-                                           layout),
+                                           layout, multistep is not None),
             lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else n_given, *([a["scale"]] if cls.guided else []), *given,
                                                   noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given),
-                                                  steer=None if steer is None else steer[:2]),
+                                                  steer=None if steer is None else steer[:2], multistep=multistep),
             mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
         if cls.given is _Dense and given:
             out[:, :gshape[1], :] = given[0]            # clean objects restored after the last step (:471-473)

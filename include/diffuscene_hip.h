@@ -489,6 +489,25 @@ int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int64_t* t, co
                         int32_t pmax, int32_t c, int32_t bbox_dim, int32_t class_dim, int32_t num_steps, int32_t num_timesteps,
                         dsc_stream_t stream);
 
+/* Multistep DPM-Solver++(2M): one launch between the model call (after dsc_steer_boxes_f32, if any) and the unchanged strided step,
+ * correcting model_out IN PLACE so that the step's x0 estimate becomes the extrapolated one (INTEGRATION.md 9 states the definition).
+ * At pair k = step[0] of num_steps, with e = weights[k] (the (num_steps,) float32 history weights, e_0 = e_{S-1} = 0, computed on the
+ * host in float64), for every free element of scene i:
+ *   m     = model_out, or u + cfg_scale[i] * (c - u) from the two halves of a (2 b, inner) model_out when cfg_scale is set (float32);
+ *   x0raw = predict_x0(x_t, m) in float32 as the step forms it; x0c = clamp(x0raw, -1, 1);
+ *   float64 from here, one final rounding: D = x0c + e (x0c - hist); d = x0raw - D; mean type x0: m -= d; eps / v: m += d / cb[t]
+ *   (cb[t] == 0: no store); with cfg_scale the same delta is added to both halves;
+ *   hist  = x0c.
+ * e == 0: hist is not read, model_out is not written.  hist is written on every pair but the last (k == num_steps - 1), where nothing
+ * is read or stored.  A given element -- rows [0, counts[i]) of pmax <= inner / c rows of c channels, or mask != 0 (x_t's shape), at most
+ * one of the two, both may be NULL -- is neither read nor written in x_t, model_out and hist.  ca / cb / x_t may be NULL for mean type
+ * x0; cfg_scale may be NULL.  step[0] and times[k] are clamped and counted once per launch, counts[i] once per scene
+ * (dsc_device_error_count).  b <= 65535 (else DSC_ERANGE); two given parts: DSC_EINVAL. */
+int dsc_multistep_x0_f32(const float* x_t, float* model_out, float* hist, const float* weights, const int64_t* step,
+                         const int64_t* times, const float* ca, const float* cb, const float* cfg_scale, const int64_t* counts,
+                         const uint8_t* mask, int32_t mean_type, int32_t b, int64_t inner, int32_t pmax, int32_t c, int32_t num_steps,
+                         int32_t num_timesteps, dsc_stream_t stream);
+
 /* Per-scene gate of the text-condition dropout (text_drop_prob): y[i, :] = keep[i] ? x[i, :] : 0 for b scenes of `inner` elements;
  * keep holds one byte per scene.  A select: the elements of a dropped scene are not read (NaN there does not propagate).  Used forward
  * on the text features and backward on their incoming gradient.  y may alias x. */
