@@ -308,6 +308,188 @@ __global__ __launch_bounds__(256) void steer_boxes_kernel(const SteerArgs p) {
     }
 }
 
+// Floor-plan steering, the field: once per call, never inside the loop.  The mask image (h rows along z, w columns
+// along x, inside iff > 0.5) covers [-s, s]^2, s = room_side; dx = 2 s / w, dz = 2 s / h.
+//   F[i, j] = 1/2 min over inside (i', j') of ((i - i') dz)^2 + ((j - j') dx)^2,  0 where no pixel is inside,
+// float64, rounded once.  The minimum is taken exactly in two passes: every float64 operation of the expression is monotone in
+// |i - i'|, so for a column j' the nearest inside row decides.  One block per (scene, row i): thread j' < w walks column j' outwards
+// from row i to its nearest inside pixel and stages ((i - i') dz)^2 in LDS (infinity: none); thread j < w then takes the minimum over
+// j' of the staged term plus ((j - j') dx)^2 -- the very expressions of the definition, so the result is the float32 nearest to it.
+constexpr int WALL_MAXHW = 256;
+
+__global__ __launch_bounds__(256) void floor_field_kernel(const float* __restrict__ mask, float* __restrict__ field, int h, int w,
+                                                          float room_side) {
+    __shared__ double col[WALL_MAXHW];
+    const int i = blockIdx.x, b = blockIdx.y, j = threadIdx.x;
+    const double rs = (double)room_side;
+    const double dx = 2.0 * rs / (double)w, dz = 2.0 * rs / (double)h;
+    const float* m = mask + (int64_t)b * h * w;
+    if (j < w) {
+        int d = -1;
+        for (int k = 0; k < h; ++k) {                                                        // |i - i'| = k, nearest first
+            const bool up = i - k >= 0 && m[(int64_t)(i - k) * w + j] > 0.5f;
+            const bool down = i + k < h && m[(int64_t)(i + k) * w + j] > 0.5f;
+            if (up || down) {
+                d = k;
+                break;
+            }
+        }
+        const double a = (double)d * dz;
+        col[j] = d < 0 ? (double)INFINITY : a * a;
+    }
+    __syncthreads();
+    if (j >= w) return;
+    double best = (double)INFINITY;
+    for (int k = 0; k < w; ++k) {
+        const double c = (double)(j - k) * dx;
+        const double cc = c * c;
+        const double v = col[k] + cc;
+        best = fmin(best, v);
+    }
+    const double f = 0.5 * best;
+    field[((int64_t)b * h + i) * w + j] = best == (double)INFINITY ? 0.f : (float)f;
+}
+
+// Floor-plan steering, the launch inside the loop: after collision steering (if any), before the multistep launch and the guidance mix.
+// One 256-thread block per scene, n <= 160, modelled on steer_boxes_kernel -- the same time sources, given parts, guidance operand and
+// the same clamped x0 row per thread:
+//   1. thread i < n forms row i of the clamped x0 estimate (steer_boxes_kernel, phase 1) and de-normalises the centre and half sizes;
+//      (c, s) = the (cos, sin) channels over their hypot (a zero pair: angle 0); valid iff the empty logit < 0;
+//   2. a valid thread visits its nine footprint points p_ab = centre_xz + R (a sx, b sz), a, b in {-1, 0, 1} in (a, b) order, R the
+//      rotation about y (x' = c lx - s lz, z' = s lx + c lz), and at each: u = (x + s) / dx - 1/2, v = (z + s) / dz - 1/2, clamped to
+//      the pixel centres, the cell j0 = min(floor(uc), w - 2), i0 likewise, and
+//      e(p) = bilinear(F; i0, j0, fv, fu) + 1/2 ((u - uc) dx)^2 + 1/2 ((v - vc) dz)^2 with its derivative by the point: inside the
+//      image the slope of the bilinear patch, outside the quadratic continuation; 36 float32 field reads per box, served by L2;
+//   3. E = sum over valid boxes of (1/9) sum e(p) in the fixed order of block_sum_steer, `outside` = the number of valid boxes with a
+//      point of e > 0, g = dE / d x0[:, {0, 2}] (* span / 2; y stays 0), and on an active step -- t < *t_below and weight[b] != 0 --
+//      the store of steer_boxes_kernel on channels 0 and 2.
+// float64 after the float32 x0 and the float32 field, one final rounding.  An inactive launch without optional outputs returns before
+// it reads the scene.  field_b == 1: one field shared by every scene.  room_side is read through its pointer, as weight and t_below.
+struct WallArgs {
+    const float* xt; float* mo;
+    const int64_t *t, *step, *times;
+    const float *ca, *cb, *partial;
+    const int64_t* counts;
+    const float* known;
+    const uint8_t* mask;
+    const float *scale, *weight;
+    const int64_t* t_below;
+    const float *field, *room_side;
+    float *energy, *grad;
+    int32_t* outside;
+    int mean_type, b, n, pmax, c, empty_col, S, T, field_b, h, w;
+    double c_lo[3], c_span[3], s_lo[3], s_span[3];
+};
+
+__global__ __launch_bounds__(256) void steer_walls_kernel(const WallArgs p) {
+    __shared__ double red[4];
+    const int b = blockIdx.x, tid = threadIdx.x, N = p.n, C = p.c, H = p.h, W = p.w;
+    const bool first = tid == 0;
+    const bool is_x0 = p.mean_type == DSC_MEAN_X0;
+    int64_t tv;
+    if (p.t) tv = dsc_checked_index(p.t[b], p.T, first);
+    else tv = dsc_checked_index(p.times[dsc_checked_index(p.step[0], p.S, first && b == 0)], p.T, first && b == 0);
+    int64_t cnt = 0;
+    if (p.counts) cnt = dsc_checked_index(p.counts[b], (int64_t)p.pmax + 1, first);
+    const float w = p.weight[b];
+    const bool active = w != 0.f && tv < p.t_below[0];
+    if (!active && !p.energy && !p.grad && !p.outside) return;                               // the whole block: nothing is stored
+    const float A = is_x0 ? 0.f : p.ca[tv], Bc = is_x0 ? 0.f : p.cb[tv];
+    const float s = p.scale ? p.scale[b] : 0.f;
+    const int64_t base = (int64_t)b * N * C, half = (int64_t)p.b * N * C;
+    const int64_t row = base + (int64_t)tid * C;
+    float raw[3] = {0.f, 0.f, 0.f}, x0c[3] = {0.f, 0.f, 0.f};
+    bool is_free[3] = {false, false, false}, ok = false;
+    double g[3] = {0., 0., 0.}, e = 0., out = 0.;
+    if (tid < N) {
+        const bool row_given = p.counts && tid < cnt;
+        const int64_t grow = ((int64_t)b * p.pmax + tid) * C;
+        float v[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const int ch = k < 8 ? k : p.empty_col;
+            const bool given = row_given || (p.mask && p.mask[row + ch] != 0);
+            if (given) {
+                v[k] = row_given ? p.partial[grow + ch] : p.known[row + ch];
+            } else {
+                float m = p.mo[row + ch];
+                if (p.scale) m = cfg_mix(m, p.mo[half + row + ch], s);
+                const float r = predict_x0(is_x0 ? 0.f : p.xt[row + ch], m, A, Bc, p.mean_type, false);
+                v[k] = fminf(fmaxf(r, -1.0f), 1.0f);
+                if (k < 3) raw[k] = r, x0c[k] = v[k];
+            }
+            if (k < 3) is_free[k] = !given;
+        }
+        ok = v[8] < 0.f;
+        if (ok) {
+            const double cx = ((double)v[0] + 1.0) * 0.5 * p.c_span[0] + p.c_lo[0];
+            const double cz = ((double)v[2] + 1.0) * 0.5 * p.c_span[2] + p.c_lo[2];
+            const double sx = ((double)v[3] + 1.0) * 0.5 * p.s_span[0] + p.s_lo[0];
+            const double sz = ((double)v[5] + 1.0) * 0.5 * p.s_span[2] + p.s_lo[2];
+            const double cs = (double)v[6], sn = (double)v[7];
+            const double hyp = sqrt(cs * cs + sn * sn);
+            double rc = 1.0, rsn = 0.0;
+            if (hyp > 0.) rc = cs / hyp, rsn = sn / hyp;
+            const double side = (double)p.room_side[0];
+            const double dx = 2.0 * side / (double)W, dz = 2.0 * side / (double)H;
+            const double rdx = 1.0 / dx, rdz = 1.0 / dz;                                      // a float64 division is a long serial chain: two per box
+            const double umax = (double)(W - 1), vmax = (double)(H - 1);
+            const float* F = p.field + (p.field_b == 1 ? 0 : (int64_t)b * H * W);
+            double esum = 0., gx = 0., gz = 0.;
+            bool any = false;
+            for (int a = -1; a <= 1; ++a) {
+                for (int bb = -1; bb <= 1; ++bb) {
+                    const double lx = (double)a * sx, lz = (double)bb * sz;
+                    const double xa = rc * lx, xb = rsn * lz, za = rsn * lx, zb = rc * lz;
+                    const double px = cx + (xa - xb), pz = cz + (za + zb);
+                    const double u = (px + side) * rdx - 0.5, vv = (pz + side) * rdz - 0.5;
+                    const double uc = fmin(fmax(u, 0.), umax), vc = fmin(fmax(vv, 0.), vmax);  // fmax(NaN, 0) = 0: always a cell
+                    const int j0 = min(max((int)floor(uc), 0), W - 2), i0 = min(max((int)floor(vc), 0), H - 2);
+                    const double fu = uc - (double)j0, fv = vc - (double)i0;
+                    const float* cell = F + (int64_t)i0 * W + j0;
+                    const double f00 = (double)cell[0], f01 = (double)cell[1], f10 = (double)cell[W], f11 = (double)cell[W + 1];
+                    const double top = f00 + (f01 - f00) * fu, bot = f10 + (f11 - f10) * fu;
+                    const double bil = top + (bot - top) * fv;
+                    const double ou = (u - uc) * dx, ov = (vv - vc) * dz;
+                    const double ep = bil + 0.5 * (ou * ou) + 0.5 * (ov * ov);
+                    esum += ep;
+                    any = any || ep > 0.;
+                    // d e / d u: the patch's slope where u is inside the image, the continuation's where it is clamped
+                    const double su = (f01 - f00) + ((f11 - f10) - (f01 - f00)) * fv;
+                    const double sv = bot - top;
+                    gx += (u == uc ? su : ou * dx) * rdx;
+                    gz += (vv == vc ? sv : ov * dz) * rdz;
+                }
+            }
+            e = esum * (1.0 / 9.0);
+            out = any ? 1. : 0.;
+            g[0] = gx * (1.0 / 9.0), g[2] = gz * (1.0 / 9.0);
+        }
+    }
+    const double E = block_sum_steer(e, red);
+    const double O = block_sum_steer(out, red);
+    if (p.energy && first) p.energy[b] = (float)E;
+    if (p.outside && first) p.outside[b] = (int32_t)O;
+    if (tid >= N) return;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double gn = g[k] * p.c_span[k] * 0.5;                                           // d centre / d x0 = span / 2
+        if (p.grad) p.grad[((int64_t)b * N + tid) * 3 + k] = (float)gn;
+        if (k == 1 || !active || !ok || !is_free[k]) continue;
+        const double wg = (double)w * gn;
+        if (wg == 0. || (!is_x0 && Bc == 0.f)) continue;
+        const double d = wg + ((double)raw[k] - (double)x0c[k]);
+        const double delta = is_x0 ? -d : d / (double)Bc;
+        if (p.scale) {
+            const float c0 = p.mo[row + k], u0 = p.mo[half + row + k];
+            p.mo[row + k] = (float)((double)c0 + delta);
+            p.mo[half + row + k] = (float)((double)u0 + delta);
+        } else {
+            p.mo[row + k] = (float)((double)p.mo[row + k] + delta);
+        }
+    }
+}
+
 // Which elements of a scene are given (completion, in-painting) instead of sampled: none, the first counts[b] rows, or a byte mask.
 enum { GIVEN_NONE = 0, GIVEN_ROWS = 1, GIVEN_MASK = 2 };
 
@@ -946,6 +1128,49 @@ extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int
     }
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(steer_boxes_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_floor_field_f32(const float* mask, float* field, int32_t b, int32_t h, int32_t w, float room_side,
+                                   dsc_stream_t stream) {
+    if (!mask || !field || b < 1 || !(room_side > 0.f) || !(room_side < INFINITY)) return DSC_EINVAL;
+    if (h < 2 || w < 2 || h > WALL_MAXHW || w > WALL_MAXHW || b > 65535) return DSC_ERANGE;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(floor_field_kernel, dim3(h, b), dim3(256), 0, static_cast<hipStream_t>(stream), mask, field, h, w, room_side);
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_steer_walls_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                                   const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                                   const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
+                                   const float* bounds, const float* field, const float* room_side, float* energy_out, float* grad_out,
+                                   int32_t* outside_out, int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c,
+                                   int32_t bbox_dim, int32_t class_dim, int32_t num_steps, int32_t num_timesteps, int32_t field_b,
+                                   int32_t h, int32_t w, dsc_stream_t stream) {
+    if (!model_out || !weight || !t_below || !bounds || !field || !room_side || b < 1 || n < 1 || c < 1 || num_timesteps < 1)
+        return DSC_EINVAL;
+    if (t ? step || times : !step || !times || num_steps < 1) return DSC_EINVAL;            // one time source
+    if (bad_mean_args(mean_type, ca, cb) || (mean_type != DSC_MEAN_X0 && !x_t)) return DSC_EINVAL;
+    if ((partial != nullptr) != (counts != nullptr) || (known != nullptr) != (mask != nullptr) || (partial && known)) return DSC_EINVAL;
+    if (partial && (pmax < 1 || pmax > n)) return DSC_EINVAL;
+    if (class_dim < 1 || bbox_dim < 1 || bbox_dim + class_dim > c) return DSC_EINVAL;        // a re-arrangement sub-shape has no such layout
+    if (field_b != 1 && field_b != b) return DSC_EINVAL;
+    if (bbox_dim != 8 || n > STEER_MAXN) return DSC_ERANGE;                                  // [translation 3 | size 3 | cos, sin]
+    if (h < 2 || w < 2 || h > WALL_MAXHW || w > WALL_MAXHW) return DSC_ERANGE;
+    WallArgs p{};
+    p.xt = x_t, p.mo = model_out, p.t = t, p.step = step, p.times = times, p.ca = ca, p.cb = cb;
+    p.partial = partial, p.counts = counts, p.known = known, p.mask = mask, p.scale = cfg_scale, p.weight = weight, p.t_below = t_below;
+    p.field = field, p.room_side = room_side, p.energy = energy_out, p.grad = grad_out, p.outside = outside_out;
+    p.mean_type = mean_type, p.b = b, p.n = n, p.pmax = partial ? pmax : 0, p.c = c, p.empty_col = bbox_dim + class_dim - 1;
+    p.S = t ? 0 : num_steps, p.T = num_timesteps, p.field_b = field_b, p.h = h, p.w = w;
+    for (int k = 0; k < 3; ++k) {
+        p.c_lo[k] = bounds[k], p.c_span[k] = (double)bounds[3 + k] - (double)bounds[k];
+        p.s_lo[k] = bounds[6 + k], p.s_span[k] = (double)bounds[9 + k] - (double)bounds[6 + k];
+    }
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(steer_walls_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     DSC_LAUNCH_CHECK();
     return 0;
 }

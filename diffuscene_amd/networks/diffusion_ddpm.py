@@ -20,6 +20,8 @@ each a generator of states (x_T, then the state after every step), and two indep
                    written
   the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine); under ``collision_scale`` _steered wraps either:
                    the model call, collision steering of its output in place (dsc_steer_boxes_f32), then the guidance mix
+                   under ``wall_scale`` _walled wraps any of them: floor-plan steering (dsc_steer_walls_f32) at the head of the ``post``
+                   hook of the model call -- after the collision steering, before the solver's launch and the guidance mix
   the solver       ``sampling_solver="dpmpp_2m"`` (strided loops): _strided_states hands the model call a ``post`` hook that issues
                    dsc_multistep_x0_f32 on the (steered) output, before the guidance mix, on every pair but the last; the step is unchanged
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
@@ -211,6 +213,40 @@ def _steered(model, diff, device, steer, part, scale=None):
 def _steer_kw(collision_scale, collision_steps):
     """The steering keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
     return {} if collision_scale is None and collision_steps is None else dict(steer=(collision_scale, collision_steps))
+
+
+def _walled(model, diff, device, walls, part, scale=None):
+    """The model call of a loop under floor-plan steering: ``model`` -- any of the calls above -- with one more launch
+    (dsc_steer_walls_f32) at the head of its ``post`` hook: on the output after collision steering, before the multistep launch and the
+    guidance mix, the place it has in the captured loop.  ``scale``: the (B,) guidance scales of a guided ``model``."""
+    weight, k, bounds, bbox_dim, class_dim, field, room_side = walls
+    ca, cb = diff._coeffs(diff.tables(device))
+    spec = (weight, torch.full((1,), k, device=device, dtype=torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim, field,
+            torch.full((1,), room_side, device=device, dtype=torch.float32))
+
+    def call(x, t_, post=None):
+        def walls_then(x, mo):
+            ops.issue(ops.walls_rec(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale,
+                                    **part.steer_operands()))
+            if post is not None:
+                post(x, mo)
+        return model(x, t_, walls_then)
+    return call
+
+
+def _renamed_bounds(diff):
+    """box_bounds of ``diff`` with the floor-plan keyword in its refusal."""
+    try:
+        return diff.box_bounds()
+    except ValueError as e:
+        raise ValueError(str(e).replace("collision_scale", "wall_scale")) from None
+
+
+def _wall_kw(wall_scale, wall_steps, room_side, room_mask):
+    """The floor-plan keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
+    if wall_scale is None and wall_steps is None and room_side is None:
+        return {}
+    return dict(walls=(wall_scale, wall_steps, room_side, room_mask))
 
 
 def _solver_kw(sampling_solver):
@@ -540,14 +576,14 @@ class GaussianDiffusion:
 
     def p_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                       clip_denoised=True, keep_running=False, graph=None,
-                      collision_scale=None, collision_steps=None):
+                      collision_scale=None, collision_steps=None, wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Generate samples, reference :355-371 (draw order: x_T, then one draw per step)."""
         return self._loop("p_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     def _loop(self, what, denoise_fn, shape, device, condition, condition_cross, noise_fn, graph, strided=None, given=None, scale=None,
-              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None, multistep=None):
+              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None, multistep=None, walls=None):
         """What every public loop does behind its signature.  The spec: ``strided`` = (sampling_timesteps, ddim_sampling_eta) or None for
         T steps; ``given`` = None, ("dense", partial_boxes), ("ragged", partial_boxes, num_partial) or ("mask", known, mask); ``scale`` =
         the guidance scale or None.  Validates (ValueError names ``what``), keeps (eta, S) on the instance as the reference does (:404-405),
@@ -555,7 +591,9 @@ class GaussianDiffusion:
         otherwise runs the eager core on the given part and the model call of the spec.  ``say_last``: the reference's print, after the
         eager loop / before the captured one; ``all_states``: the list of states (eager).  ``steer`` = (collision_scale, collision_steps)
         or None: collision steering after every model call (_steer_inputs), on either path.  ``multistep`` = the name of a multistep
-        solver (ops.SOLVERS) or None: the strided loop takes its steps on the solver's extrapolated x0 (_check_solver)."""
+        solver (ops.SOLVERS) or None: the strided loop takes its steps on the solver's extrapolated x0 (_check_solver).
+        ``walls`` = (wall_scale, wall_steps, room_side, room_mask) or None: floor-plan steering after the collision steering
+        (_wall_inputs), on either path."""
         assert isinstance(shape, (tuple, list))
         if strided is not None:
             S, eta = _check_ddim(self.num_timesteps, *strided)
@@ -570,6 +608,8 @@ class GaussianDiffusion:
             values = self._masked_inputs(shape, device, *values, what)
         if steer is not None:
             steer = self._steer_inputs(shape, device, *steer, what)
+        if walls is not None:
+            walls = self._wall_inputs(shape, device, *walls, what)
         if scale is not None:
             condition, condition_cross, scale = self._guided_inputs(shape, device, condition, condition_cross, scale, what)
         if strided is not None:
@@ -584,7 +624,8 @@ class GaussianDiffusion:
             front = getattr(sampler, front_end_name(strided is not None, kind, scale is not None))
             return front(self, denoise_fn, tuple(shape), device, condition, condition_cross, *(() if scale is None else (scale,)), *sched,
                          noise_fn, *values, **({} if steer is None else dict(steer=steer)),
-                         **({} if multistep is None else dict(multistep=self.multistep_table(S, device))))
+                         **({} if multistep is None else dict(multistep=self.multistep_table(S, device))),
+                         **({} if walls is None else dict(walls=walls)))
         part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
             self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
         if steer is None:
@@ -594,6 +635,8 @@ class GaussianDiffusion:
         else:                                   # the denoiser at 2 B, steered with the scales, then mixed
             model = _steered(lambda x, t_: denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), condition, condition_cross),
                              self, device, steer, part, scale)
+        if walls is not None:
+            model = _walled(model, self, device, walls, part, scale)
         if strided is not None:
             states = self._strided_states(model, shape, device, noise_fn, S, eta, part,
                                           *(() if multistep is None else ((scale,),)))
@@ -688,7 +731,8 @@ class GaussianDiffusion:
     @torch.no_grad()
     def ddim_sample_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
                          sampling_timesteps=50, ddim_sampling_eta=0., return_all_timesteps=False, graph=None,
-                         collision_scale=None, collision_steps=None, sampling_solver=None):
+                         collision_scale=None, collision_steps=None,
+                         wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
         """DDIM sampling, reference :402-444 (its two call-site slips bridged: model_predictions gets ``denoise_fn``, and there is no
         self-conditioning).  Draw order: x_T, then one draw per pair except the last ((t, -1) takes x_start): S draws in all.
         x_start is always clamped to [-1, 1], as in the reference, whatever ``clip_denoised`` says.  The network runs on the static
@@ -699,7 +743,8 @@ class GaussianDiffusion:
         D = x0 + e_k (x0 - x0_prev); same draws, needs ddim_sampling_eta == 0, S <= 2 is DDIM bit for bit."""
         return self._loop("ddim_sample_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), all_states=return_all_timesteps,
-                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
+                          **_steer_kw(collision_scale, collision_steps),
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
 
     # ------------------------------------------------------------------ classifier-free guidance
     def _guided_inputs(self, shape, device, condition, condition_cross, guidance_scale, what):
@@ -756,10 +801,39 @@ class GaussianDiffusion:
         k = ops.collision_steps(collision_steps, self.num_timesteps)
         return weight.to(device), k, self.box_bounds(), self.bbox_dim, self.class_dim
 
+    def _wall_inputs(self, shape, device, wall_scale, wall_steps, room_side, room_mask, what, field=True):
+        """(weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim, field (B or 1, H, W) f32 on the device, room_side) of a loop
+        under floor-plan steering (ops.walls_rec), or ValueError -- before anything is drawn.  At every step whose t < K the clamped x0
+        estimate of scene b moves by -weight[b] * d E / d x0[:, {0, 2}], E the out-of-room energy of the footprints of its non-empty
+        boxes over the distance field of ``room_mask``; ``wall_steps`` None steers every step.  ``field=False``: the
+        checks alone (the field is None)."""
+        B, N, C = shape
+        if wall_scale is None:
+            raise ValueError("%s: wall_steps and room_side go with wall_scale" % what)
+        if room_side is None:
+            raise ValueError("%s: wall_scale needs room_side, half the side in metres of the window the room mask was rendered in" % what)
+        side = ops.room_side_value(room_side)
+        if room_mask is None:
+            raise ValueError("%s: wall_scale needs the room_mask" % what)
+        ops.room_mask_dims(room_mask, B)
+        if (self.translation_dim, self.size_dim, self.angle_dim) != (3, 3, 2):
+            raise ValueError("%s: floor-plan steering needs translation_dim = 3, size_dim = 3 and angle_dim = 2 (cos, sin), got %d / %d / %d"
+                             % (what, self.translation_dim, self.size_dim, self.angle_dim))
+        if self.class_dim < 1 or C < self.bbox_dim + self.class_dim:
+            raise ValueError("%s: floor-plan steering needs the full object layout, at least %d channels, got %d"
+                             % (what, self.bbox_dim + max(self.class_dim, 1), C))
+        if N > ops.STEER_MAX_OBJECTS:
+            raise ValueError("%s: floor-plan steering handles at most %d objects per scene, got %d" % (what, ops.STEER_MAX_OBJECTS, N))
+        weight = ops.wall_scales(wall_scale, B, "cpu")
+        k = ops.wall_steps(wall_steps, self.num_timesteps)
+        bounds = _renamed_bounds(self)
+        return (weight.to(device), k, bounds, self.bbox_dim, self.class_dim,
+                ops.floor_field(room_mask.to(device), side) if field else None, side)
+
     @torch.no_grad()
     def p_sample_loop_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                              clip_denoised=True, keep_running=False, graph=None,
-                             collision_scale=None, collision_steps=None):
+                             collision_scale=None, collision_steps=None, wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Classifier-free guidance in T steps.  Scene b is the reference's p_sample_loop (:355-371) with
         m = u + w[b] * (c - u) in place of the model output inside p_mean_variance: c the denoiser on (x, t, condition, condition_cross),
         u the denoiser on (x, t, condition, 0) -- the null condition is condition_cross == 0, the features AFTER fc_text_f --, the
@@ -771,12 +845,13 @@ class GaussianDiffusion:
         replays one captured step whose update is the fused dsc_p_sample_cfg_f32, bit-identical."""
         return self._loop("p_sample_loop_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     @torch.no_grad()
     def ddim_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                          sampling_timesteps=50, ddim_sampling_eta=0., graph=None,
-                         collision_scale=None, collision_steps=None, sampling_solver=None):
+                         collision_scale=None, collision_steps=None,
+                         wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
         """Classifier-free guidance in S strided (DDIM) steps: scene b is the reference's ddim_sample_loop (:402-444) with the guided
         output m of p_sample_loop_guided in place of the model output inside model_predictions.  x_start is always clamped to [-1, 1].
         Draws: exactly those of ddim_sample_loop at batch B (x_T, then one per pair except the last).  The eager loop is built from the
@@ -784,22 +859,25 @@ class GaussianDiffusion:
         dsc_ddim_cfg_step_f32, bit-identical."""
         return self._loop("ddim_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), scale=guidance_scale,
-                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
+                          **_steer_kw(collision_scale, collision_steps),
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
 
     # ------------------------------------------------------------------ completion, in-painting, re-arrangement
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None,
-                               collision_scale=None, collision_steps=None):
+                               collision_scale=None, collision_steps=None,
+                               wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
         model call) and overwrites the first P rows of x_t in place; at t == 0 the clean objects are restored."""
         return self._loop("p_sample_loop_complete", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("dense", partial_boxes), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     @torch.no_grad()
     def p_sample_loop_complete_ragged(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                       clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None,
-                                      collision_scale=None, collision_steps=None):
+                                      collision_scale=None, collision_steps=None,
+                                      wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Scene completion of a batch whose scenes are given DIFFERENT numbers of objects.  ``partial_boxes`` is (B, Pmax, C) with
         1 <= Pmax <= N, ``num_partial`` the (B,) integer counts, 0 <= num_partial[b] <= Pmax; rows >= num_partial[b] of scene b are
         padding and never read.  Scene b is the reference's p_sample_loop_complete (:447-476) run on that scene alone with
@@ -809,12 +887,13 @@ class GaussianDiffusion:
         rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
         return self._loop("p_sample_loop_complete_ragged", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("ragged", partial_boxes, num_partial), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     @torch.no_grad()
     def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                   sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None,
-                                  collision_scale=None, collision_steps=None, sampling_solver=None):
+                                  collision_scale=None, collision_steps=None,
+                                  wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
         """Strided (DDIM) scene completion of a batch with per-scene numbers of given objects.  Scene b is ddim_sample_loop (reference
         :402-444) run on that scene alone with ONE addition taken from p_sample_loop_complete (:447-476): before every model call at pair
         (t, t_next) the first num_partial[b] rows of the state are overwritten in place with q_sample(partial_boxes[b], t, fresh noise);
@@ -830,7 +909,8 @@ class GaussianDiffusion:
         dsc_ddim_inpaint_step_f32, bit-identical."""
         return self._loop("ddim_complete_ragged_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial),
-                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
+                          **_steer_kw(collision_scale, collision_steps),
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
 
     def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
         """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
@@ -853,7 +933,7 @@ class GaussianDiffusion:
     @torch.no_grad()
     def p_sample_loop_masked(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
                              keep_running=False, known=None, mask=None, graph=None,
-                             collision_scale=None, collision_steps=None):
+                             collision_scale=None, collision_steps=None, wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Element-wise in-painting in T steps.  ``known`` is (B, N, C) f32 in the network's encoding, ``mask`` (B, N, C) or (B, N) bool /
         uint8 (ops.known_mask), non-zero = this element is given.  Scene b is the reference's p_sample_loop_complete (:447-476) on that
         scene alone with its two torch.cat's replaced by a select: before the model call at step t,
@@ -865,12 +945,13 @@ class GaussianDiffusion:
         by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
         return self._loop("p_sample_loop_masked", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("mask", known, mask), clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
                          ddim_sampling_eta=0., known=None, mask=None, graph=None,
-                         collision_scale=None, collision_steps=None, sampling_solver=None):
+                         collision_scale=None, collision_steps=None,
+                         wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
         """Element-wise in-painting in S strided (DDIM) steps; ``known`` / ``mask`` as in p_sample_loop_masked.  Scene b is ddim_sample_loop
         (reference :402-444) on that scene alone: before every model call at pair (t, t_next),
         x = where(mask, q_sample(known, t, fresh noise), x); after the last pair, x = where(mask, known, x).  x_start is always clamped
@@ -880,12 +961,14 @@ class GaussianDiffusion:
         graph path replays one captured step whose update is the fused dsc_ddim_masked_step_f32, bit-identical."""
         return self._loop("ddim_masked_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask),
-                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
+                          **_steer_kw(collision_scale, collision_steps),
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
 
     @torch.no_grad()
     def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                                     clip_denoised=True, keep_running=False, known=None, mask=None, graph=None,
-                                    collision_scale=None, collision_steps=None):
+                                    collision_scale=None, collision_steps=None,
+                                    wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
         """Text-guided element-wise in-painting in T steps: scene b is p_sample_loop_masked with m = u + w[b] * (c - u) in place of the
         model output (c, u and ``guidance_scale`` as in p_sample_loop_guided; ``known`` / ``mask`` as in p_sample_loop_masked).  Both
         halves of the 2 B model call see the same overwritten x_t.  Draws: exactly those of p_sample_loop_masked at batch B, in its
@@ -894,19 +977,21 @@ class GaussianDiffusion:
         dsc_p_sample_masked_cfg_f32, bit-identical."""
         return self._loop("p_sample_loop_masked_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("mask", known, mask), scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     @torch.no_grad()
     def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                                 sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None,
-                                collision_scale=None, collision_steps=None, sampling_solver=None):
+                                collision_scale=None, collision_steps=None,
+                                wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
         """Text-guided element-wise in-painting in S strided (DDIM) steps: scene b is ddim_masked_loop with the guided output m of
         p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
         ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
         step whose update is the fused dsc_ddim_masked_cfg_step_f32, bit-identical."""
         return self._loop("ddim_masked_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale,
-                          **_steer_kw(collision_scale, collision_steps), **_solver_kw(sampling_solver))
+                          **_steer_kw(collision_scale, collision_steps),
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,

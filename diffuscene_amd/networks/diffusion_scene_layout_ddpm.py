@@ -289,7 +289,8 @@ class DiffusionSceneLayout_DDPM(Module):
     def sample(self, room_mask, num_points, point_dim, batch_size=1, text=None, partial_boxes=None,
                input_boxes=None, ret_traj=False, ddim=False, clip_denoised=False, freq=40, batch_seeds=None,
                sampling_timesteps=None, ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None,
-               collision_steps=None, sampling_solver=None):
+               collision_steps=None, sampling_solver=None,
+               wall_scale=None, wall_steps=None, room_side=None):
         """reference :228-310.  ``ddim`` keeps the reference's meaning: accepted and ignored.  ``sampling_timesteps`` is the DDIM
         switch: None runs the T-step DDPM loop; an integer S runs ``gen_samples_ddim`` (S strided steps, ``ddim_sampling_eta``) for
         unconditional, instance- and text-conditioned generation, and with ``ret_traj`` returns its S + 1 states.  The reference
@@ -310,10 +311,18 @@ class DiffusionSceneLayout_DDPM(Module):
         ``sampling_solver`` (None: this method as it was; "dpmpp_2m"): the multistep DPM-Solver++(2M) on the strided loop -- the S
         steps are taken on the extrapolated x0 estimate D = x0 + e_k (x0 - x0_prev) (``_check_solver``), one model
         call per step as before; combines with guidance, steering and seeds.  Needs ``sampling_timesteps`` and
-        ``ddim_sampling_eta == 0``."""
+        ``ddim_sampling_eta == 0``.
+        ``wall_scale`` (None: this method as it was): a float or ``batch_size`` per-scene weights w >= 0 of floor-plan steering -- after
+        every model call whose timestep is below ``wall_steps`` (None: every step) the clamped x0 estimate of scene b moves by
+        -w[b] * dE/d(x, z translations), E the out-of-room energy of the oriented footprints of its non-empty boxes over the distance
+        field of ``room_mask`` ((B, 1, H, W) or (1, 1, H, W), inside > 0.5), rendered in the window [-room_side, room_side]^2 metres
+        (``_check_walls``, GaussianDiffusion._wall_inputs).  Runs after collision steering; the same loops accept and
+        refuse it.  Needs ``room_side`` and the train-stats file."""
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, ret_traj)
+        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
+                                       (batch_size, num_points, point_dim), input_boxes, ret_traj))
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
@@ -377,6 +386,19 @@ class DiffusionSceneLayout_DDPM(Module):
         self.diffusion.diffusion._steer_inputs(tuple(int(v) for v in shape), "cpu", collision_scale, collision_steps, what)
         return dict(collision_scale=collision_scale, collision_steps=collision_steps)
 
+    def _check_walls(self, wall_scale, wall_steps, room_side, room_mask, shape, input_boxes=None, ret_traj=False, what="sample"):
+        """The refusals of ``wall_scale`` / ``wall_steps`` / ``room_side``, before anything is computed or drawn -> the keywords the loop
+        receives (the room mask among them): none at all without floor-plan steering, so that call stays what it was."""
+        if wall_scale is None and wall_steps is None and room_side is None:
+            return {}
+        if input_boxes is not None or self.room_arrange_condition:
+            raise ValueError("wall_scale: re-arrangement diffuses [translation | angle] only, the boxes are not steered there")
+        if ret_traj:
+            raise ValueError("wall_scale: the steered loops return the final scenes only (ret_traj is not supported)")
+        self.diffusion.diffusion._wall_inputs(tuple(int(v) for v in shape), "cpu", wall_scale, wall_steps, room_side, room_mask, what,
+                                              field=False)
+        return dict(wall_scale=wall_scale, wall_steps=wall_steps, room_side=room_side, room_mask=room_mask)
+
     def _check_solver(self, sampling_solver, sampling_timesteps, ddim_sampling_eta, what="sample"):
         """The refusals of ``sampling_solver``, before anything is computed or drawn -- an unknown name, no ``sampling_timesteps``,
         ``ddim_sampling_eta != 0`` -> the keyword the strided loop receives: none at all without a solver, so that call stays what it
@@ -403,11 +425,13 @@ class DiffusionSceneLayout_DDPM(Module):
     def generate_layout(self, room_mask, num_points, point_dim, batch_size=1, text=None, ret_traj=False, ddim=False,
                         clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
                         ddim_sampling_eta=0.0, guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None,
-                        sampling_solver=None):
+                        sampling_solver=None,
+                        wall_scale=None, wall_steps=None, room_side=None):
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, ret_traj=ret_traj, ddim=ddim,
                               clip_denoised=clip_denoised, batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
                               **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
-                              **_steer_kwargs(collision_scale, collision_steps), **_solver_kwargs(sampling_solver))
+                              **_steer_kwargs(collision_scale, collision_steps),
+                              **_wall_kwargs(wall_scale, wall_steps, room_side), **_solver_kwargs(sampling_solver))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
@@ -464,7 +488,8 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                       ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None):
+                       ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None,
+                       wall_scale=None, wall_steps=None, room_side=None):
         """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
         every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
         x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part.  ``collision_scale`` / ``collision_steps``:
@@ -474,23 +499,29 @@ class DiffusionSceneLayout_DDPM(Module):
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
+            steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
+                                           (batch_size, num_points, point_dim), what="complete_scene"))
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
             samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
                               ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds,
-                              **_seed_kwargs(scene_seeds), **_steer_kwargs(collision_scale, collision_steps))
+                              **_seed_kwargs(scene_seeds), **_steer_kwargs(collision_scale, collision_steps),
+                              **_wall_kwargs(wall_scale, wall_steps, room_side))
         return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
 
     @torch.no_grad()
     def arrange_scene(self, room_mask, num_points, point_dim, input_boxes, batch_size=1, ret_traj=False, ddim=False,
                       clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
-                      ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None):
+                      ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None,
+                      wall_scale=None, wall_steps=None, room_side=None):
         """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop.
         ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
         ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
+        self._check_walls(wall_scale, wall_steps, room_side, room_mask,
+                          (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
@@ -557,16 +588,19 @@ class DiffusionSceneLayout_DDPM(Module):
     def generate_layout_batched(self, room_mask, num_points, point_dim, batch_size, text=None, clip_denoised=False,
                                 batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
                                 guidance_scale=None, scene_seeds=None, collision_scale=None, collision_steps=None,
-                                sampling_solver=None):
+                                sampling_solver=None,
+                                wall_scale=None, wall_steps=None, room_side=None):
         """``generate_layout`` for a whole batch: one reverse loop for ``batch_size`` scenes, each post-filtered on its own.
         ``guidance_scale``: a float or one classifier-free guidance scale per scene (see ``sample``).  ``scene_seeds``: one seed per
         scene (``_seeded``): scene b can then be regenerated alone, or the batch split over calls and devices.  ``collision_scale`` /
         ``collision_steps``: collision steering, a weight per scene (see ``sample``).  ``sampling_solver``: "dpmpp_2m" with
-        ``sampling_timesteps`` (see ``sample``)."""
+        ``sampling_timesteps`` (see ``sample``).  ``wall_scale`` / ``wall_steps`` / ``room_side``: floor-plan steering on ``room_mask``,
+        a weight per scene (see ``sample``)."""
         samples = self.sample(room_mask, num_points, point_dim, batch_size, text=text, clip_denoised=clip_denoised,
                               batch_seeds=batch_seeds, **_ddim_kwargs(sampling_timesteps, ddim_sampling_eta),
                               **_guidance_kwargs(guidance_scale), **_seed_kwargs(scene_seeds),
-                              **_steer_kwargs(collision_scale, collision_steps), **_solver_kwargs(sampling_solver))
+                              **_steer_kwargs(collision_scale, collision_steps),
+                              **_wall_kwargs(wall_scale, wall_steps, room_side), **_solver_kwargs(sampling_solver))
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     def _ragged_partial(self, partial_boxes, num_partial, batch_size, num_points, point_dim, device):
@@ -616,7 +650,8 @@ class DiffusionSceneLayout_DDPM(Module):
     def complete_scene_batched(self, room_mask, num_points, point_dim, partial_boxes, num_partial=None, batch_size=None,
                                clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
                                ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None,
-                               sampling_solver=None):
+                               sampling_solver=None,
+                               wall_scale=None, wall_steps=None, room_side=None):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
@@ -633,6 +668,8 @@ class DiffusionSceneLayout_DDPM(Module):
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene_batched")
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
+        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
+                                       (batch_size, num_points, point_dim), what="complete_scene_batched"))
         seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
@@ -653,12 +690,15 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
                               batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0, scene_seeds=None,
-                              collision_scale=None, collision_steps=None, sampling_solver=None):
+                              collision_scale=None, collision_steps=None, sampling_solver=None,
+                              wall_scale=None, wall_steps=None, room_side=None):
         """``arrange_scene`` for a whole batch: one ``arrange_samples`` loop for the B scenes of ``input_boxes`` (B, num_points, C),
         each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead.
         ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
         ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         self._check_steer(collision_scale, collision_steps, (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
+        self._check_walls(wall_scale, wall_steps, room_side, room_mask,
+                          (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene_batched")
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
             raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
@@ -738,7 +778,8 @@ class DiffusionSceneLayout_DDPM(Module):
     @torch.no_grad()
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
-                              scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None, sampling_solver=None):
+                              scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None, sampling_solver=None,
+                              wall_scale=None, wall_steps=None, room_side=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -766,6 +807,7 @@ class DiffusionSceneLayout_DDPM(Module):
         B, N, C = int(batch_size), int(num_points), int(point_dim)
         scale = None if guidance_scale is None else ops.guidance_scales(guidance_scale, B, "cpu")   # checked on the host; the loop uploads it
         steer = self._check_steer(collision_scale, collision_steps, (B, N, C), what="inpaint_scene_batched")
+        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, (B, N, C), what="inpaint_scene_batched"))
         seeded = self._seeded(scene_seeds, batch_seeds, B, device)
         if isinstance(boxes, (list, tuple)):
             if len(boxes) != B:
@@ -845,6 +887,13 @@ def _steer_kwargs(collision_scale, collision_steps):
     if collision_scale is None and collision_steps is None:
         return {}
     return dict(collision_scale=collision_scale, collision_steps=collision_steps)
+
+
+def _wall_kwargs(wall_scale, wall_steps, room_side):
+    """The floor-plan keywords ``sample`` receives: none at all without them, so that call stays what it was."""
+    if wall_scale is None and wall_steps is None and room_side is None:
+        return {}
+    return dict(wall_scale=wall_scale, wall_steps=wall_steps, room_side=room_side)
 
 
 def _solver_kwargs(sampling_solver):

@@ -1006,6 +1006,123 @@ def box_repulsion(x0, bounds, bbox_dim=8, class_dim=1):
     return energy, grad
 
 
+# ---------------------------------------------------------------------------------- floor-plan steering
+
+WALL_MAX_SIDE = 256                # pixels per side of the room mask (csrc/diffusion.hip: WALL_MAXHW)
+
+
+def _renamed(fn, old, new, *args, **kw):
+    """``fn(*args, **kw)`` of collision steering with the names of another steering part in its messages."""
+    try:
+        return fn(*args, **kw)
+    except ValueError as e:
+        raise ValueError(str(e).replace(old, new)) from None
+
+
+def wall_scales(scale, b, device):
+    """The per-scene weights of dsc_steer_walls_f32: collision_scales under the name ``wall_scale``."""
+    return _renamed(collision_scales, "collision_scale", "wall_scale", scale, b, device)
+
+
+def wall_steps(steps, num_timesteps):
+    """K of dsc_steer_walls_f32: collision_steps under the name ``wall_steps``."""
+    return _renamed(collision_steps, "collision_steps", "wall_steps", steps, num_timesteps)
+
+
+def room_side_value(room_side):
+    """``room_side`` -- half the side of the square window the room mask was rendered in, metres -- as a float; ValueError unless it is
+    one finite number > 0."""
+    if isinstance(room_side, bool) or not isinstance(room_side, numbers.Real) or not 0 < float(room_side) < float("inf"):
+        raise ValueError("room_side must be a finite number > 0 (half the side of the mask's window, in metres), got %r" % (room_side,))
+    return float(room_side)
+
+
+def room_mask_dims(room_mask, b):
+    """(leading dimension 1 or b, H, W) of a room mask for b scenes, checked on the host: a (b, 1, H, W) or (1, 1, H, W) tensor, float
+    or uint8 / bool, 2 <= H, W <= 256.  ValueError otherwise."""
+    if not isinstance(room_mask, torch.Tensor) or room_mask.dim() != 4 or room_mask.shape[1] != 1:
+        raise ValueError("room_mask must be a (B, 1, H, W) or (1, 1, H, W) tensor, got %s"
+                         % (tuple(room_mask.shape) if isinstance(room_mask, torch.Tensor) else type(room_mask).__name__,))
+    fb, _, h, w = (int(v) for v in room_mask.shape)
+    if fb not in (1, int(b)):
+        raise ValueError("room_mask holds %d masks for %d scenes (one for each, or one for all)" % (fb, b))
+    if not (2 <= h <= WALL_MAX_SIDE and 2 <= w <= WALL_MAX_SIDE):
+        raise ValueError("room_mask must have 2 <= H, W <= %d, got %d x %d" % (WALL_MAX_SIDE, h, w))
+    if not (room_mask.is_floating_point() or room_mask.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("room_mask must be float or uint8, got %s" % room_mask.dtype)
+    return fb, h, w
+
+
+def floor_field_rec(mask, field, room_side):
+    """The launch record of dsc_floor_field_f32: ``mask`` (b, H, W) f32 -> ``field`` (b, H, W) f32."""
+    _c(mask, "mask"); _c(field, "field")
+    if mask.dim() != 3 or tuple(field.shape) != tuple(mask.shape):
+        raise RuntimeError("diffuscene_amd: mask and field must be (b, H, W), got %s / %s" % (tuple(mask.shape), tuple(field.shape)))
+    b, h, w = mask.shape
+    return "dsc_floor_field_f32", (mask.data_ptr(), field.data_ptr(), b, h, w, room_side_value(room_side)), (mask, field)
+
+
+def floor_field(room_mask, room_side, out=None):
+    """The distance field of floor-plan steering: ``room_mask`` (b, 1, H, W), float or uint8 on the device, inside
+    iff > 0.5 -> (b, H, W) f32, half the squared distance in metres^2 from each pixel centre to the nearest inside one.  Once per call."""
+    fb, h, w = room_mask_dims(room_mask, room_mask.shape[0] if isinstance(room_mask, torch.Tensor) and room_mask.dim() else 1)
+    if not room_mask.is_cuda:
+        raise RuntimeError("diffuscene_amd: room_mask must live on a HIP device (no CPU fallback exists)")
+    mask = room_mask.reshape(fb, h, w).to(torch.float32).contiguous()
+    field = torch.empty((fb, h, w), device=mask.device, dtype=torch.float32) if out is None else out
+    issue(floor_field_rec(mask, field, room_side))
+    return field
+
+
+def walls_rec(x_t, model_out, mean_type, tables, walls, energy_out=None, grad_out=None, outside_out=None, **operands):
+    """The launch record of floor-plan steering (dsc_steer_walls_f32), marshalled once like steer_rec and with its operand groups
+    (``operands``: the time source ``t`` or ``strided``, the given part, ``scale``).  ``walls`` = (weight (B,) f32, t_below (1,) int64,
+    bounds (steer_bounds), bbox_dim, class_dim, field (B or 1, H, W) f32, room_side (1,) f32) -- weight, t_below, field and room_side on
+    the device, read at launch.  ``outside_out`` (B,) int32: the third optional output."""
+    weight, t_below, bounds, bbox_dim, class_dim, field, room_side = walls
+    _, a, keep = _renamed(steer_rec, "collision steering", "floor-plan steering", x_t, model_out, mean_type, tables,
+                          (weight, t_below, bounds, bbox_dim, class_dim), energy_out=energy_out, grad_out=grad_out, **operands)
+    b = a[18]
+    _c(field, "field"); _c(room_side, "room_side")
+    if field.dim() != 3 or field.shape[0] not in (1, b) or not all(2 <= int(v) <= WALL_MAX_SIDE for v in field.shape[1:]):
+        raise RuntimeError("diffuscene_amd: field must be (%d or 1, H, W) with 2 <= H, W <= %d, got %s" % (b, WALL_MAX_SIDE, tuple(field.shape)))
+    if room_side.numel() != 1:
+        raise RuntimeError("diffuscene_amd: room_side must hold one f32")
+    if outside_out is not None and (tuple(_dev(outside_out, "outside_out", torch.int32).shape) != (b,) or not outside_out.is_contiguous()):
+        raise RuntimeError("diffuscene_amd: outside_out must be a contiguous (%d,) int32 tensor" % b)
+    fb, h, w = field.shape
+    args = a[:15] + (field.data_ptr(), room_side.data_ptr()) + a[15:17] + (_opt(outside_out),) + a[17:] + (fb, h, w)
+    return "dsc_steer_walls_f32", args, (keep, field, room_side, outside_out)
+
+
+def steer_walls(x_t, model_out, weight, t_below, bounds, field, room_side, mean_type, ca=None, cb=None, bbox_dim=8, class_dim=1,
+                energy_out=None, grad_out=None, outside_out=None, **operands):
+    """Floor-plan steering of ``model_out`` in place, eagerly; ``operands``: the time source and the optional groups of walls_rec.
+    Returns ``model_out``."""
+    issue(walls_rec(x_t, model_out, mean_type, (ca, cb), (weight, t_below, bounds, bbox_dim, class_dim, field, room_side),
+                    energy_out=energy_out, grad_out=grad_out, outside_out=outside_out, **operands))
+    return model_out
+
+
+def floor_violation(x0, room_mask, room_side, bounds, bbox_dim=8, class_dim=1):
+    """The out-of-room energy of floor-plan steering, standalone: ``x0`` (B, N, C) scenes in the network's encoding (clamped to [-1, 1]
+    first), ``room_mask`` (B or 1, 1, H, W) -> (energy (B,), grad (B, N, 3) = d energy / d x0[:, :, 0:3], its y column 0, outside (B,)
+    int32 = the number of non-empty boxes with a footprint point outside the room).  The steering entry point with mean type x0,
+    weight 0 and the optional outputs: nothing is written to ``x0``."""
+    _c(x0, "x0")
+    b, n = x0.shape[0], x0.shape[1]
+    dev = x0.device
+    room_mask_dims(room_mask, b)
+    field = floor_field(room_mask.to(dev), room_side)
+    energy = torch.empty((b,), device=dev, dtype=torch.float32)
+    grad = torch.empty((b, n, 3), device=dev, dtype=torch.float32)
+    outside = torch.empty((b,), device=dev, dtype=torch.int32)
+    steer_walls(None, x0, torch.zeros((b,), device=dev), torch.zeros((1,), device=dev, dtype=torch.int64), bounds, field,
+                torch.full((1,), room_side_value(room_side), device=dev), MEAN_X0, bbox_dim=bbox_dim, class_dim=class_dim,
+                energy_out=energy, grad_out=grad, outside_out=outside, t=torch.zeros((b,), device=dev, dtype=torch.int64))
+    return energy, grad, outside
+
+
 # ---------------------------------------------------------------------------------- multistep solver
 
 SOLVERS = ("dpmpp_2m",)            # sampling_solver= of the strided loops

@@ -30,7 +30,9 @@ A loop is three orthogonal parts, the axes of the one step kernel (csrc/diffusio
   multistep       _Multistep (optional, ``multistep=``, strided rows only): the x0 history and the (S,) history weights of
                   DPM-Solver++(2M) in buffers of the graph, ONE launch (dsc_multistep_x0_f32) after the steering in the replayed
                   non-final graph -- the last pair has weight 0 and needs none; the step kernel is the unchanged one.
-_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] [multistep unless final,] main draw, given draw unless
+  walls           _Walls (optional, ``walls=``): floor-plan steering -- the weights, K, the distance field of the room mask and the room
+                  side in buffers of the graph, ONE launch (dsc_steer_walls_f32) after _Steer and before _Multistep.
+_Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] [walls,] [multistep unless final,] main draw, given draw unless
 final, [cfg_combine,] ONE update launch laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
 The ten classes are rows:                    schedule   given            guided   fused=False unfuses
   _StepGraph                                 T steps    - / _Dense       -        (sub-batch chains: _chains_for, this row only)
@@ -524,6 +526,33 @@ class _Steer:
         ops.issue(ops.steer_rec(g.x, mo, g.mean_type, steer=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
 
 
+class _Walls:
+    """Floor-plan steering (dsc_steer_walls_f32): one launch after collision steering (if any) and before the multistep launch, on
+    the same output with the same operands as _Steer -- walls have the last word.  ``weight`` (B,) f32, ``t_below`` (1,) int64, ``field``
+    (B, H, W) f32 and ``room_side`` (1,) f32 are buffers of the graph, captured by pointer and refreshed in place: one graph serves
+    every mask, room side, per-scene weight and number of steered steps.  The field comes from ops.floor_field, once per call; a shared
+    (1, H, W) field is broadcast into the buffer.  ``layout`` = (bounds, bbox_dim, class_dim, H, W) is baked into the launch and part
+    of the cache key."""
+
+    def __init__(self, g, layout):
+        bounds, bbox_dim, class_dim, h, w = layout
+        self.weight = torch.zeros((g.shape[0],), device=g.device, dtype=torch.float32)
+        self.t_below = torch.zeros((1,), device=g.device, dtype=torch.int64)
+        self.field = torch.zeros((g.shape[0], h, w), device=g.device, dtype=torch.float32)
+        self.room_side = torch.ones((1,), device=g.device, dtype=torch.float32)
+        self.spec = (self.weight, self.t_below, ops.steer_bounds(bounds), bbox_dim, class_dim, self.field, self.room_side)
+
+    def load(self, weight, t_below, field, room_side):
+        self.weight.copy_(weight)               # in place: the graph holds these pointers
+        self.t_below.fill_(int(t_below))
+        self.field.copy_(field)                 # (B, H, W), or (1, H, W) broadcast
+        self.room_side.fill_(float(room_side))
+
+    def apply(self, g, mo):
+        scale = dict(scale=g.guide.scale) if g.guide else {}
+        ops.issue(ops.walls_rec(g.x, mo, g.mean_type, walls=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
+
+
 class _Multistep:
     """DPM-Solver++(2M) (dsc_multistep_x0_f32): one launch after the model call and the steering that moves the model output -- under
     guidance the 2 B output, with the scales -- so that the unchanged strided step runs on the extrapolated x0 estimate, and keeps the
@@ -550,7 +579,7 @@ class _Loop:
     given, guided, chains, what, multistep = _Given, False, False, None, None
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None,
-                 steer=None, multistep=False):
+                 steer=None, multistep=False, walls=None):
         nch = (_chains_for(shape[0]),) if self.chains else ()
         super().__init__(diff, model, shape, device, condition, condition_cross, sched, replay, 2 if self.guided else 1, *nch)
         self.fused = fused
@@ -560,6 +589,7 @@ class _Loop:
         self.part = part(self, partial_shape, fused) if part is _Ragged else part(self, partial_shape)
         self.guide = _Guidance(self, fused) if self.guided else None
         self.steer = _Steer(self, steer) if steer is not None else None
+        self.walls = _Walls(self, walls) if walls is not None else None
         if multistep and not self.strided:
             raise ValueError("a multistep solver rides on the strided loops")
         self.multistep = _Multistep(self) if multistep else None
@@ -597,13 +627,15 @@ class _Loop:
         return self.model_out
 
     def _step(self, final):
-        """[the unfused overwrite,] model call, [collision steering,] [the multistep launch unless final,] main draw, the given draw of
-        the NEXT step unless final,
+        """[the unfused overwrite,] model call, [collision steering,] [floor-plan steering,] [the multistep launch unless final,] main
+        draw, the given draw of the NEXT step unless final,
         [cfg_combine,] one update launch, [the copy into the null half,] decrement or advance unless final."""
         self.part.before(self)
         mo = self._model_call()
         if self.steer:
             self.steer.apply(self, mo)
+        if self.walls:
+            self.walls.apply(self, mo)
         if self.multistep and not final:
             self.multistep.apply(self, mo)
         noise = self._main_draw(final)
@@ -615,7 +647,7 @@ class _Loop:
         if not final:
             self._move()
 
-    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None, multistep=None):
+    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None, multistep=None, walls=None):
         """``sched``: total_steps of a T-step loop, the device tables (GaussianDiffusion.ddim_tables) of a strided one.  ``values``: the
         (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword).  ``multistep``: the
         (S,) history weights of a loop with a multistep part."""
@@ -629,6 +661,8 @@ class _Loop:
         self.part.load(self, *values)
         if self.steer:
             self.steer.load(*steer)             # (weight (B,), K): steered while t < K
+        if self.walls:
+            self.walls.load(*walls)             # (weight (B,), K, field, room_side)
         self._upload((self.noise, noise_buffer, 1), *([(self.part.noise, given_noise, 1 if self.part.fused else 0)] if self.part.noise else []))
         self.part.first(self)
         if self.part.fused and self.x_null is not None:         # guided: both halves of the state stay current
@@ -749,11 +783,14 @@ def _front_end(name, cls):
     bounds and the two dims --, never the weights or K.
     ``multistep`` (keyword, strided rows; None: the loop and its graph as they are without it) = the (S,) f32 history weights of
     GaussianDiffusion.multistep_table on the device: DPM-Solver++(2M) (_Multistep) after the steering of every pair but the last; the key
-    gains the flag, never the weights."""
+    gains the flag, never the weights.
+    ``walls`` (keyword; None: the loop and its graph as they are without it) = (weight (B,) f32 on the device, K, bounds, bbox_dim,
+    class_dim, field (B or 1, H, W) f32 on the device, room_side) of GaussianDiffusion._wall_inputs: floor-plan steering (_Walls) after
+    the collision steering; the key gains the layout and (H, W) -- never the weights, K, the mask or room_side."""
     names = (("scale",) if cls.guided else ()) + (("sampling_timesteps", "eta") if cls.strided else ("clip_denoised", "total_steps")) \
         + ("noise_fn",) + cls.given.values + (("fused",) if cls.guided or cls.given is _Ragged else ())
 
-    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, multistep=None, **kw):
+    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, multistep=None, walls=None, **kw):
         if multistep is not None and not cls.strided:
             raise ValueError("%s: a multistep solver rides on the strided loops" % name)
         if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
@@ -769,17 +806,20 @@ def _front_end(name, cls):
             sched, n_main, n_given = bool(a["clip_denoised"]), a["total_steps"] + 1, a["total_steps"]
         # steer = (weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim): the first two live in buffers, the rest is the key
         layout = None if steer is None else (tuple(float(v) for v in steer[2]), int(steer[3]), int(steer[4]))
+        # walls = (weight, K, bounds, bbox_dim, class_dim, field (B or 1, H, W) f32 on the device, room_side): the key is the layout and (H, W)
+        wall_layout = None if walls is None else (tuple(float(v) for v in walls[2]), int(walls[3]), int(walls[4])) + tuple(walls[5].shape[1:])
         check = cls.what and _replay_check(cls.what % sched if "%" in cls.what else cls.what, n_main,
                                            shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
         out = _cached_loop(
             name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"],
             (cls.__name__, sched, bool(a["fused"]), gshape) + (() if steer is None else (layout,))
-            + (() if multistep is None else ("multistep",)),
+            + (() if multistep is None else ("multistep",)) + (() if walls is None else (("walls",) + wall_layout,)),
             lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape,
-                                           layout, multistep is not None),
+                                           layout, multistep is not None, *(() if walls is None else (wall_layout,))),
             lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else n_given, *([a["scale"]] if cls.guided else []), *given,
                                                   noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given),
-                                                  steer=None if steer is None else steer[:2], multistep=multistep),
+                                                  steer=None if steer is None else steer[:2], multistep=multistep,
+                                                  **({} if walls is None else dict(walls=walls[:2] + walls[5:]))),
             mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
         if cls.given is _Dense and given:
             out[:, :gshape[1], :] = given[0]            # clean objects restored after the last step (:471-473)

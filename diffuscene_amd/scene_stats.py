@@ -233,6 +233,23 @@ def scene_stats_from_dicts(dicts, model_ids=None, return_pairs=False, device=Non
     return st
 
 
+def out_of_room(boxes, room_mask, room_side, bounds, bbox_dim=8, class_dim=1):
+    """How far the boxes of B scenes reach outside their rooms -- what ``wall_scale`` acts on, measured by the same
+    launch (ops.floor_violation).  ``boxes``: (B, N, C) scenes in the network's encoding, as the loops return them; ``room_mask``: (B, 1,
+    H, W) or (1, 1, H, W), inside > 0.5, rendered in the window [-room_side, room_side]^2; ``bounds``: the 12 de-normalisation bounds
+    (GaussianDiffusion.box_bounds).  -> (energy (B,) f32: the summed out-of-room energy of the kept -- non-empty -- boxes, metres^2;
+    share (B,) f32: the share of kept boxes with at least one of their nine footprint points outside the room, 0 for a scene that keeps
+    no box)."""
+    dev = _device_of(boxes, room_mask)
+    x = _as_f32(boxes, "boxes", dev)
+    if x.dim() != 3:
+        raise ValueError("boxes: (B, N, C) scenes expected, got shape %s" % (tuple(x.shape),))
+    mask = room_mask if torch.is_tensor(room_mask) else torch.from_numpy(np.ascontiguousarray(room_mask))
+    energy, _, outside = ops.floor_violation(x, mask.to(dev), room_side, bounds, bbox_dim=bbox_dim, class_dim=class_dim)
+    kept = (x[..., bbox_dim + class_dim - 1] < 0).sum(dim=1)
+    return energy, outside.to(torch.float32) / kept.clamp(min=1).to(torch.float32)
+
+
 def summarize(stats):
     """The running quantities of the reference's iou_states.txt after the last scene (its AverageAggregator means, the std of the
     object counts and the two totals).  ``stats``: a SceneStats or the list ``to_reference()`` returns."""

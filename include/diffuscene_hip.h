@@ -508,6 +508,36 @@ int dsc_multistep_x0_f32(const float* x_t, float* model_out, float* hist, const 
                          const uint8_t* mask, int32_t mean_type, int32_t b, int64_t inner, int32_t pmax, int32_t c, int32_t num_steps,
                          int32_t num_timesteps, dsc_stream_t stream);
 
+/* Floor-plan steering, the field: once per call.  mask (b, h, w) f32, pixel (i, j) inside iff > 0.5; the image
+ * covers x in [-room_side, room_side] along its columns and z likewise along its rows, dx = 2 room_side / w, dz = 2 room_side / h.
+ *   field[i, j] = 1/2 min over inside pixels (i', j') of ((i - i') dz)^2 + ((j - j') dx)^2   (metres^2; 0 at inside pixels),
+ * the float32 nearest to the float64 expression (an exact two-pass minimum); a mask without an inside pixel gives field == 0.
+ * 2 <= h, w <= 256 and b <= 65535 (else DSC_ERANGE); room_side must be finite and > 0 (else DSC_EINVAL). */
+int dsc_floor_field_f32(const float* mask, float* field, int32_t b, int32_t h, int32_t w, float room_side, dsc_stream_t stream);
+
+/* Floor-plan steering, the launch inside the loop: after dsc_steer_boxes_f32 (if any), before dsc_multistep_x0_f32 and the guidance
+ * mix, correcting model_out IN PLACE so that the step's x0 estimate moves its boxes into the room (INTEGRATION.md 9 states the
+ * definition).  x0, validity, the operand groups (time source, given part, cfg_scale), bounds (HOST), weight / t_below (DEVICE) and the
+ * store rule are those of dsc_steer_boxes_f32; the store goes to channels 0 and 2 only.  Scene i of b:
+ *   points : the nine points centre_xz + R (a sx, b sz), a, b in {-1, 0, 1}, of every valid box: the oriented footprint, R the rotation
+ *            about y by the (cos, sin) channels over their hypot (x' = c lx - s lz, z' = s lx + c lz; both zero: angle 0).
+ *   e(p)   : u = (x + s) / dx - 1/2, v = (z + s) / dz - 1/2, s = room_side[0]; uc = clamp(u, 0, w - 1), j0 = min(floor(uc), w - 2),
+ *            fu = uc - j0, likewise vc, i0, fv with h;  e = bilinear(field; i0, j0, fv, fu) + 1/2 ((u - uc) dx)^2 + 1/2 ((v - vc) dz)^2.
+ *   energy : E = sum over valid boxes of (1/9) sum of e over the nine points;  g = dE / d x0[:, {0, 2}] (it includes span / 2).
+ * field is (field_b, h, w) f32 from dsc_floor_field_f32 with field_b == b or 1 (shared by all scenes); room_side (1,) f32 is a DEVICE
+ * buffer read through its pointer, like weight and t_below: one captured graph serves every mask and every room side.  Optional
+ * outputs, written whether or not the step is active: energy_out (b,), grad_out (b, n, 3) (the y column is 0), outside_out (b,) int32 =
+ * the number of valid boxes with a point of e > 0.  An inactive launch without optional outputs reads no scene.  One 256-thread block
+ * per scene, n <= 160; float64 after the float32 x0 and field, fixed summation order, scene i's result does not depend on b.  n > 160,
+ * bbox_dim != 8, h or w outside [2, 256]: DSC_ERANGE; the DSC_EINVAL cases of dsc_steer_boxes_f32, and field_b not in {1, b}. */
+int dsc_steer_walls_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                        const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                        const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
+                        const float* bounds, const float* field, const float* room_side, float* energy_out, float* grad_out,
+                        int32_t* outside_out, int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c, int32_t bbox_dim,
+                        int32_t class_dim, int32_t num_steps, int32_t num_timesteps, int32_t field_b, int32_t h, int32_t w,
+                        dsc_stream_t stream);
+
 /* Per-scene gate of the text-condition dropout (text_drop_prob): y[i, :] = keep[i] ? x[i, :] : 0 for b scenes of `inner` elements;
  * keep holds one byte per scene.  A select: the elements of a dropped scene are not read (NaN there does not propagate).  Used forward
  * on the text features and backward on their incoming gradient.  y may alias x. */
