@@ -246,6 +246,15 @@ SIGNATURES = {
     "dsc_steer_walls_f32": (C.c_int, [c_f32p, c_f32p] + [c_i64p] * 3 + [c_f32p] * 3 + [c_i64p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_i64p,
                                       C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p] + [C.c_int32] * 12 + [C.c_void_p]),
     "dsc_scene_gate_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int32, C.c_int64, C.c_void_p]),
+    "dsc_conv_patches_f32": (C.c_int, [c_f32p, c_f32p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "dsc_conv_patches_bwd_f32": (C.c_int, [c_f32p, c_f32p] + [C.c_int32] * 7 + [C.c_void_p]),
+    "dsc_maxpool2d_f32": (C.c_int, [c_f32p, c_f32p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "dsc_maxpool2d_bwd_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "dsc_frozen_bn_act_f32": (C.c_int, [c_f32p] * 7 + [C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "dsc_frozen_bn_workspace_floats": (C.c_int64, [C.c_int64, C.c_int32]),
+    "dsc_frozen_bn_act_bwd_f32": (C.c_int, [c_f32p] * 10 + [C.c_int64, C.c_int32, C.c_int32, c_f32p, C.c_int64, C.c_void_p]),
+    "dsc_avgpool_rows_f32": (C.c_int, [c_f32p, c_f32p] + [C.c_int32] * 3 + [C.c_void_p]),
+    "dsc_avgpool_rows_bwd_f32": (C.c_int, [c_f32p, c_f32p] + [C.c_int32] * 3 + [C.c_void_p]),
 }
 
 _lib = None

@@ -57,8 +57,9 @@ def _with_param_ema(optimizer, parameters, ema_decay, ema_warmup):
 
 
 def build_network(input_dims, n_classes, config, weight_file=None, device="cpu"):
-    """reference :37-68.  The floor-plan feature extractor is only built when the config uses it
-    (``room_mask_condition``; no shipped config does) because it needs torchvision."""
+    """reference :37-68.  The floor-plan feature extractor is built when the config uses it (``room_mask_condition``, default true as
+    in the reference; every shipped config says false): the package's own ResNet18 on HIP kernels (feature_extractors.py), no
+    torchvision.  ``feature_extractor.name: alexnet`` and ``freeze_bn: false`` raise NotImplementedError."""
     network_type = config["network"]["type"]
     if network_type != "diffusion_scene_layout_ddpm":
         raise NotImplementedError()

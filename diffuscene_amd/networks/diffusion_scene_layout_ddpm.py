@@ -9,7 +9,9 @@ What changed underneath:
 * ``train_on_batch`` reads all logged scalars with ONE device->host copy instead of 11 ``.item()`` syncs
   (:461-473), and all-reduces gradients over RCCL when torch.distributed is initialised (data parallel);
 * post-filtering of empty boxes (:351-406) is vectorised; it still looks only at batch row 0, as the reference.
-Optional third-party encoders (BERT / CLIP / floor-plan ResNet) are imported only when the config asks for them.
+Optional third-party encoders (BERT / CLIP) are imported only when the config asks for them; the floor-plan encoder of a
+``room_mask_condition`` model is the package's own (feature_extractors.py): ``room_mask`` is then (B, c, H, W) or (1, c, H, W) -- one
+room for all B layouts, encoded once per call, outside every captured loop -- and the same mask serves ``wall_scale``.
 """
 import torch
 import torch.nn as nn
@@ -157,6 +159,8 @@ class DiffusionSceneLayout_DDPM(Module):
 
     def _base_condition(self, room_mask, batch_size, num_points, device):
         room_layout_f = self.fc_room_f(self.feature_extractor(room_mask)) if self.room_mask_condition else None
+        if room_layout_f is not None and room_layout_f.shape[0] == 1 and batch_size > 1:
+            room_layout_f = room_layout_f.expand(batch_size, -1)       # one room, B layouts: encoded once
         inst = self._instance_condition(batch_size, device)
         if room_layout_f is not None and inst is not None:
             return torch.cat([room_layout_f[:, None, :].repeat(1, num_points, 1), inst], dim=-1).contiguous()
@@ -191,11 +195,27 @@ class DiffusionSceneLayout_DDPM(Module):
         tr, sz, bb = self.translation_dim, self.size_dim, self.bbox_dim
         return torch.cat([boxes[:, :, tr:tr + sz], boxes[:, :, bb:]], dim=-1).contiguous()
 
-    def _sampling_conditions(self, room_mask, num_points, device, text=None, padded_partial=None, input_boxes=None):
+    def _check_room(self, room_mask, batch_size, what="sample"):
+        """The refusal of a floor-plan-conditioned model's ``room_mask``, before anything is computed or drawn: (batch_size, c, H, W), or
+        (1, c, H, W) -- one room for all ``batch_size`` layouts, encoded once and expanded.  Other models take the mask as they did."""
+        if not self.room_mask_condition:
+            return
+        if not isinstance(room_mask, torch.Tensor) or room_mask.dim() != 4:
+            raise ValueError("%s: room_mask must be a (B, c, H, W) tensor on a room_mask_condition model, got %s"
+                             % (what, tuple(room_mask.shape) if isinstance(room_mask, torch.Tensor) else type(room_mask).__name__))
+        if room_mask.shape[0] not in (1, int(batch_size)):
+            raise ValueError("%s: room_mask holds %d rooms for a batch of %d (give one room per scene, or one room for all)"
+                             % (what, room_mask.shape[0], batch_size))
+
+    def _sampling_conditions(self, room_mask, num_points, device, text=None, padded_partial=None, input_boxes=None, batch_size=None):
         """(condition, condition_cross) of a sampling call, reference :233-262: the base condition, then the embedding of the given
         objects padded with zeros to ``num_points`` (room_partial_condition) and of the kept channels of ``input_boxes``
-        (room_arrange_condition), and the text features.  One copy for ``sample`` and the batched / strided entry points."""
-        condition = self._base_condition(room_mask, room_mask.size(0), num_points, device)
+        (room_arrange_condition), and the text features.  One copy for ``sample`` and the batched / strided entry points.  The floor-plan
+        features of a room_mask_condition model are computed here, once per call and outside every captured loop; ``batch_size`` is the
+        number of scenes they are expanded to when the mask holds one room."""
+        if not self.room_mask_condition or batch_size is None:
+            batch_size = room_mask.size(0)
+        condition = self._base_condition(room_mask, batch_size, num_points, device)
         if self.room_partial_condition:
             condition = torch.cat([condition, self.fc_partial_condition(padded_partial)], dim=-1).contiguous()
         if self.room_arrange_condition:
@@ -318,6 +338,7 @@ class DiffusionSceneLayout_DDPM(Module):
         field of ``room_mask`` ((B, 1, H, W) or (1, 1, H, W), inside > 0.5), rendered in the window [-room_side, room_side]^2 metres
         (``_check_walls``, GaussianDiffusion._wall_inputs).  Runs after collision steering; the same loops accept and
         refuse it.  Needs ``room_side`` and the train-stats file."""
+        self._check_room(room_mask, batch_size)
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, ret_traj)
@@ -336,7 +357,7 @@ class DiffusionSceneLayout_DDPM(Module):
                                 device=device)
             padded = torch.cat([partial_boxes, zeros], dim=1).contiguous()
         condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, text=text, padded_partial=padded,
-                                                               input_boxes=input_boxes)
+                                                               input_boxes=input_boxes, batch_size=batch_size)
         if self.text_condition and not (self.text_glove_embedding or self.text_clip_embedding):
             print('after bert:', condition_cross.shape)
         if input_boxes is not None:
@@ -463,7 +484,7 @@ class DiffusionSceneLayout_DDPM(Module):
         torch.randn((batch_size, num_points, point_dim))           # CPU draw kept, as in sample (:232)
         if self.room_arrange_condition:
             raise ValueError("scene completion: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
-        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded, batch_size=batch_size)
         print('scene completion sampling')
         return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                            condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
@@ -478,7 +499,7 @@ class DiffusionSceneLayout_DDPM(Module):
         torch.randn((batch_size, num_points, point_dim))           # CPU draw kept, as in sample (:232)
         if self.room_partial_condition:
             raise ValueError("re-arrangement: a room_partial_condition model completes scenes (complete_scene_batched)")
-        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, input_boxes=input_boxes)
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, input_boxes=input_boxes, batch_size=batch_size)
         print('scene arrangement sampling')
         return self.diffusion.arrange_samples_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                    condition_cross=condition_cross, input_boxes=input_boxes,
@@ -496,6 +517,7 @@ class DiffusionSceneLayout_DDPM(Module):
         collision steering (see ``sample``); the given objects repel the free ones and are never moved.  ``sampling_solver``:
         "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene")
+        self._check_room(room_mask, batch_size, "complete_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
@@ -523,6 +545,7 @@ class DiffusionSceneLayout_DDPM(Module):
         self._check_walls(wall_scale, wall_steps, room_side, room_mask,
                           (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene")
+        self._check_room(room_mask, batch_size, "arrange_scene")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
@@ -667,6 +690,7 @@ class DiffusionSceneLayout_DDPM(Module):
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene_batched")
+        self._check_room(room_mask, batch_size, "complete_scene_batched")
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
         steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
                                        (batch_size, num_points, point_dim), what="complete_scene_batched"))
@@ -680,7 +704,7 @@ class DiffusionSceneLayout_DDPM(Module):
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
         if self.room_arrange_condition:
             raise ValueError("complete_scene_batched: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
-        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded)
+        condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded, batch_size=batch_size)
         print('scene completion sampling')
         samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                                          clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded,
@@ -708,6 +732,7 @@ class DiffusionSceneLayout_DDPM(Module):
             raise ValueError("input_boxes holds %d scenes for a batch of %d" % (input_boxes.shape[0], batch_size))
         if input_boxes.shape[1] != num_points or input_boxes.shape[2] != point_dim:
             raise ValueError("input_boxes: every scene must be (%d, %d), got %s" % (num_points, point_dim, tuple(input_boxes.shape[1:])))
+        self._check_room(room_mask, batch_size, "arrange_scene_batched")
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
@@ -805,6 +830,7 @@ class DiffusionSceneLayout_DDPM(Module):
         if batch_size is None:
             batch_size = len(boxes) if isinstance(boxes, (list, tuple)) else int(boxes.shape[0])
         B, N, C = int(batch_size), int(num_points), int(point_dim)
+        self._check_room(room_mask, B, "inpaint_scene_batched")
         scale = None if guidance_scale is None else ops.guidance_scales(guidance_scale, B, "cpu")   # checked on the host; the loop uploads it
         steer = self._check_steer(collision_scale, collision_steps, (B, N, C), what="inpaint_scene_batched")
         steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, (B, N, C), what="inpaint_scene_batched"))
@@ -834,14 +860,14 @@ class DiffusionSceneLayout_DDPM(Module):
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
         if scale is not None:                                      # the last refusal of the keyword, still before any draw
-            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
+            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text, batch_size=B)
             if condition_cross is None or condition_cross.dim() != 3:
                 raise ValueError("guidance_scale: the text encoder must give (B, L, text_embed_dim) features, got %s (the null "
                                  "condition is defined on the cross-attention features)"
                                  % (None if condition_cross is None else tuple(condition_cross.shape),))
         torch.randn((B, N, C))                                     # CPU draw kept, as in sample (:232)
         if scale is None:
-            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text)
+            condition, condition_cross = self._sampling_conditions(room_mask, N, device, text=text, batch_size=B)
         print('scene in-painting sampling')
         if scale is not None:
             guided = dict(condition=condition, condition_cross=condition_cross, guidance_scale=scale, known=known, mask=mask, **seeded,

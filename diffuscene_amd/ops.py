@@ -1451,3 +1451,165 @@ def ddpm_loss(target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, bounds, 
     issue(ddpm_loss_rec(target, out, x_t, t, loss_weight, ca, cb, alphas_cumprod, bounds, dims, separate, iou, mean_type, grad_scale,
                         losses, parts, dout))
     return losses, parts, dout
+
+
+# ---------------------------------------------------------------------------------- floor-plan encoder (csrc/floorplan.hip)
+
+def conv_out_size(n, k, stride, pad):
+    return (n + 2 * pad - k) // stride + 1
+
+
+def conv_kpad(c, k):
+    """Columns of a patch row: k * k * c rounded up to the K granule of the GEMMs (32)."""
+    return (k * k * c + 31) // 32 * 32
+
+
+def _image(x, geom, name):
+    """x [b * h * w][c] contiguous on the device for geom = (b, h, w) -> c."""
+    _c(x, name)
+    b, h, w = geom
+    if x.dim() != 2 or x.shape[0] != b * h * w:
+        raise RuntimeError("diffuscene_amd: %s must be [%d * %d * %d][c], got %s" % (name, b, h, w, tuple(x.shape)))
+    return x.shape[1]
+
+
+def conv_patches(x, geom, k, stride, pad, out=None):
+    """Patch rows of a k x k convolution over x [b * h * w][c] (dsc_conv_patches_f32) -> [b * ho * wo][conv_kpad(c, k)]."""
+    c = _image(x, geom, "x")
+    b, h, w = geom
+    rows = b * conv_out_size(h, k, stride, pad) * conv_out_size(w, k, stride, pad)
+    if out is None:
+        out = torch.empty((max(rows, 0), conv_kpad(c, k)), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, conv_kpad(c, k)):
+        raise RuntimeError("conv_patches: out must be %s, got %s" % ((rows, conv_kpad(c, k)), tuple(out.shape)))
+    _lib.check(_lib.fn("dsc_conv_patches_f32")(x.data_ptr(), _c(out, "out").data_ptr(), b, h, w, c, k, stride, pad, stream_ptr()),
+               "dsc_conv_patches_f32")
+    return out
+
+
+def conv_patches_bwd(dpatches, geom, c, k, stride, pad, out=None):
+    """Gradient of conv_patches: dpatches [b * ho * wo][kpad] -> dx [b * h * w][c] (dsc_conv_patches_bwd_f32)."""
+    b, h, w = geom
+    rows = b * conv_out_size(h, k, stride, pad) * conv_out_size(w, k, stride, pad)
+    if tuple(_c(dpatches, "dpatches").shape) != (rows, conv_kpad(c, k)):
+        raise RuntimeError("conv_patches_bwd: dpatches must be %s, got %s" % ((rows, conv_kpad(c, k)), tuple(dpatches.shape)))
+    if out is None:
+        out = torch.empty((b * h * w, c), device=dpatches.device, dtype=torch.float32)
+    elif tuple(out.shape) != (b * h * w, c):
+        raise RuntimeError("conv_patches_bwd: out must be %s, got %s" % ((b * h * w, c), tuple(out.shape)))
+    _lib.check(_lib.fn("dsc_conv_patches_bwd_f32")(dpatches.data_ptr(), _c(out, "out").data_ptr(), b, h, w, c, k, stride, pad,
+                                                   stream_ptr()), "dsc_conv_patches_bwd_f32")
+    return out
+
+
+def maxpool2d(x, geom, out=None, arg=None):
+    """nn.MaxPool2d(3, 2, 1) over x [b * h * w][c] (dsc_maxpool2d_f32) -> (y [b * ho * wo][c], arg uint8 window slots)."""
+    c = _image(x, geom, "x")
+    b, h, w = geom
+    rows = b * conv_out_size(h, 3, 2, 1) * conv_out_size(w, 3, 2, 1)
+    if out is None:
+        out = torch.empty((rows, c), device=x.device, dtype=torch.float32)
+    if arg is None:
+        arg = torch.empty((rows, c), device=x.device, dtype=torch.uint8)
+    if tuple(out.shape) != (rows, c) or tuple(arg.shape) != (rows, c) or not arg.is_contiguous() or arg.dtype != torch.uint8:
+        raise RuntimeError("maxpool2d: out / arg must be contiguous %s float32 / uint8" % ((rows, c),))
+    _lib.check(_lib.fn("dsc_maxpool2d_f32")(x.data_ptr(), _c(out, "out").data_ptr(), arg.data_ptr(), b, h, w, c, stream_ptr()),
+               "dsc_maxpool2d_f32")
+    return out, arg
+
+
+def maxpool2d_bwd(dy, arg, geom, out=None):
+    """dy, arg [b * ho * wo][c] -> dx [b * h * w][c] (dsc_maxpool2d_bwd_f32)."""
+    b, h, w = geom
+    rows = b * conv_out_size(h, 3, 2, 1) * conv_out_size(w, 3, 2, 1)
+    c = _c(dy, "dy").shape[1]
+    if dy.shape[0] != rows or tuple(arg.shape) != (rows, c) or not arg.is_cuda or arg.dtype != torch.uint8 or not arg.is_contiguous():
+        raise RuntimeError("maxpool2d_bwd: dy / arg must be contiguous %s float32 / uint8" % ((rows, c),))
+    if out is None:
+        out = torch.empty((b * h * w, c), device=dy.device, dtype=torch.float32)
+    elif tuple(out.shape) != (b * h * w, c):
+        raise RuntimeError("maxpool2d_bwd: out must be %s, got %s" % ((b * h * w, c), tuple(out.shape)))
+    _lib.check(_lib.fn("dsc_maxpool2d_bwd_f32")(dy.data_ptr(), arg.data_ptr(), _c(out, "out").data_ptr(), b, h, w, c, stream_ptr()),
+               "dsc_maxpool2d_bwd_f32")
+    return out
+
+
+def _bn_vectors(ch, *named):
+    for t, name in named:
+        if tuple(_c(t, name).shape) != (ch,):
+            raise RuntimeError("diffuscene_amd: %s must be (%d,), got %s" % (name, ch, tuple(t.shape)))
+
+
+def frozen_bn_act(x, weight, bias, running_mean, running_var, residual=None, relu=False, out=None):
+    """y = act(x * s + t (+ residual)) over x [rows][ch], s = weight / sqrt(running_var), t = bias - running_mean * s
+    (dsc_frozen_bn_act_f32); weight None (then all four): y = act(x (+ residual))."""
+    rows, ch = _c(x, "x").shape
+    if weight is not None:
+        _bn_vectors(ch, (weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var"))
+    if residual is not None and tuple(_c(residual, "residual").shape) != (rows, ch):
+        raise RuntimeError("frozen_bn_act: residual must be %s" % ((rows, ch),))
+    if out is None:
+        out = torch.empty_like(x)
+    elif tuple(out.shape) != (rows, ch):
+        raise RuntimeError("frozen_bn_act: out must be %s" % ((rows, ch),))
+    _lib.check(_lib.fn("dsc_frozen_bn_act_f32")(x.data_ptr(), _opt(weight), _opt(bias), _opt(running_mean), _opt(running_var),
+                                                _opt(residual), _c(out, "out").data_ptr(), rows, ch, 1 if relu else 0, stream_ptr()),
+               "dsc_frozen_bn_act_f32")
+    return out
+
+
+def frozen_bn_act_bwd(dy, y, x, weight, running_mean, running_var, relu=False, want_residual=False, outs=None):
+    """-> (dx, dresidual or None, dweight or None, dbias or None) of frozen_bn_act (dsc_frozen_bn_act_bwd_f32); ``y`` is the forward's
+    output (read only with ``relu``), ``x`` its input (read only with a ``weight``).  ``outs``: that tuple preallocated."""
+    rows, ch = _c(dy, "dy").shape
+    for t, name in ((y, "y"), (x, "x")):
+        if t is not None and tuple(_c(t, name).shape) != (rows, ch):
+            raise RuntimeError("frozen_bn_act_bwd: %s must be %s" % (name, (rows, ch)))
+    dx, dres, dw, db = outs if outs is not None else (None, None, None, None)
+    dx = torch.empty_like(dy) if dx is None else dx
+    dres = torch.empty_like(dy) if want_residual and dres is None else dres
+    ws = None
+    if weight is not None:
+        _bn_vectors(ch, (weight, "weight"), (running_mean, "running_mean"), (running_var, "running_var"))
+        dw = torch.empty((ch,), device=dy.device, dtype=torch.float32) if dw is None else dw
+        db = torch.empty((ch,), device=dy.device, dtype=torch.float32) if db is None else db
+        _bn_vectors(ch, (dw, "dweight"), (db, "dbias"))
+    for t, name in ((dx, "dx"), (dres, "dresidual")):
+        if t is not None and tuple(_c(t, name).shape) != (rows, ch):
+            raise RuntimeError("frozen_bn_act_bwd: %s must be %s" % (name, (rows, ch)))
+    if weight is not None:
+        wsf = _lib.fn("dsc_frozen_bn_workspace_floats")(rows, ch)
+        if wsf < 0:
+            _lib.check(int(wsf), "dsc_frozen_bn_workspace_floats")
+        ws = scratch(dy.device, wsf)
+    _lib.check(_lib.fn("dsc_frozen_bn_act_bwd_f32")(dy.data_ptr(), _opt(y), _opt(x if weight is not None else None), _opt(weight),
+                                                    _opt(running_mean), _opt(running_var), dx.data_ptr(), _opt(dres), _opt(dw), _opt(db),
+                                                    rows, ch, 1 if relu else 0, _opt(ws), ws.numel() if ws is not None else 0,
+                                                    stream_ptr()), "dsc_frozen_bn_act_bwd_f32")
+    return dx, dres, dw, db
+
+
+def avgpool_rows(x, b, out=None):
+    """x [b * hw][ch] -> the mean over hw, [b][ch] (dsc_avgpool_rows_f32)."""
+    rows, ch = _c(x, "x").shape
+    if b < 1 or rows % b:
+        raise RuntimeError("avgpool_rows: %d rows are not %d images" % (rows, b))
+    if out is None:
+        out = torch.empty((b, ch), device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (b, ch):
+        raise RuntimeError("avgpool_rows: out must be %s" % ((b, ch),))
+    _lib.check(_lib.fn("dsc_avgpool_rows_f32")(x.data_ptr(), _c(out, "out").data_ptr(), b, rows // b, ch, stream_ptr()),
+               "dsc_avgpool_rows_f32")
+    return out
+
+
+def avgpool_rows_bwd(dy, hw, out=None):
+    """dy [b][ch] -> dx [b * hw][ch] = dy / hw (dsc_avgpool_rows_bwd_f32)."""
+    b, ch = _c(dy, "dy").shape
+    if out is None:
+        out = torch.empty((b * hw, ch), device=dy.device, dtype=torch.float32)
+    elif tuple(out.shape) != (b * hw, ch):
+        raise RuntimeError("avgpool_rows_bwd: out must be %s" % ((b * hw, ch),))
+    _lib.check(_lib.fn("dsc_avgpool_rows_bwd_f32")(dy.data_ptr(), _c(out, "out").data_ptr(), b, hw, ch, stream_ptr()),
+               "dsc_avgpool_rows_bwd_f32")
+    return out

@@ -98,7 +98,8 @@ def plan_supported(model):
     net = model.diffusion.model
     p = next(model.parameters())
     if not p.is_cuda or model.room_mask_condition:
-        return False                    # the room-mask feature extractor is out of scope (networks/feature_extractors.py)
+        return False                    # the floor-plan encoder (networks/feature_extractors.py) runs under autograd, in front of the
+                                        # denoiser: these models train on the autograd path; admitting them to the plan is not built
     # room_partial_condition (reference :193-199; no shipped YAML sets it): fc_partial_condition(target * mask) is one more torch module
     # in front of the plan, like fc_arrange_condition -- its rows enter as per-token context and its gradient leaves through d_ctx
     if d.loss_type != 'mse' or d.translation_dim != 3 or model.sample_num_points > 160:

@@ -851,6 +851,49 @@ int dsc_point_affine_bwd_f32(const float* dy, const float* x, int64_t ldx, int32
                              int32_t clouds, int32_t n, int32_t ch, int32_t d, float* dx, int64_t lddx, float* dwp, int64_t lddw,
                              float* dt, float* workspace, int64_t workspace_floats, dsc_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Floor-plan encoder (scene_synthesis/networks/feature_extractors.py: ResNet18 on the room mask; frozen_batchnorm.py), the pieces
+ * around its convolutions' GEMMs (csrc/floorplan.hip).  Images are channel-last, token-major: x [b * h * w][c], row = (b * h + y) * w + x;
+ * a (B, 1, H, W) mask is already in that layout.  Every kernel is a gather with a fixed summation order (no atomics): results are
+ * deterministic for a shape.  Element offsets are int64; b * h * w and the output row count must fit int32 (else DSC_ERANGE), h, w, c <= 4096.
+ * Channel counts that are a multiple of 4 with 16-byte aligned bases move 16 bytes per lane, anything else 4 bytes per lane, same results.
+ * ------------------------------------------------------------------------------------------- */
+/* Patch gather of a k x k convolution (k in {1, 3, 7}, stride in {1, 2}, 0 <= pad < k, zero padding; anything else DSC_EINVAL):
+ *   patches[(b * ho + oy) * wo + ox][(ky * k + kx) * c + ch] = x[b][oy * stride - pad + ky][ox * stride - pad + kx][ch]   (0 outside)
+ * ho = (h + 2 pad - k) / stride + 1, wo likewise; patches is dense [b * ho * wo][kpad], kpad = k * k * c rounded up to a multiple of 32
+ * (the K granule of dsc_gemm_f32), columns [k * k * c, kpad) are written as zero.  The convolution is then dsc_gemm_f32 with the weight
+ * as [out][(ky, kx, ch)] padded to kpad.  The backward sums, for every input element, the at most k * k patch entries that read it, taps
+ * in (ky, kx) row-major order. */
+int dsc_conv_patches_f32(const float* x, float* patches, int32_t b, int32_t h, int32_t w, int32_t c, int32_t k, int32_t stride,
+                         int32_t pad, dsc_stream_t stream);
+int dsc_conv_patches_bwd_f32(const float* dpatches, float* dx, int32_t b, int32_t h, int32_t w, int32_t c, int32_t k, int32_t stride,
+                             int32_t pad, dsc_stream_t stream);
+/* nn.MaxPool2d(3, stride 2, padding 1): y [b * ho * wo][c], ho = (h - 1) / 2 + 1.  The padding never wins; among equal maxima the first
+ * in row-major window order wins and NaN propagates (torch.nn.functional.max_pool2d); arg holds the winner's window slot ky * 3 + kx.
+ * The backward is a gather: every input element sums dy of the at most four windows whose winner it is (oy, ox ascending). */
+int dsc_maxpool2d_f32(const float* x, float* y, uint8_t* arg, int32_t b, int32_t h, int32_t w, int32_t c, dsc_stream_t stream);
+int dsc_maxpool2d_bwd_f32(const float* dy, const uint8_t* arg, float* dx, int32_t b, int32_t h, int32_t w, int32_t c,
+                          dsc_stream_t stream);
+/* FrozenBatchNorm2d.forward (frozen_batchnorm.py:56-68) with the residual add and ReLU of a BasicBlock behind it:
+ *   y = act(x * s[c] + t[c] (+ residual)),  s = weight / sqrt(running_var),  t = bias - running_mean * s,  act = ReLU when relu != 0.
+ * The reference's constructor already added eps to running_var; no second eps is added here.  weight == NULL (then bias, running_mean
+ * and running_var too): y = act(x (+ residual)), the plain ReLU of the head.  ch a power of two in [4, 1024] (else DSC_ERANGE), dense
+ * [rows][ch], 16-byte aligned (else DSC_EALIGN).
+ * Backward: g = dy * [y > 0] (relu; y is the forward's output) or dy; dx = g * s; dresidual (optional) = g; dweight[c] = sum over rows
+ * of g * ((x - running_mean[c]) / sqrt(running_var[c])), dbias[c] = sum of g: column sums in a fixed order through `workspace`
+ * (>= dsc_frozen_bn_workspace_floats(rows, ch) floats, 8-byte aligned: it holds float64 partial sums).  weight == NULL: x, dweight, dbias
+ * NULL as well, no workspace.  Forward and backward evaluate their expressions in float64 and round to float32 once, as do the sums of
+ * dsc_conv_patches_bwd_f32 and dsc_avgpool_rows_f32. */
+int dsc_frozen_bn_act_f32(const float* x, const float* weight, const float* bias, const float* running_mean, const float* running_var,
+                          const float* residual, float* y, int64_t rows, int32_t ch, int32_t relu, dsc_stream_t stream);
+int64_t dsc_frozen_bn_workspace_floats(int64_t rows, int32_t ch);
+int dsc_frozen_bn_act_bwd_f32(const float* dy, const float* y, const float* x, const float* weight, const float* running_mean,
+                              const float* running_var, float* dx, float* dresidual, float* dweight, float* dbias, int64_t rows,
+                              int32_t ch, int32_t relu, float* workspace, int64_t workspace_floats, dsc_stream_t stream);
+/* nn.AdaptiveAvgPool2d((1, 1)): x [b][hw][ch] -> y [b][ch] = (sum over hw, ascending) / hw; backward dx[b][p][ch] = dy[b][ch] / hw. */
+int dsc_avgpool_rows_f32(const float* x, float* y, int32_t b, int32_t hw, int32_t ch, dsc_stream_t stream);
+int dsc_avgpool_rows_bwd_f32(const float* dy, float* dx, int32_t b, int32_t hw, int32_t ch, dsc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
