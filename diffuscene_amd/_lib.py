@@ -242,6 +242,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_float), c_f32p, c_f32p] + [C.c_int32] * 9 + [C.c_void_p]),
     "dsc_multistep_x0_f32": (C.c_int, [c_f32p] * 4 + [c_i64p] * 2 + [c_f32p] * 3 + [c_i64p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64] +
                              [C.c_int32] * 4 + [C.c_void_p]),
+    "dsc_resample_jump_f32": (C.c_int, [c_f32p] * 4 + [c_i64p] * 3 + [c_f32p] * 2 + [C.c_void_p, c_i64p] + [c_f32p] * 3 +
+                              [C.c_int32, C.c_int32, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p]),
+    "dsc_ddim_seek_i64": (C.c_int, [c_i64p, c_i64p, c_i64p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p]),
     "dsc_floor_field_f32": (C.c_int, [c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "dsc_steer_walls_f32": (C.c_int, [c_f32p, c_f32p] + [c_i64p] * 3 + [c_f32p] * 3 + [c_i64p, c_f32p, C.c_void_p, c_f32p, c_f32p, c_i64p,
                                       C.POINTER(C.c_float), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p] + [C.c_int32] * 12 + [C.c_void_p]),

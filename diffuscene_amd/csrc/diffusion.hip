@@ -688,6 +688,70 @@ __global__ __launch_bounds__(256) void overwrite_kernel(float* __restrict__ x, c
     }
 }
 
+// The resampling jump of the completion and in-painting loops (RePaint): after the step that leaves the state at
+// remaining index s, the whole state is diffused forward by j steps in one draw, x = ja[pos] * x + jb[pos] * noise, and the loop walks
+// the stretch down again.  ja / jb are host tables (float64, rounded once) of sqrt(abar[time(s + j)] / abar[time(s)]) and its
+// complement, indexed by the position the move of the step has left: the scene's own t[b] = s (T-step), or the step counter
+// k = step[0] (strided; the target pair is k - j).  In place.
+//   GIVEN none:  every element takes the jump -- dsc_q_sample_f32 on (ja, jb) at t = s.  The eager loops and the unfused graphs.
+//         rows / mask:  a given element takes what the overwrite in front of the next model call would write,
+//                q_sample(given, time(s + j), noise_g): the jump and that overwrite in one launch, bit-identical to their composition.
+// Read sets as in step_kernel: a given element reads mask (nothing, for rows), given and noise_g only, a free one mask, x and noise
+// only.  x_dup (may be NULL) receives a second copy of every written element (the null half of a guided loop's state).
+// Bad indices: t[b], t[b] + j and counts[b] once per scene; step[0], step[0] - j and times[.] once per launch; the target is looked up
+// only where a given part exists.
+// Width: a scene's base is b * inner floats and inner is N * C -- 12 * 62, 21 * 65, 21 * 62: mostly off the 16-byte grid, as in
+// scene_noise_kernel's per_scene % 4 != 0 case -- so every lane moves one dword and a wave covers 256 contiguous bytes per operand; the
+// launch moves four floats per element and is latency at the loops' sizes, a dwordx4 form for the aligned shapes would buy nothing.
+template <bool STRIDED, int GIVEN>
+__global__ __launch_bounds__(256) void jump_kernel(float* x, const float* __restrict__ noise, const float* __restrict__ ja,
+                                                  const float* __restrict__ jb, const int64_t* __restrict__ t,
+                                                  const int64_t* __restrict__ step, const int64_t* __restrict__ times,
+                                                  const float* __restrict__ given, const float* __restrict__ noise_g,
+                                                  const uint8_t* __restrict__ mask, const int64_t* __restrict__ counts,
+                                                  const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ x_dup,
+                                                  int jump, int64_t inner, int pmax, int c, int S, int T) {
+    constexpr bool HAS_GIVEN = GIVEN != GIVEN_NONE;
+    const int b = blockIdx.y;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    int64_t pos, target = 0;
+    if constexpr (STRIDED) {
+        pos = dsc_checked_index(step[0], S, first && b == 0);
+        if constexpr (HAS_GIVEN) target = dsc_checked_index(times[dsc_checked_index(pos - jump, S, first && b == 0)], T, first && b == 0);
+    } else {
+        pos = dsc_checked_index(t[b], T, first);
+        if constexpr (HAS_GIVEN) target = dsc_checked_index(pos + jump, T, first);
+    }
+    const float a = ja[pos], s = jb[pos];
+    Renoise r{};
+    if constexpr (HAS_GIVEN) r = renoise_coef(true, target, sa, sb);
+    int64_t cnt = 0;
+    if constexpr (GIVEN == GIVEN_ROWS) cnt = dsc_checked_index(counts[b], (int64_t)pmax + 1, first) * c;
+    const int64_t base = (int64_t)b * inner;
+    const int64_t gbase = GIVEN == GIVEN_ROWS ? (int64_t)b * pmax * c : base;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < inner; i += (int64_t)gridDim.x * blockDim.x) {
+        bool is_given = false;
+        if constexpr (GIVEN == GIVEN_ROWS) is_given = i < cnt;
+        if constexpr (GIVEN == GIVEN_MASK) is_given = mask[base + i] != 0;
+        float y;
+        if (is_given) y = renoise(given[gbase + i], noise_g[gbase + i], r.a, r.s);
+        else y = renoise(x[base + i], noise[base + i], a, s);
+        x[base + i] = y;
+        if (x_dup) x_dup[base + i] = y;
+    }
+}
+
+// The move after a jump in a strided loop, the seek form of ddim_advance_kernel: step += delta, then t[i] = times[step].  One block:
+// every thread reads the counter before thread 0 stores it.
+__global__ __launch_bounds__(256) void ddim_seek_kernel(int64_t* step, const int64_t* __restrict__ times, int64_t* __restrict__ t,
+                                                       int count, int S, int64_t delta) {
+    const int64_t k = dsc_checked_index(step[0] + delta, S, threadIdx.x == 0);
+    __syncthreads();
+    if (threadIdx.x == 0) step[0] = k;
+    const int64_t tv = times[k];
+    for (int i = threadIdx.x; i < count; i += blockDim.x) t[i] = tv;
+}
+
 // Per-scene gate of the text-condition dropout (text_drop_prob): y[b, :] = keep[b] ? x[b, :] : 0 -- a select, a dropped scene's x is
 // not read.  Forward on the text features, backward on their incoming gradient.  y may alias x.
 __global__ __launch_bounds__(256) void scene_gate_kernel(const float* x, const uint8_t* __restrict__ keep, float* y, int64_t inner) {
@@ -1198,6 +1262,43 @@ extern "C" int dsc_multistep_x0_f32(const float* x_t, float* model_out, float* h
         if (cfg_scale) DSC_MULTISTEP_LAUNCH(GIVEN_NONE, true); else DSC_MULTISTEP_LAUNCH(GIVEN_NONE, false);
     }
 #undef DSC_MULTISTEP_LAUNCH
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_resample_jump_f32(float* x, const float* noise, const float* ja, const float* jb, const int64_t* t,
+                                     const int64_t* step, const int64_t* times, const float* given, const float* noise_g,
+                                     const uint8_t* mask, const int64_t* counts, const float* sqrt_ac, const float* sqrt_1mac,
+                                     float* x_dup, int32_t jump, int32_t b, int64_t inner, int32_t pmax, int32_t c, int32_t num_steps,
+                                     int32_t num_timesteps, dsc_stream_t stream) {
+    if (!x || !noise || !ja || !jb || jump < 1 || b < 1 || inner < 1 || num_timesteps < 1) return DSC_EINVAL;
+    if (t ? step || times : !step || !times || num_steps < 1) return DSC_EINVAL;            // one time source
+    if (counts && mask) return DSC_EINVAL;                                                   // one given part
+    if (given ? !noise_g || !sqrt_ac || !sqrt_1mac || (!counts && !mask) : noise_g || counts || mask) return DSC_EINVAL;
+    if (counts && (c < 1 || pmax < 1 || inner % c != 0 || (int64_t)pmax * c > inner)) return DSC_EINVAL;
+    if (b > 65535) return DSC_ERANGE;                                                        // blockIdx.y carries the scene
+    const dim3 grid(grid_x(inner), b), block(256);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    DSC_CLEAR_STALE_ERROR();
+#define DSC_JUMP_LAUNCH(STRIDED, GIVEN)                                                                                            \
+    hipLaunchKernelGGL((jump_kernel<STRIDED, GIVEN>), grid, block, 0, s, x, noise, ja, jb, t, step, times, given, noise_g, mask, counts, \
+                       sqrt_ac, sqrt_1mac, x_dup, jump, inner, pmax, c, num_steps, num_timesteps)
+    if (t) {
+        if (counts) DSC_JUMP_LAUNCH(false, GIVEN_ROWS); else if (mask) DSC_JUMP_LAUNCH(false, GIVEN_MASK); else DSC_JUMP_LAUNCH(false, GIVEN_NONE);
+    } else {
+        if (counts) DSC_JUMP_LAUNCH(true, GIVEN_ROWS); else if (mask) DSC_JUMP_LAUNCH(true, GIVEN_MASK); else DSC_JUMP_LAUNCH(true, GIVEN_NONE);
+    }
+#undef DSC_JUMP_LAUNCH
+    DSC_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsc_ddim_seek_i64(int64_t* step, const int64_t* times, int64_t* t, int32_t count, int32_t num_steps, int64_t delta,
+                                 dsc_stream_t stream) {
+    if (!step || !times || !t || count < 1 || num_steps < 1) return DSC_EINVAL;
+    DSC_CLEAR_STALE_ERROR();
+    hipLaunchKernelGGL(ddim_seek_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), step, times, t, count, num_steps,
+                       delta);
     DSC_LAUNCH_CHECK();
     return 0;
 }

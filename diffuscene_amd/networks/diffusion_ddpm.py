@@ -267,6 +267,18 @@ def _check_solver(solver, strided, what):
     return solver
 
 
+def _resample_kw(resample, resample_steps):
+    """The resampling keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
+    return {} if resample is None and resample_steps is None else dict(resample=(resample, resample_steps))
+
+
+def _jump_draw(noise_fn, shape, device):
+    """The draw of a resampling jump: one more draw of the MAIN stream right after the step's.  A noise_fn that tells its streams apart by
+    counting calls (RaggedNoiseReplay, SceneNoise) has ``main_draw`` for it; any other is simply called."""
+    draw = getattr(noise_fn, "main_draw", noise_fn)
+    return draw(size=shape, dtype=torch.float, device=device).contiguous()
+
+
 def _arm(noise_fn, given):
     """A SceneNoise starts a new loop here: its draw numbers go back to 0 and it learns whether the loop draws for a given part."""
     if isinstance(noise_fn, SceneNoise):
@@ -528,20 +540,33 @@ class GaussianDiffusion:
         print('last:', 0, self.num_timesteps, len(self.betas))          # the reference's print at t == 0 (:469, :497)
 
     # the two eager loops (module docstring); a state that a given part overwrites in place stays the same tensor until the update
-    def _t_states(self, model, shape, device, noise_fn, clip_denoised, total_steps, given=_FREE, draw=None):
-        """The T-step loop, reference :355-371: fill t_, [overwrite the given part], model call, one draw, ops.p_sample -- at t == 0 too."""
+    def _t_states(self, model, shape, device, noise_fn, clip_denoised, total_steps, given=_FREE, draw=None, jumps=None):
+        """The T-step loop, reference :355-371: fill t_, [overwrite the given part], model call, one draw, ops.p_sample -- at t == 0 too.
+        ``jumps`` = (schedule, (ja, jb), j) of _resample_inputs: the loop walks the schedule's op list instead -- a call is the step
+        below, a jump one more main draw and dsc_resample_jump_f32 on the whole state at t = s."""
         _arm(noise_fn, given)
         x = noise_fn(size=shape, dtype=torch.float, device=device)
         if given.inplace:
             x = x.clone()                       # a caller's tensor (a row of a NoiseReplay buffer) is not written
         yield x
+        if jumps is not None:
+            sched, (ja, jb), j = jumps
+            for op, u in sched.ops:
+                t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(u)
+                if op == "jump":
+                    ops.resample_jump(x, _jump_draw(noise_fn, shape, device), ja, jb, j, t=t_)
+                    continue
+                given.before(x, t_)
+                x = self._posterior_step(x, model(x, t_), t_, noise_fn, clip_denoised, draw=draw)
+                yield given.finish(x) if u == 0 else x
+            return
         for t in reversed(range(0, total_steps)):
             t_ = torch.empty(shape[0], dtype=torch.int64, device=device).fill_(t)
             given.before(x, t_)
             x = self._posterior_step(x, model(x, t_), t_, noise_fn, clip_denoised, draw=draw)
             yield given.finish(x) if t == 0 else x      # not a copy: ``given.before`` of the next step writes into it (keep a clone)
 
-    def _strided_states(self, model, shape, device, noise_fn, S, eta, given=_FREE, multistep=None):
+    def _strided_states(self, model, shape, device, noise_fn, S, eta, given=_FREE, multistep=None, jumps=None):
         """The strided (DDIM) loop, reference :402-444: a device step counter, [overwrite the given part], model call, a draw except on
         the last pair ((t, -1) takes x_start), ddim_step, ddim_advance.  ``multistep`` = (the (B,) guidance scales or None,): the
         DPM-Solver++(2M) launch (dsc_multistep_x0_f32) on the (steered) model output of every pair but the last, before ddim_step; the
@@ -564,6 +589,22 @@ class GaussianDiffusion:
         if given.inplace:
             x = x.clone()
         yield x
+        if jumps is not None:                   # walk the op list: the pair of call u is k = S - 1 - u, where the counter stands
+            sched, (ja, jb), j = jumps
+            for op, u in sched.ops:
+                if op == "jump":                # the counter stands on the pair at s: jump, then seek back j pairs
+                    ops.resample_jump(x, _jump_draw(noise_fn, shape, device), ja, jb, j, strided=(step, dtab[1]))
+                    ops.ddim_seek(step, dtab[1], t_, -j)
+                    continue
+                given.before(x, t_)
+                last = u == 0
+                model_output = model(x, t_)
+                noise = x if last else noise_fn(size=shape, dtype=torch.float, device=device)
+                x = self.ddim_step(x.contiguous(), model_output.contiguous(), noise.contiguous(), step, dtab)
+                if not last:
+                    ops.ddim_advance(step, dtab[1], t_)
+                yield given.finish(x) if last else x
+            return
         for time, time_next in pairs:
             given.before(x, t_)
             last = time_next < 0
@@ -583,7 +624,8 @@ class GaussianDiffusion:
                           **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
 
     def _loop(self, what, denoise_fn, shape, device, condition, condition_cross, noise_fn, graph, strided=None, given=None, scale=None,
-              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None, multistep=None, walls=None):
+              clip_denoised=True, keep_running=False, say_last=False, all_states=False, steer=None, multistep=None, walls=None,
+              resample=None):
         """What every public loop does behind its signature.  The spec: ``strided`` = (sampling_timesteps, ddim_sampling_eta) or None for
         T steps; ``given`` = None, ("dense", partial_boxes), ("ragged", partial_boxes, num_partial) or ("mask", known, mask); ``scale`` =
         the guidance scale or None.  Validates (ValueError names ``what``), keeps (eta, S) on the instance as the reference does (:404-405),
@@ -593,12 +635,15 @@ class GaussianDiffusion:
         or None: collision steering after every model call (_steer_inputs), on either path.  ``multistep`` = the name of a multistep
         solver (ops.SOLVERS) or None: the strided loop takes its steps on the solver's extrapolated x0 (_check_solver).
         ``walls`` = (wall_scale, wall_steps, room_side, room_mask) or None: floor-plan steering after the collision steering
-        (_wall_inputs), on either path."""
+        (_wall_inputs), on either path.  ``resample`` = ((jump_length, n_resample), resample_steps) or None: RePaint's resampling jumps
+        (_check_resample, _resample_inputs) on a loop with a given part, on either path."""
         assert isinstance(shape, (tuple, list))
         if strided is not None:
             S, eta = _check_ddim(self.num_timesteps, *strided)
         if multistep is not None:
             _check_solver(multistep, strided, what)
+        if resample is not None:
+            resample = self._check_resample(what, *resample, given=given, multistep=multistep, all_states=all_states)
         kind, values = (None, ()) if given is None else (given[0], given[1:])
         if kind == "dense":
             values = (values[0].contiguous(),)
@@ -617,6 +662,9 @@ class GaussianDiffusion:
             sched = (S, eta)
         else:
             sched = (clip_denoised, self._total_steps(keep_running))
+        # (schedule, (ja, jb) on the device, j), or None where the schedule holds no jump: then the loop is the one without the keyword
+        jumps = None if resample is None else self._resample_inputs(device, *resample, *((S, eta) if strided is not None else (sched[1],)))
+        jump_kw = {} if jumps is None else dict(jumps=jumps)
         if not all_states and _use_graph(graph, noise_fn, denoise_fn):
             from .. import sampler
             if say_last:
@@ -625,7 +673,7 @@ class GaussianDiffusion:
             return front(self, denoise_fn, tuple(shape), device, condition, condition_cross, *(() if scale is None else (scale,)), *sched,
                          noise_fn, *values, **({} if steer is None else dict(steer=steer)),
                          **({} if multistep is None else dict(multistep=self.multistep_table(S, device))),
-                         **({} if walls is None else dict(walls=walls)))
+                         **({} if walls is None else dict(walls=walls)), **jump_kw)
         part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
             self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
         if steer is None:
@@ -639,12 +687,12 @@ class GaussianDiffusion:
             model = _walled(model, self, device, walls, part, scale)
         if strided is not None:
             states = self._strided_states(model, shape, device, noise_fn, S, eta, part,
-                                          *(() if multistep is None else ((scale,),)))
+                                          *(() if multistep is None else ((scale,),)), **jump_kw)
         elif scale is not None and kind is None:        # p_sample_loop_guided: the device check before the first draw, its own draw keywords
             self.tables(device)
             states = self._t_states(model, shape, device, noise_fn, *sched, part, draw=dict(size=shape, dtype=torch.float, device=device))
         else:
-            states = self._t_states(model, shape, device, noise_fn, *sched, part)
+            states = self._t_states(model, shape, device, noise_fn, *sched, part, **jump_kw)
         if all_states:
             imgs = list(states)
             assert imgs[-1].shape == tuple(shape)
@@ -653,6 +701,53 @@ class GaussianDiffusion:
         if say_last:
             self._say_last()
         return img
+
+    # ------------------------------------------------------------------ resampling jumps (RePaint)
+    def _check_resample(self, what, resample, resample_steps, given=None, multistep=None, all_states=False):
+        """The refusals of ``resample`` / ``resample_steps``, before anything is drawn or computed -> (j, r, K)."""
+        if resample is None:
+            raise ValueError("%s: resample_steps goes with resample=(jump_length, n_resample)" % what)
+        j, r = ops.resample_pair(resample, what)
+        k = ops.resample_steps_value(resample_steps, self.num_timesteps, what)
+        if given is None:
+            raise ValueError("%s: resample needs a given part (completion, in-painting): nothing is given here" % what)
+        if multistep is not None:
+            raise ValueError("%s: resample does not combine with sampling_solver=%r: the x0 history is void after a jump" % (what, multistep))
+        if all_states:
+            raise ValueError("%s: resample returns the final scenes only (no trajectory)" % what)
+        if self.room_partial_condition or self.room_arrange_condition:
+            raise ValueError("%s: resample on a room_partial_condition / room_arrange_condition model: its condition tensors already "
+                             "encode a prefix / a sub-shape of the scene" % what)
+        return j, r, k
+
+    def resample_schedule(self, jump_length, n_resample, resample_steps=None, total_steps=None, sampling_timesteps=None):
+        """The op list and the counts of a resampled loop (ops.resample_schedule): of the T-step loop of ``total_steps`` (default T)
+        steps, or of the strided loop of ``sampling_timesteps`` pairs on ddim_schedule's times."""
+        if sampling_timesteps is None:
+            return ops.resample_schedule(self.num_timesteps if total_steps is None else total_steps, jump_length, n_resample,
+                                         resample_steps=resample_steps)
+        pairs, _ = self.ddim_schedule(sampling_timesteps, 0.0)
+        return ops.resample_schedule(len(pairs), jump_length, n_resample, [p[0] for p in pairs], resample_steps)
+
+    def jump_table(self, jump_length, device, sampling_timesteps=None):
+        """(ja, jb) of ops.jump_tables from the float64 alphas_cumprod, on ``device``: T rows indexed by s, or -- strided -- S rows indexed
+        by the step counter on ddim_schedule's times; once per (j, S, device)."""
+        device = torch.device(device)
+        key = ("jump", int(jump_length), sampling_timesteps, device)
+        hit = self._ddim_dev.get(key)
+        if hit is None:
+            times = None if sampling_timesteps is None else [p[0] for p in self.ddim_schedule(sampling_timesteps, 0.0)[0]]
+            hit = tuple(tb.to(device) for tb in ops.jump_tables(np.cumprod(1. - self.np_betas, axis=0), jump_length, times))
+            self._ddim_dev[key] = hit
+        return hit
+
+    def _resample_inputs(self, device, j, r, k, U, eta=None):
+        """(schedule, (ja, jb) on the device, j) of a resampled loop of ``U`` calls (strided when ``eta`` is given), or None where the
+        schedule holds no jump -- r == 1, j >= U, K below every jump point's time: the loop is then the one without the keyword."""
+        sched = self.resample_schedule(j, r, k, *((U,) if eta is None else (None, U)))
+        if sched.jumps == 0:
+            return None
+        return sched, self.jump_table(j, device, None if eta is None else U), j
 
     def p_sample_loop_trajectory(self, denoise_fn, shape, device, freq, condition, condition_cross,
                                  noise_fn=torch.randn, clip_denoised=True, keep_running=False):
@@ -866,18 +961,21 @@ class GaussianDiffusion:
     def p_sample_loop_complete(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                clip_denoised=True, keep_running=False, partial_boxes=None, graph=None,
                                collision_scale=None, collision_steps=None,
-                               wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
+                               wall_scale=None, wall_steps=None, room_side=None, room_mask=None,
+                               resample=None, resample_steps=None):
         """Scene completion, reference :447-476: every step re-noises the given objects (noise drawn BEFORE the
         model call) and overwrites the first P rows of x_t in place; at t == 0 the clean objects are restored."""
         return self._loop("p_sample_loop_complete", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("dense", partial_boxes), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
-                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def p_sample_loop_complete_ragged(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                       clip_denoised=True, keep_running=False, partial_boxes=None, num_partial=None, graph=None,
                                       collision_scale=None, collision_steps=None,
-                                      wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
+                                      wall_scale=None, wall_steps=None, room_side=None, room_mask=None,
+                                      resample=None, resample_steps=None):
         """Scene completion of a batch whose scenes are given DIFFERENT numbers of objects.  ``partial_boxes`` is (B, Pmax, C) with
         1 <= Pmax <= N, ``num_partial`` the (B,) integer counts, 0 <= num_partial[b] <= Pmax; rows >= num_partial[b] of scene b are
         padding and never read.  Scene b is the reference's p_sample_loop_complete (:447-476) run on that scene alone with
@@ -887,13 +985,15 @@ class GaussianDiffusion:
         rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_inpaint_f32, bit-identical."""
         return self._loop("p_sample_loop_complete_ragged", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("ragged", partial_boxes, num_partial), clip_denoised=clip_denoised, keep_running=keep_running, say_last=True,
-                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def ddim_complete_ragged_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn,
                                   sampling_timesteps=50, ddim_sampling_eta=0., partial_boxes=None, num_partial=None, graph=None,
                                   collision_scale=None, collision_steps=None,
-                                  wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
+                                  wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None,
+                                  resample=None, resample_steps=None):
         """Strided (DDIM) scene completion of a batch with per-scene numbers of given objects.  Scene b is ddim_sample_loop (reference
         :402-444) run on that scene alone with ONE addition taken from p_sample_loop_complete (:447-476): before every model call at pair
         (t, t_next) the first num_partial[b] rows of the state are overwritten in place with q_sample(partial_boxes[b], t, fresh noise);
@@ -910,7 +1010,8 @@ class GaussianDiffusion:
         return self._loop("ddim_complete_ragged_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("ragged", partial_boxes, num_partial),
                           **_steer_kw(collision_scale, collision_steps),
-                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver),
+                          **_resample_kw(resample, resample_steps))
 
     def _ragged_inputs(self, shape, device, partial_boxes, num_partial, what):
         """(partial_boxes (B, Pmax, C) contiguous, counts (B,) int64 on the device: ops.ragged_counts) of a ragged completion loop."""
@@ -933,7 +1034,8 @@ class GaussianDiffusion:
     @torch.no_grad()
     def p_sample_loop_masked(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, clip_denoised=True,
                              keep_running=False, known=None, mask=None, graph=None,
-                             collision_scale=None, collision_steps=None, wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
+                             collision_scale=None, collision_steps=None, wall_scale=None, wall_steps=None, room_side=None, room_mask=None,
+                             resample=None, resample_steps=None):
         """Element-wise in-painting in T steps.  ``known`` is (B, N, C) f32 in the network's encoding, ``mask`` (B, N, C) or (B, N) bool /
         uint8 (ops.known_mask), non-zero = this element is given.  Scene b is the reference's p_sample_loop_complete (:447-476) on that
         scene alone with its two torch.cat's replaced by a select: before the model call at step t,
@@ -945,13 +1047,15 @@ class GaussianDiffusion:
         by the rules of p_sample_loop) replays one captured step whose update is the fused dsc_p_sample_masked_f32, bit-identical."""
         return self._loop("p_sample_loop_masked", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("mask", known, mask), clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def ddim_masked_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,
                          ddim_sampling_eta=0., known=None, mask=None, graph=None,
                          collision_scale=None, collision_steps=None,
-                         wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
+                         wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None,
+                         resample=None, resample_steps=None):
         """Element-wise in-painting in S strided (DDIM) steps; ``known`` / ``mask`` as in p_sample_loop_masked.  Scene b is ddim_sample_loop
         (reference :402-444) on that scene alone: before every model call at pair (t, t_next),
         x = where(mask, q_sample(known, t, fresh noise), x); after the last pair, x = where(mask, known, x).  x_start is always clamped
@@ -962,13 +1066,15 @@ class GaussianDiffusion:
         return self._loop("ddim_masked_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask),
                           **_steer_kw(collision_scale, collision_steps),
-                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def p_sample_loop_masked_guided(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                                     clip_denoised=True, keep_running=False, known=None, mask=None, graph=None,
                                     collision_scale=None, collision_steps=None,
-                                    wall_scale=None, wall_steps=None, room_side=None, room_mask=None):
+                                    wall_scale=None, wall_steps=None, room_side=None, room_mask=None,
+                                    resample=None, resample_steps=None):
         """Text-guided element-wise in-painting in T steps: scene b is p_sample_loop_masked with m = u + w[b] * (c - u) in place of the
         model output (c, u and ``guidance_scale`` as in p_sample_loop_guided; ``known`` / ``mask`` as in p_sample_loop_masked).  Both
         halves of the 2 B model call see the same overwritten x_t.  Draws: exactly those of p_sample_loop_masked at batch B, in its
@@ -977,13 +1083,15 @@ class GaussianDiffusion:
         dsc_p_sample_masked_cfg_f32, bit-identical."""
         return self._loop("p_sample_loop_masked_guided", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           given=("mask", known, mask), scale=guidance_scale, clip_denoised=clip_denoised, keep_running=keep_running,
-                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask))
+                          **_steer_kw(collision_scale, collision_steps), **_wall_kw(wall_scale, wall_steps, room_side, room_mask),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def ddim_masked_guided_loop(self, denoise_fn, shape, device, condition, condition_cross, guidance_scale, noise_fn=torch.randn,
                                 sampling_timesteps=50, ddim_sampling_eta=0., known=None, mask=None, graph=None,
                                 collision_scale=None, collision_steps=None,
-                                wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None):
+                                wall_scale=None, wall_steps=None, room_side=None, room_mask=None, sampling_solver=None,
+                                resample=None, resample_steps=None):
         """Text-guided element-wise in-painting in S strided (DDIM) steps: scene b is ddim_masked_loop with the guided output m of
         p_sample_loop_masked_guided in place of the model output.  x_start is always clamped to [-1, 1].  Draws: exactly those of
         ddim_masked_loop at batch B (2 S in all).  The eager loop is built from the unfused pieces; the graph path replays one captured
@@ -991,7 +1099,8 @@ class GaussianDiffusion:
         return self._loop("ddim_masked_guided_loop", denoise_fn, shape, device, condition, condition_cross, noise_fn, graph,
                           strided=(sampling_timesteps, ddim_sampling_eta), given=("mask", known, mask), scale=guidance_scale,
                           **_steer_kw(collision_scale, collision_steps),
-                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver))
+                          **_wall_kw(wall_scale, wall_steps, room_side, room_mask), **_solver_kw(sampling_solver),
+                          **_resample_kw(resample, resample_steps))
 
     @torch.no_grad()
     def ddim_arrange_loop(self, denoise_fn, shape, device, condition, condition_cross, noise_fn=torch.randn, sampling_timesteps=50,

@@ -430,6 +430,27 @@ class DiffusionSceneLayout_DDPM(Module):
         strided = None if sampling_timesteps is None else self._check_strided(sampling_timesteps, ddim_sampling_eta)
         return dict(sampling_solver=_check_solver(sampling_solver, strided, what))
 
+    def _check_resample(self, resample, resample_steps, sampling_solver=None, ret_traj=False, what="sample"):
+        """The refusals of ``resample`` / ``resample_steps``, before anything is computed or drawn -- not a pair of integers >= 1, K
+        without the pair or outside [0, T], a multistep solver, ``ret_traj``, a room_partial_condition / room_arrange_condition model
+        -> the keywords the loop receives: none at all without resampling, so that call stays what it was."""
+        if resample is None and resample_steps is None:
+            return {}
+        from .. import ops
+        if resample is None:
+            raise ValueError("%s: resample_steps goes with resample=(jump_length, n_resample)" % what)
+        ops.resample_pair(resample, what)
+        ops.resample_steps_value(resample_steps, int(self.config["diffusion_kwargs"].get("time_num", 1000)), what)
+        if sampling_solver is not None:
+            raise ValueError("%s: resample does not combine with sampling_solver=%r: the x0 history is void after a jump"
+                             % (what, sampling_solver))
+        if ret_traj:
+            raise ValueError("%s: resample returns the final scenes only (ret_traj is not supported)" % what)
+        if self.room_partial_condition or self.room_arrange_condition:
+            raise ValueError("%s: resample on a room_partial_condition / room_arrange_condition model: its condition tensors already "
+                             "encode a prefix / a sub-shape of the scene" % what)
+        return dict(resample=resample, resample_steps=resample_steps)
+
     def _check_guidance(self, text, partial_boxes=None, input_boxes=None, ret_traj=False):
         """The refusals of ``guidance_scale``, before anything is computed or drawn."""
         if not self.text_condition:
@@ -477,7 +498,7 @@ class DiffusionSceneLayout_DDPM(Module):
         return _check_ddim(int(self.config["diffusion_kwargs"].get("time_num", 1000)), sampling_timesteps, ddim_sampling_eta)
 
     def _complete_strided(self, room_mask, num_points, point_dim, padded, counts, batch_size, sampling_timesteps, ddim_sampling_eta,
-                          seeded={}, steer={}, solver={}):
+                          seeded={}, steer={}, solver={}, resample={}):
         """The strided completion call behind complete_scene / complete_scene_batched: the condition assembly of ``sample`` (the CPU
         draw included), then ``complete_samples_ragged_ddim``."""
         device = room_mask.device
@@ -489,7 +510,7 @@ class DiffusionSceneLayout_DDPM(Module):
         return self.diffusion.complete_samples_ragged_ddim((batch_size, num_points, point_dim), device, condition=condition,
                                                            condition_cross=condition_cross, partial_boxes=padded, num_partial=counts,
                                                            sampling_timesteps=sampling_timesteps, ddim_sampling_eta=ddim_sampling_eta,
-                                                           **seeded, **steer, **solver)
+                                                           **seeded, **steer, **solver, **resample)
 
     def _arrange_strided(self, room_mask, num_points, point_dim, input_boxes, batch_size, sampling_timesteps, ddim_sampling_eta,
                          seeded={}, solver={}):
@@ -510,14 +531,26 @@ class DiffusionSceneLayout_DDPM(Module):
     def complete_scene(self, room_mask, num_points, point_dim, partial_boxes, batch_size=1, ret_traj=False, ddim=False,
                        clip_denoised=False, batch_seeds=None, device="cpu", keep_empty=False, sampling_timesteps=None,
                        ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None, sampling_solver=None,
-                       wall_scale=None, wall_steps=None, room_side=None):
+                       wall_scale=None, wall_steps=None, room_side=None, resample=None, resample_steps=None):
         """reference :335-340.  ``sampling_timesteps=S`` runs the strided loop (``complete_samples_ragged_ddim`` with uniform counts:
         every scene is given all rows of ``partial_boxes``) instead of the T-step one; the post-filter is the same (batch row 0).
         x_start is always clamped there and ``clip_denoised`` / ``ret_traj`` play no part.  ``collision_scale`` / ``collision_steps``:
         collision steering (see ``sample``); the given objects repel the free ones and are never moved.  ``sampling_solver``:
-        "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
+        "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``).  ``resample`` / ``resample_steps``: RePaint's resampling jumps (see
+        ``complete_scene_batched``); the T-step call is then that method's (``_complete_tstep`` with uniform counts), the post-filter this
+        one's."""
+        jumps = self._check_resample(resample, resample_steps, sampling_solver, ret_traj, "complete_scene")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene")
         self._check_room(room_mask, batch_size, "complete_scene")
+        if jumps and sampling_timesteps is None:                  # sample() does not take the keyword: the T-step call of complete_scene_batched
+            shape = (batch_size, num_points, point_dim)
+            steer = self._check_steer(collision_scale, collision_steps, shape, what="complete_scene")
+            steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, shape, what="complete_scene"))
+            seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
+            padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
+            samples = self._complete_tstep(room_mask, num_points, point_dim, padded, counts, batch_size, clip_denoised, seeded, steer, jumps,
+                                           "complete_scene")
+            return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
@@ -525,7 +558,8 @@ class DiffusionSceneLayout_DDPM(Module):
                                            (batch_size, num_points, point_dim), what="complete_scene"))
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver,
+                                             jumps)
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         samples = self.sample(room_mask, num_points, point_dim, batch_size, partial_boxes=partial_boxes,
                               ret_traj=ret_traj, ddim=ddim, clip_denoised=clip_denoised, batch_seeds=batch_seeds,
@@ -674,7 +708,7 @@ class DiffusionSceneLayout_DDPM(Module):
                                clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None,
                                ddim_sampling_eta=0.0, scene_seeds=None, collision_scale=None, collision_steps=None,
                                sampling_solver=None,
-                               wall_scale=None, wall_steps=None, room_side=None):
+                               wall_scale=None, wall_steps=None, room_side=None, resample=None, resample_steps=None):
         """``complete_scene`` for a whole batch in which every scene is given ITS OWN number of objects: one reverse loop
         (``complete_samples_ragged``), each scene post-filtered on its own -- scene b is ``complete_scene`` at batch_size 1 with
         partial_boxes[b].  ``partial_boxes``: a list of B (P_b, C) tensors, or a padded (B, Pmax, C) tensor with ``num_partial`` (B,)
@@ -685,10 +719,18 @@ class DiffusionSceneLayout_DDPM(Module):
         given rows re-noised with fresh noise before every model call -- so at eta = 0 the free rows are deterministic given x_T and
         those draws, not given x_T alone; x_start always clamped, ``clip_denoised`` ignored) instead of the T-step one.
         ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); the given objects repel the
-        free ones and are never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
+        free ones and are never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``).
+        ``resample=(jump_length, n_resample)`` (None: this method as it was, same code path, same draws): RePaint's resampling jumps
+        -- after every stretch of ``jump_length`` reverse steps the whole state is diffused forward again by that many steps in one
+        draw and the stretch is walked down once more, ``n_resample`` times in all, so the free part sees the given part several times
+        at each noise level; ``resample_steps=K`` resamples only where the timestep is below K.  The cost is model
+        calls: U + (n_resample - 1) * jump_length per jump point (GaussianDiffusion.resample_schedule).  Combines with
+        ``sampling_timesteps``, steering and seeds; refused with ``sampling_solver`` and on room_partial_condition /
+        room_arrange_condition models."""
         device = room_mask.device
         if batch_size is None:
             batch_size = len(partial_boxes) if isinstance(partial_boxes, (list, tuple)) else int(partial_boxes.shape[0])
+        jumps = self._check_resample(resample, resample_steps, sampling_solver, False, "complete_scene_batched")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene_batched")
         self._check_room(room_mask, batch_size, "complete_scene_batched")
         steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
@@ -698,18 +740,26 @@ class DiffusionSceneLayout_DDPM(Module):
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
             padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
-            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver)
+            samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver,
+                                             jumps)
             return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
         padded, counts = self._ragged_partial(partial_boxes, num_partial, batch_size, num_points, point_dim, device)
+        samples = self._complete_tstep(room_mask, num_points, point_dim, padded, counts, batch_size, clip_denoised, seeded, steer, jumps)
+        return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
+
+    def _complete_tstep(self, room_mask, num_points, point_dim, padded, counts, batch_size, clip_denoised, seeded={}, steer={}, resample={},
+                        what="complete_scene_batched"):
+        """The T-step completion call behind complete_scene_batched (and complete_scene under ``resample``): the condition assembly of
+        ``sample`` (the CPU draw included), then ``complete_samples_ragged``."""
+        device = room_mask.device
         noise = torch.randn((batch_size, num_points, point_dim))   # CPU draw kept, as in sample (:232)
         if self.room_arrange_condition:
-            raise ValueError("complete_scene_batched: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)")
+            raise ValueError("%s: a room_arrange_condition model re-arranges scenes (arrange_scene_batched)" % what)
         condition, condition_cross = self._sampling_conditions(room_mask, num_points, device, padded_partial=padded, batch_size=batch_size)
         print('scene completion sampling')
-        samples = self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
-                                                         clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded,
-                                                         **steer)
-        return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
+        return self.diffusion.complete_samples_ragged(noise.shape, device, condition=condition, condition_cross=condition_cross,
+                                                      clip_denoised=clip_denoised, partial_boxes=padded, num_partial=counts, **seeded,
+                                                      **steer, **resample)
 
     @torch.no_grad()
     def arrange_scene_batched(self, room_mask, num_points, point_dim, input_boxes, batch_size=None, clip_denoised=False,
@@ -804,7 +854,7 @@ class DiffusionSceneLayout_DDPM(Module):
     def inpaint_scene_batched(self, room_mask, num_points, point_dim, boxes, known_mask, batch_size=None, text=None,
                               clip_denoised=False, batch_seeds=None, keep_empty=False, sampling_timesteps=None, ddim_sampling_eta=0.0,
                               scene_seeds=None, guidance_scale=None, collision_scale=None, collision_steps=None, sampling_solver=None,
-                              wall_scale=None, wall_steps=None, room_side=None):
+                              wall_scale=None, wall_steps=None, room_side=None, resample=None, resample_steps=None):
         """Attribute-level in-painting of a batch: every element of ``boxes`` marked in ``known_mask`` is held fixed, the rest of each
         scene is sampled around it -- one reverse loop (``inpaint_samples``; ``sampling_timesteps=S``: ``inpaint_samples_ddim``, x_start
         always clamped and ``clip_denoised`` ignored), each scene post-filtered on its own.  ``boxes``: (B, num_points, point_dim) in
@@ -818,8 +868,11 @@ class DiffusionSceneLayout_DDPM(Module):
         it back (``inpaint_samples_guided`` / ``inpaint_samples_guided_ddim``).  Needs ``text``; refused, before anything is drawn, on a
         model without ``text_condition`` and on a text encoder that does not give (B, L, text_embed_dim) features.
         ``collision_scale`` / ``collision_steps``: collision steering, a weight per scene (see ``sample``); a known element enters the
-        boxes with its known value and is never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
+        boxes with its known value and is never moved.  ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``).
+        ``resample`` / ``resample_steps``: RePaint's resampling jumps (see ``complete_scene_batched``), with or without ``text`` /
+        ``guidance_scale``."""
         from .. import ops
+        jumps = self._check_resample(resample, resample_steps, sampling_solver, False, "inpaint_scene_batched")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "inpaint_scene_batched")
         if self.room_partial_condition or self.room_arrange_condition:
             raise ValueError("inpaint_scene_batched: a room_partial_condition / room_arrange_condition model conditions on a prefix / a "
@@ -871,7 +924,7 @@ class DiffusionSceneLayout_DDPM(Module):
         print('scene in-painting sampling')
         if scale is not None:
             guided = dict(condition=condition, condition_cross=condition_cross, guidance_scale=scale, known=known, mask=mask, **seeded,
-                          **steer)
+                          **steer, **jumps)
             if sampling_timesteps is not None:
                 samples = self.diffusion.inpaint_samples_guided_ddim((B, N, C), device, sampling_timesteps=S, ddim_sampling_eta=eta,
                                                                      **guided, **solver)
@@ -880,10 +933,10 @@ class DiffusionSceneLayout_DDPM(Module):
         elif sampling_timesteps is not None:
             samples = self.diffusion.inpaint_samples_ddim((B, N, C), device, condition=condition, condition_cross=condition_cross,
                                                           known=known, mask=mask, sampling_timesteps=S, ddim_sampling_eta=eta, **seeded,
-                                                          **steer, **solver)
+                                                          **steer, **solver, **jumps)
         else:
             samples = self.diffusion.inpaint_samples((B, N, C), device, condition=condition, condition_cross=condition_cross,
-                                                     clip_denoised=clip_denoised, known=known, mask=mask, **seeded, **steer)
+                                                     clip_denoised=clip_denoised, known=known, mask=mask, **seeded, **steer, **jumps)
         return self.delete_empty_per_scene(samples, keep_empty=keep_empty)
 
     @torch.no_grad()

@@ -4,9 +4,11 @@ PyTorch is used for device memory and streams only: every function takes CUDA(HI
 passes raw device pointers + the current torch stream to libdiffuscene_hip.so and returns the output
 tensor.  There is no CPU path: a CPU tensor raises.
 """
+import collections
 import ctypes as C
 import numbers
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1192,6 +1194,154 @@ def multistep_rec(x_t, model_out, hist, weights, mean_type, tables, strided=None
     args = (_opt(x_t), model_out.data_ptr(), hist.data_ptr(), weights.data_ptr(), sp, tmp, _opt(ca), _opt(cb), _opt(scale), _opt(counts),
             _opt(mk), mean_type, b, hist.numel() // b, pmax, c, S, T)
     return "dsc_multistep_x0_f32", args, (x_t, model_out, hist, weights, tables, strided, rows, mask, scale)
+
+
+# ---------------------------------------------------------------------------------- resampling jumps
+
+ResampleSchedule = collections.namedtuple("ResampleSchedule", "ops calls jumps points")
+
+
+def resample_pair(resample, what):
+    """(jump_length, n_resample) of ``resample=``, two integers >= 1, or ValueError naming ``what``."""
+    ok = isinstance(resample, (tuple, list)) and len(resample) == 2 and all(
+        isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 1 for v in resample)
+    if not ok:
+        raise ValueError("%s: resample must be (jump_length, n_resample), two integers >= 1, got %r" % (what, resample))
+    return int(resample[0]), int(resample[1])
+
+
+def resample_steps_value(resample_steps, num_timesteps, what):
+    """K of ``resample_steps=``: None (no limit) or an integer in [0, T]; jump points whose time is below K resample."""
+    if resample_steps is None:
+        return None
+    k = resample_steps
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= int(k) <= num_timesteps:
+        raise ValueError("%s: resample_steps must be an integer in [0, %d], got %r" % (what, num_timesteps, k))
+    return int(k)
+
+
+def resample_schedule(U, jump_length, n_resample, times=None, resample_steps=None):
+    """The op list of a resampled loop (RePaint's get_schedule_jump).  Model calls are numbered by their remaining
+    index u = U - 1 ... 0; ``times`` None: time(u) = u (the T-step loops), else the (S,) times of the pairs, time(u) = times[U - 1 - u].
+    Jump points are s = 0, j, 2 j, ... < U - j with time(s) < ``resample_steps`` (None: all); each is jumped from r - 1 times, to s + j.
+    -> ResampleSchedule(ops, calls, jumps, points): ``ops`` the list of ("call", u) and ("jump", s) in order, a jump following the call
+    at s + 1; the number of model calls, of jumps and of jump points.  calls == U + (r - 1) * j * points."""
+    U, j, r = int(U), int(jump_length), int(n_resample)
+    if U < 1 or j < 1 or r < 1:
+        raise ValueError("resample_schedule: U, jump_length and n_resample must be >= 1, got %r" % ((U, j, r),))
+    if times is not None and len(times) != U:
+        raise ValueError("resample_schedule: %d times for %d calls" % (len(times), U))
+    time_of = (lambda u: u) if times is None else (lambda u: int(times[U - 1 - u]))
+    budget = {s: r - 1 for s in range(0, U - j, j) if resample_steps is None or time_of(s) < resample_steps}
+    points = sum(1 for v in budget.values() if v > 0)
+    out, calls, jumps = [], 0, 0
+    u = U
+    while u >= 1:
+        u -= 1
+        out.append(("call", u))
+        calls += 1
+        s = u - 1
+        if budget.get(s, 0) > 0:
+            budget[s] -= 1
+            out.append(("jump", s))
+            jumps += 1
+            u = s + j + 1
+    return ResampleSchedule(out, calls, jumps, points)
+
+
+def jump_tables(alphas_cumprod, jump_length, times=None):
+    """(ja, jb) float32 CPU tables of dsc_resample_jump_f32 from the float64 ``alphas_cumprod`` (T,): ja = sqrt(abar[time(s + j)] /
+    abar[time(s)]), jb = sqrt(1 - that ratio), float64 on the host, rounded once.  ``times`` None: T rows indexed by s (time(s) = s);
+    else S rows indexed by the step counter k of the pair at s (time = times[k], the target times[k - j]).  A row that no jump can start
+    from (s + j > T - 1, k < j) holds (1, 0)."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    j = int(jump_length)
+    if ac.ndim != 1 or j < 1:
+        raise ValueError("jump_tables: alphas_cumprod must be a (T,) float64 table and jump_length >= 1")
+    if times is None:
+        n = ac.shape[0]
+        src = np.arange(n)
+        dst = src + j
+        ok = dst < n
+        frm, to = ac[src[ok]], ac[dst[ok]]
+    else:
+        tm = np.asarray([int(v) for v in times], dtype=np.int64)
+        n = tm.shape[0]
+        k = np.arange(n)
+        ok = k >= j
+        frm, to = ac[tm[k[ok]]], ac[tm[k[ok] - j]]
+    ratio = np.ones((n,), dtype=np.float64)
+    ratio[ok] = to / frm
+    ja, jb = np.sqrt(ratio), np.sqrt(1.0 - ratio)
+    return torch.from_numpy(ja.astype(np.float32)), torch.from_numpy(jb.astype(np.float32))
+
+
+def jump_rec(x, noise, ja, jb, jump, t=None, strided=None, rows=None, mask=None, q=(), x_dup=None):
+    """The launch record of one resampling jump (dsc_resample_jump_f32), in place on ``x``: the time source -- ``t`` (B,) int64 holding s,
+    or ``strided`` = (step, times, ...) with the counter on the pair at s --, the tables of jump_tables on the device, and optionally the
+    given part of the NEXT model call, ``rows`` = (partial, noise_p, counts) or ``mask`` = (known, noise_k, mask) with ``q`` = (sqrt_ac,
+    sqrt_1mac): the fused form.  ``x_dup``: the null half of a guided loop's state."""
+    if rows is not None and mask is not None:
+        raise ValueError("diffuscene_amd: resample_jump takes one given part, rows or mask")
+    if (t is None) == (strided is None):
+        raise ValueError("diffuscene_amd: resample_jump takes one time source, t or strided")
+    given = rows if rows is not None else mask
+    if len(q) != (2 if given is not None else 0):
+        raise ValueError("diffuscene_amd: resample_jump takes q = (sqrt_ac, sqrt_1mac) with a given part and only then")
+    _c(x, "x"); _c(noise, "noise"); _c(ja, "ja"); _c(jb, "jb")
+    jump = int(jump)
+    if jump < 1:
+        raise ValueError("diffuscene_amd: resample_jump needs jump >= 1, got %d" % jump)
+    b = x.shape[0]
+    _same_shape("resample_jump", x, noise, x_dup)
+    if x_dup is not None:
+        _c(x_dup, "x_dup")
+    T = _table_rows(*q) if q else 2 ** 31 - 1
+    tp = sp = tmp = None
+    S = 0
+    if strided is not None:
+        step, times = strided[0], strided[1]
+        _dev(step, "step", torch.int64); _dev(times, "times", torch.int64)
+        if not times.is_contiguous():
+            raise RuntimeError("diffuscene_amd: times must be contiguous")
+        sp, tmp, S = step.data_ptr(), times.data_ptr(), times.numel()
+        if _table_rows(ja, jb) != S:
+            raise RuntimeError("diffuscene_amd: ja / jb of a strided jump hold one row per pair (%d)" % S)
+    else:
+        _scene_t(t, b)
+        tp = t.data_ptr()
+        rows_j = _table_rows(ja, jb)
+        if q and rows_j != T:
+            raise RuntimeError("diffuscene_amd: ja / jb (%d rows) and the schedule tables (%d rows) differ" % (rows_j, T))
+        T = rows_j
+    gp = ngp = mk = counts = None
+    pmax = c = 0
+    if rows is not None:
+        _dev(rows[2], "counts", torch.int64)
+        _, _, pmax, c, cnt = _ragged_args(x, *rows)
+        gp, ngp, counts = rows[0].data_ptr(), rows[1].data_ptr(), cnt.data_ptr()
+    if mask is not None:
+        _masked_args(x, *mask)
+        gp, ngp, mk = mask[0].data_ptr(), mask[1].data_ptr(), mask[2].data_ptr()
+    args = (x.data_ptr(), noise.data_ptr(), ja.data_ptr(), jb.data_ptr(), tp, sp, tmp, gp, ngp, mk, counts,
+            q[0].data_ptr() if q else None, q[1].data_ptr() if q else None, _opt(x_dup), jump, b, x.numel() // b, pmax, c, S, T)
+    return "dsc_resample_jump_f32", args, (x, noise, ja, jb, t, strided, rows, mask, q, x_dup)
+
+
+def resample_jump(x, noise, ja, jb, jump, **operands):
+    """One resampling jump in place (jump_rec issued at once) -> x."""
+    issue(jump_rec(x, noise, ja, jb, jump, **operands))
+    return x
+
+
+def ddim_seek(step, times, t, delta):
+    """step += delta; t[:] = times[step] (device-side, capturable): the move after a jump in a strided loop."""
+    _dev(step, "step", torch.int64); _dev(t, "t", torch.int64); _dev(times, "times", torch.int64)
+    if not times.is_contiguous():
+        raise RuntimeError("diffuscene_amd: times must be contiguous")
+    _lib.check(_lib.fn("dsc_ddim_seek_i64")(step.data_ptr(), times.data_ptr(), t.data_ptr(), t.numel(), times.numel(), int(delta),
+                                            stream_ptr()), "dsc_ddim_seek_i64")
+    return t
 
 
 def scene_gate(x, keep, out=None):

@@ -32,6 +32,9 @@ A loop is three orthogonal parts, the axes of the one step kernel (csrc/diffusio
                   non-final graph -- the last pair has weight 0 and needs none; the step kernel is the unchanged one.
   walls           _Walls (optional, ``walls=``): floor-plan steering -- the weights, K, the distance field of the room mask and the room
                   side in buffers of the graph, ONE launch (dsc_steer_walls_f32) after _Steer and before _Multistep.
+  jumps           _Jump (optional, ``jumps=``): RePaint's resampling jumps -- the jump tables in buffers of the graph, two more graphs (``jump``:
+                  the jump draw, the given draw of the next call, ONE launch dsc_resample_jump_f32, the move; ``prejump``: the step a jump
+                  follows, without its given draw), replayed along the host's op list (ops.resample_schedule); j is part of the key.
 _Loop has the one ``_step(final)`` -- [unfused overwrite,] model call, [steering,] [walls,] [multistep unless final,] main draw, given draw unless
 final, [cfg_combine,] ONE update launch laid out by ops.step_rec from the operands of the three parts, [copy into the null half,] move unless final -- and the one ``run``.
 The ten classes are rows:                    schedule   given            guided   fused=False unfuses
@@ -74,6 +77,10 @@ class NoiseReplay:
             n = self.partial_buffer[self.ip]
             self.ip += 1
             return n
+        return self.main_draw(size)
+
+    def main_draw(self, size=None, dtype=None, device=None):
+        """The next row of the main buffer, whatever the shapes or the call count say: also the draw of a resampling jump."""
         n = self.buffer[self.i]
         self.i += 1
         assert tuple(n.shape) == tuple(size), (tuple(n.shape), tuple(size))
@@ -161,6 +168,8 @@ class _LoopGraph:
     scene of the loop (2 for the guided loops), ``draws``: rows of the main replay buffer, ``nch``: sub-batch chains.  ``replay``: the
     noise mode -- False / RANDN, True / REPLAY, or SEEDED: the graph owns a (B,) seed buffer, refreshed in place by ``seeded_x_T``."""
 
+    resample = prejump = jump = None         # the jump part of a _Loop and its two graphs
+
     def __init__(self, diff, model, shape, device, condition, condition_cross, replay, draws, mult=1, nch=1):
         B, N, C = shape
         self.shape, self.device = shape, device
@@ -200,6 +209,7 @@ class _LoopGraph:
     def _capture(self, kinds):
         """Warm-up on a side stream (loads every code object, sizes the allocator), then capture: ``graph`` = _step(False) and
         ``final`` = _step(True), from ``graph``'s pool where there is one, for the kinds asked for.
+        ``kinds`` may also name the two graphs of a jump part, "prejump" and "jump" (_Loop._body), kept under those names.
         Building the graph must not cost the caller random numbers: the loops are the default path behind the reference's call sites,
         and a run seeded with torch.manual_seed has to draw what the eager loop draws whether or not this call had to capture first --
         so the device generator's state is put back afterwards (normal_() and the warm-up steps draw from it).
@@ -213,19 +223,26 @@ class _LoopGraph:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            for final in kinds:
-                self._step(final)
+            for kind in kinds:
+                self._body(kind)
         torch.cuda.current_stream(dev).wait_stream(side)
-        for final in kinds:
+        pool = None                             # every graph from the pool of the first one captured
+        for kind in kinds:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=None if self.graph is None else self.graph.pool()):
-                self._step(final)
-            if final:
+            with torch.cuda.graph(g, pool=pool):
+                self._body(kind)
+            pool = pool or g.pool()
+            if kind is True:
                 self.final = g
-            else:
+            elif kind is False:
                 self.graph = g
+            else:
+                setattr(self, kind, g)
         torch.cuda.set_rng_state(rng_state, dev)
         self._park()
+
+    def _body(self, kind):
+        self._step(kind)
 
     def _park(self):
         """The in-graph timestep holds -1 after a T-step loop: put the counters on valid rows, so that one replay too many (a caller
@@ -295,7 +312,7 @@ class _PosteriorLoop(_LoopGraph):
         return [False, True] if fused_given else [False]
 
     def _capture(self, kinds):
-        self.t.fill_(1)
+        self.t.fill_(0 if kinds[0] == "jump" else 1)    # a warm-up that opens with the jump: 0 -> j -> j - 1, all rows of the schedule
         super()._capture(kinds)
 
     def _main_draw(self, final):
@@ -303,6 +320,12 @@ class _PosteriorLoop(_LoopGraph):
 
     def _move(self):
         ops.add_scalar_i64(self.t, -1)
+
+    def _jump_time(self):
+        return dict(t=self.t[:self.shape[0]])
+
+    def _jump_move(self, j):
+        ops.add_scalar_i64(self.t, j)
 
     def _begin(self, total_steps):
         """-> (the first timestep, the steps of this run)."""
@@ -342,13 +365,24 @@ class _DDIMLoop(_LoopGraph):
         self.t.fill_(t0)
 
     def _copy_rows(self, dst, src):
-        dst.copy_(src[:self.S])                 # the buffers hold exactly S rows
+        dst.copy_(src[:dst.shape[0]])           # the buffers hold exactly S rows (with a jump part: the rows of its schedule)
+
+    def _capture(self, kinds):
+        if self.resample:                       # the warm-up of a jump part: [j - 1 ->] j -> 0 -> 1, all pairs of the schedule
+            self.step.fill_(self.resample.j - (kinds[0] == "prejump"))
+        super()._capture(kinds)
 
     def _main_draw(self, final):
         return self.x if final else self.noise()                # not read on the last pair
 
     def _move(self):
         ops.ddim_advance(self.step, self.times, self.t)
+
+    def _jump_time(self):
+        return dict(strided=(self.step, self.times))
+
+    def _jump_move(self, j):
+        ops.ddim_seek(self.step, self.times, self.t, -j)
 
     def _begin(self, dtab, weights=None):
         """The tables of this run into the graph's own -> (the first timestep, S).  ``weights``: the (S,) history weights of a loop
@@ -398,6 +432,10 @@ class _Given:
 
     def steer_operands(self, g):
         """What the part adds to ops.steer_rec: a given element enters the boxes with its given value and is never moved."""
+        return {}
+
+    def jump_operands(self, g):
+        """What a fused part adds to ops.jump_rec: its values and the given draw of the model call the jump leads to."""
         return {}
 
 
@@ -450,6 +488,9 @@ class _Ragged(_Given):
     def operands(self, g, final):                  # the partial draw is not read after the last step
         return dict(rows=(self.partial, self.partial if final else self.noise(), self.counts), q=g.q) if self.fused else {}
 
+    def jump_operands(self, g):
+        return dict(rows=(self.partial, self.noise(), self.counts), q=g.q) if self.fused else {}
+
     def restore(self, g, out):
         return out if self.fused else restore_given_rows(out, self.partial, self.counts)
 
@@ -476,6 +517,9 @@ class _Masked(_Given):
 
     def operands(self, g, final):                  # the known-draw is not read after the last step
         return dict(mask=(self.known, self.known if final else self.noise(), self.mask), q=g.q)
+
+    def jump_operands(self, g):
+        return dict(mask=(self.known, self.noise(), self.mask), q=g.q)
 
     def steer_operands(self, g):
         return dict(mask=(self.known, None, self.mask))
@@ -572,6 +616,33 @@ class _Multistep:
         ops.issue(ops.multistep_rec(g.x, mo, self.hist, self.weights, g.mean_type, **g.sched, **g.part.steer_operands(g), **scale))
 
 
+class _Jump:
+    """Resampling jumps (RePaint; INTEGRATION.md 9, dsc_resample_jump_f32).  ``j`` is baked into the launch and the move and part of the
+    cache key; the tables ``ja`` / ``jb`` (T rows, or S of a strided loop) are buffers of the graph refreshed in place; r and K are host
+    control -- ``run`` replays along the op list of ops.resample_schedule, so one graph set serves every (r, K).  Two more graphs:
+      jump     the jump draw (main stream), the given draw of the model call at s + j where the given part is fused, ONE launch -- the
+               jump of the free elements and the re-noising of the given ones at time(s + j), both halves of a guided state --, the move
+               (t += j; strided: step -= j, t = times[step]);
+      prejump  beside a fused given part, the step that a jump follows: the step without its given draw -- the jump makes the one the
+               next model call needs, and writes every given element, so what this step leaves there is never read.
+    ``rows`` = (main rows, given rows) of the replay buffers, from the schedule's counts (replay mode only: then part of the key)."""
+
+    def __init__(self, g, j):
+        self.j = int(j)
+        rows = g.S if g.strided else g.T
+        self.ja = torch.ones((rows,), device=g.device, dtype=torch.float32)
+        self.jb = torch.zeros((rows,), device=g.device, dtype=torch.float32)
+
+    def load(self, tables):
+        self.ja.copy_(tables[0])                # in place: the graph holds these pointers
+        self.jb.copy_(tables[1])
+
+    def apply(self, g):
+        noise = g.noise()
+        ops.issue(ops.jump_rec(g.x, noise, self.ja, self.jb, self.j, **g._jump_time(), **g.part.jump_operands(g), x_dup=g.x_null))
+        g._jump_move(self.j)
+
+
 class _Loop:
     """One captured loop = a schedule (_PosteriorLoop or _DDIMLoop, by inheritance), a given part and guidance: the row a class below
     declares.  ``sched``: clip_denoised of a T-step loop, S of a strided one.  ``fused`` unfuses what the row has a kernel for: the
@@ -579,10 +650,13 @@ class _Loop:
     given, guided, chains, what, multistep = _Given, False, False, None, None
 
     def __init__(self, diff, model, shape, device, condition, condition_cross, sched, replay=False, fused=True, partial_shape=None,
-                 steer=None, multistep=False, walls=None):
-        nch = (_chains_for(shape[0]),) if self.chains else ()
+                 steer=None, multistep=False, walls=None, resample=None):
+        nch = (_chains_for(shape[0]),) if self.chains and resample is None else ()     # a loop with a jump part runs as one chain
         super().__init__(diff, model, shape, device, condition, condition_cross, sched, replay, 2 if self.guided else 1, *nch)
         self.fused = fused
+        if resample is not None and self.replay:                # (j, main rows, given rows): the replay buffers follow the schedule
+            self.noise = self._stream(shape, resample[1])
+            self.given_draws = resample[2]
         self.side = [torch.cuda.Stream(device=device) for _ in range(len(self.plans) - 1)]
         self.model_out = torch.empty(shape, device=device, dtype=torch.float32) if self.side else None
         part = self.given if self.given is not _Dense or partial_shape is not None else _Given
@@ -593,11 +667,25 @@ class _Loop:
         if multistep and not self.strided:
             raise ValueError("a multistep solver rides on the strided loops")
         self.multistep = _Multistep(self) if multistep else None
+        if resample is not None and multistep:
+            raise ValueError("resampling jumps do not combine with a multistep solver")
+        self.resample = _Jump(self, resample[0]) if resample is not None else None
         for owner in (self.part, self.guide):   # the buffers, by the names tests, tools and bench.py read
             for name in ("partial", "counts", "known", "mask", "scale", "m"):
                 if hasattr(owner, name):
                     setattr(self, name, getattr(owner, name))
-        self._capture(self._kinds(self.part.fused))
+        kinds = self._kinds(self.part.fused)
+        if self.resample:                       # the jump graphs first: the warm-up then stays on rows of the schedule (_capture)
+            kinds = (["prejump"] if self.part.fused else []) + ["jump"] + kinds
+        self._capture(kinds)
+
+    def _body(self, kind):
+        if kind == "jump":
+            self.resample.apply(self)
+        elif kind == "prejump":
+            self._step(False, given_draw=False)
+        else:
+            self._step(kind)
 
     def _model_call(self):
         """One plan, or the sub-batch chains of _chains_for: chain 0 on the current stream, the others on side streams."""
@@ -626,8 +714,9 @@ class _Loop:
             cur.wait_stream(st)
         return self.model_out
 
-    def _step(self, final):
-        """[the unfused overwrite,] model call, [collision steering,] [floor-plan steering,] [the multistep launch unless final,] main
+    def _step(self, final, given_draw=True):
+        """``given_draw=False``: the step a jump follows (_Jump).
+        [the unfused overwrite,] model call, [collision steering,] [floor-plan steering,] [the multistep launch unless final,] main
         draw, the given draw of the NEXT step unless final,
         [cfg_combine,] one update launch, [the copy into the null half,] decrement or advance unless final."""
         self.part.before(self)
@@ -639,7 +728,7 @@ class _Loop:
         if self.multistep and not final:
             self.multistep.apply(self, mo)
         noise = self._main_draw(final)
-        given = self.part.operands(self, final)
+        given = self.part.operands(self, final or not given_draw)
         mo, guided = self.guide.apply(self, mo) if self.guide else (mo, {})
         ops.issue(ops.step_rec(self.x, mo, noise, self.x, self.mean_type, **self.sched, **given, **guided))
         if self.guide:
@@ -647,10 +736,25 @@ class _Loop:
         if not final:
             self._move()
 
-    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None, multistep=None, walls=None):
+    def _replays_along(self, op_list):
+        """One loop along the op list of ops.resample_schedule: a call is ``final`` at u == 0 where the class has one, ``prejump`` where a
+        jump follows and the given part is fused, else ``graph``; a jump is ``jump``."""
+        for i, (op, u) in enumerate(op_list):
+            if op == "jump":
+                self.jump.replay()
+            elif u == 0 and self.final is not None:
+                self.final.replay()
+            elif self.prejump is not None and i + 1 < len(op_list) and op_list[i + 1][0] == "jump":
+                self.prejump.replay()
+            else:
+                self.graph.replay()
+        return self.x.clone()
+
+    def run(self, x_T, sched, *values, noise_buffer=None, given_noise=None, partial=None, steer=None, multistep=None, walls=None,
+            jumps=None):
         """``sched``: total_steps of a T-step loop, the device tables (GaussianDiffusion.ddim_tables) of a strided one.  ``values``: the
         (B,) scales of a guided row, then what the given part loads (``partial``: the dense prefix by keyword).  ``multistep``: the
-        (S,) history weights of a loop with a multistep part."""
+        (S,) history weights of a loop with a multistep part.  ``jumps`` = (schedule, (ja, jb)) of a loop with a jump part."""
         t0, steps = self._begin(sched, *(() if self.multistep is None else (multistep,)))
         self._start(x_T, t0)
         if partial is not None:
@@ -663,11 +767,13 @@ class _Loop:
             self.steer.load(*steer)             # (weight (B,), K): steered while t < K
         if self.walls:
             self.walls.load(*walls)             # (weight (B,), K, field, room_side)
+        if self.resample:
+            self.resample.load(jumps[1])
         self._upload((self.noise, noise_buffer, 1), *([(self.part.noise, given_noise, 1 if self.part.fused else 0)] if self.part.noise else []))
         self.part.first(self)
         if self.part.fused and self.x_null is not None:         # guided: both halves of the state stay current
             self.x_null.copy_(self.x)
-        out = self.part.restore(self, self._replays(steps))
+        out = self.part.restore(self, self._replays_along(jumps[0].ops) if self.resample else self._replays(steps))
         self._end()
         return out
 
@@ -790,9 +896,12 @@ def _front_end(name, cls):
     names = (("scale",) if cls.guided else ()) + (("sampling_timesteps", "eta") if cls.strided else ("clip_denoised", "total_steps")) \
         + ("noise_fn",) + cls.given.values + (("fused",) if cls.guided or cls.given is _Ragged else ())
 
-    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, multistep=None, walls=None, **kw):
+    def loop(diff, denoise_fn, shape, device, condition, condition_cross, *args, steer=None, multistep=None, walls=None, jumps=None,
+             **kw):
         if multistep is not None and not cls.strided:
             raise ValueError("%s: a multistep solver rides on the strided loops" % name)
+        if jumps is not None and multistep is not None:
+            raise ValueError("%s: resampling jumps do not combine with a multistep solver" % name)
         if len(args) > len(names) or not set(kw) <= set(names[len(args):]):
             raise TypeError("%s(diff, denoise_fn, shape, device, condition, condition_cross, %s)" % (name, ", ".join(names)))
         a = dict(dict.fromkeys(names), noise_fn=torch.randn, fused=True)
@@ -804,22 +913,33 @@ def _front_end(name, cls):
             sched = n_main = n_given = int(a["sampling_timesteps"])
         else:
             sched, n_main, n_given = bool(a["clip_denoised"]), a["total_steps"] + 1, a["total_steps"]
+        total = None if cls.strided else n_given
+        jump_key = jump_spec = None
+        if jumps is not None:                   # (schedule, (ja, jb) on the device, j): the buffers follow the schedule's counts
+            js = jumps[0]
+            n_main, n_given = js.calls + js.jumps + (0 if cls.strided else 1), js.calls
+            jump_spec = (int(jumps[2]), n_main, n_given)
+            jump_key = ("resample",) + (jump_spec if isinstance(a["noise_fn"], NoiseReplay) else jump_spec[:1])
         # steer = (weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim): the first two live in buffers, the rest is the key
         layout = None if steer is None else (tuple(float(v) for v in steer[2]), int(steer[3]), int(steer[4]))
         # walls = (weight, K, bounds, bbox_dim, class_dim, field (B or 1, H, W) f32 on the device, room_side): the key is the layout and (H, W)
         wall_layout = None if walls is None else (tuple(float(v) for v in walls[2]), int(walls[3]), int(walls[4])) + tuple(walls[5].shape[1:])
-        check = cls.what and _replay_check(cls.what % sched if "%" in cls.what else cls.what, n_main,
+        what = cls.what or (jumps is not None and "the resampled T-step loop") or None
+        check = what and _replay_check((what % sched if "%" in what else what) + (" with resampling jumps" if jumps is not None and cls.what else ""), n_main,
                                            shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
         out = _cached_loop(
             name, diff, denoise_fn, shape, device, condition, condition_cross, a["noise_fn"],
             (cls.__name__, sched, bool(a["fused"]), gshape) + (() if steer is None else (layout,))
-            + (() if multistep is None else ("multistep",)) + (() if walls is None else (("walls",) + wall_layout,)),
+            + (() if multistep is None else ("multistep",)) + (() if walls is None else (("walls",) + wall_layout,))
+            + (() if jumps is None else (jump_key,)),
             lambda model, dev, replay: cls(diff, model, tuple(shape), dev, condition, condition_cross, sched, replay, a["fused"], gshape,
-                                           layout, multistep is not None, *(() if walls is None else (wall_layout,))),
-            lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else n_given, *([a["scale"]] if cls.guided else []), *given,
+                                           layout, multistep is not None, *(() if walls is None else (wall_layout,)),
+                                           **({} if jumps is None else dict(resample=jump_spec))),
+            lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else total, *([a["scale"]] if cls.guided else []), *given,
                                                   noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given),
                                                   steer=None if steer is None else steer[:2], multistep=multistep,
-                                                  **({} if walls is None else dict(walls=walls[:2] + walls[5:]))),
+                                                  **({} if walls is None else dict(walls=walls[:2] + walls[5:])),
+                                                  **({} if jumps is None else dict(jumps=jumps[:2]))),
             mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
         if cls.given is _Dense and given:
             out[:, :gshape[1], :] = given[0]            # clean objects restored after the last step (:471-473)

@@ -98,6 +98,13 @@ class SceneNoise:
             raise ValueError("SceneNoise holds %d seeds, the loop draws for %d scenes" % (self.seeds.shape[0], size[0]))
         stream = GIVEN if self.given and self.calls % 2 == 1 else MAIN
         self.calls += 1
+        return self._draw(stream, size)
+
+    def main_draw(self, size=None, dtype=None, device=None):
+        """One more draw of the main stream that does not take a turn of the alternation: the draw of a resampling jump."""
+        return self._draw(MAIN, tuple(size))
+
+    def _draw(self, stream, size):
         draw = torch.full((1,), self.next_draw[stream], dtype=torch.int64, device=self.device)
         self.next_draw[stream] += 1
         return ops.scene_randn(self.seeds, draw, stream, size)

@@ -508,6 +508,30 @@ int dsc_multistep_x0_f32(const float* x_t, float* model_out, float* hist, const 
                          const uint8_t* mask, int32_t mean_type, int32_t b, int64_t inner, int32_t pmax, int32_t c, int32_t num_steps,
                          int32_t num_timesteps, dsc_stream_t stream);
 
+/* The resampling jump of the completion and in-painting loops (RePaint; INTEGRATION.md 9 states the schedule): one forward diffusion of
+ * the whole state x (b, inner), IN PLACE, from remaining index s to s + jump:
+ *   free element:   x = (ja[pos] * x) + (jb[pos] * noise)
+ *   given element:  x = (sqrt_ac[tt] * given) + (sqrt_1mac[tt] * noise_g)   -- what the overwrite in front of the next model call writes
+ * the two products and the sum rounded one by one.  One time source: t (b,) -- pos = t[i], tt = t[i] + jump, ja / jb of num_timesteps
+ * rows -- or step (1,) and times (num_steps,) -- pos = k = *step, tt = times[k - jump], ja / jb of num_steps rows.  ja[pos] =
+ * sqrt(abar[time(s + jump)] / abar[time(s)]) and jb[pos] = sqrt(1 - that ratio) are tabulated by the host in float64 and rounded once.
+ * The given part: rows [0, counts[i]) of pmax <= inner / c rows of c channels (given / noise_g are (b, pmax, c)), or mask != 0 (given /
+ * noise_g / mask have x's shape), at most one of the two; given == NULL (then noise_g, counts and mask must be NULL too) is the plain jump
+ * of every element, dsc_q_sample_f32 on the tables (ja, jb).  A given element reads mask, given and noise_g only, a free one mask, x and
+ * noise only.  x_dup (may be NULL) receives a second copy of every element written.  The result is bit-identical to dsc_q_sample_f32
+ * with (ja, jb) at t = s followed by the matching dsc_*_overwrite*_f32 at tt.  Indices are clamped and counted (dsc_device_error_count):
+ * t[i], t[i] + jump and counts[i] once per scene; *step, k - jump and times[.] once per launch; tt only with a given part.
+ * b <= 65535 (else DSC_ERANGE); jump < 1, two time sources or two given parts: DSC_EINVAL. */
+int dsc_resample_jump_f32(float* x, const float* noise, const float* ja, const float* jb, const int64_t* t, const int64_t* step,
+                          const int64_t* times, const float* given, const float* noise_g, const uint8_t* mask, const int64_t* counts,
+                          const float* sqrt_ac, const float* sqrt_1mac, float* x_dup, int32_t jump, int32_t b, int64_t inner,
+                          int32_t pmax, int32_t c, int32_t num_steps, int32_t num_timesteps, dsc_stream_t stream);
+
+/* The move after a jump in a strided loop, the seek form of dsc_ddim_advance_i64: *step += delta (clamped to [0, num_steps) and
+ * counted), then t[i] = times[*step] for i < count.  One launch of one block. */
+int dsc_ddim_seek_i64(int64_t* step, const int64_t* times, int64_t* t, int32_t count, int32_t num_steps, int64_t delta,
+                      dsc_stream_t stream);
+
 /* Floor-plan steering, the field: once per call.  mask (b, h, w) f32, pixel (i, j) inside iff > 0.5; the image
  * covers x in [-room_side, room_side] along its columns and z likewise along its rows, dx = 2 room_side / w, dz = 2 room_side / h.
  *   field[i, j] = 1/2 min over inside pixels (i', j') of ((i - i') dz)^2 + ((j - j') dx)^2   (metres^2; 0 at inside pixels),
