@@ -195,47 +195,96 @@ __device__ __forceinline__ double block_sum_steer(double v, double* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The frame both steering kernels stand on.  The scene: the checked time and given-row count, the weight, whether this launch moves the
+// model output, the x0 coefficients, the guidance scale and the offsets of thread tid's row in either half of the model output.
+struct SteerScene {
+    int64_t cnt, row, half;
+    float w, A, Bc, s;
+    bool is_x0, active;
+};
+
+__device__ __forceinline__ SteerScene steer_scene(const SteerArgs& p, int b, int tid) {
+    SteerScene f;
+    const bool first = tid == 0;
+    f.is_x0 = p.mean_type == DSC_MEAN_X0;
+    int64_t tv;
+    if (p.t) tv = dsc_checked_index(p.t[b], p.T, first);
+    else tv = dsc_checked_index(p.times[dsc_checked_index(p.step[0], p.S, first && b == 0)], p.T, first && b == 0);
+    f.cnt = 0;
+    if (p.counts) f.cnt = dsc_checked_index(p.counts[b], (int64_t)p.pmax + 1, first);
+    f.w = p.weight[b];
+    f.active = f.w != 0.f && tv < p.t_below[0];
+    f.A = f.is_x0 ? 0.f : p.ca[tv], f.Bc = f.is_x0 ? 0.f : p.cb[tv];
+    f.s = p.scale ? p.scale[b] : 0.f;
+    f.half = (int64_t)p.b * p.n * p.c;
+    f.row = (int64_t)b * p.n * p.c + (int64_t)tid * p.c;
+    return f;
+}
+
+// Row tid < n of the clamped x0 estimate: the 8 box channels and the 'empty' logit, and for the translation channels the unclamped and
+// the clamped prediction and whether the element is free.
+struct SteerRow {
+    float v[9], raw[3], x0c[3];
+    bool is_free[3];
+};
+
+__device__ __forceinline__ SteerRow steer_x0_row(const SteerArgs& p, const SteerScene& f, int b, int tid) {
+    SteerRow r{};
+    const int64_t row = f.row, half = f.half;
+    const bool row_given = p.counts && tid < f.cnt;
+    const int64_t grow = ((int64_t)b * p.pmax + tid) * p.c;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const int ch = k < 8 ? k : p.empty_col;
+        const bool given = row_given || (p.mask && p.mask[row + ch] != 0);
+        if (given) {
+            r.v[k] = row_given ? p.partial[grow + ch] : p.known[row + ch];
+        } else {
+            float m = p.mo[row + ch];
+            if (p.scale) m = cfg_mix(m, p.mo[half + row + ch], f.s);
+            const float x = predict_x0(f.is_x0 ? 0.f : p.xt[row + ch], m, f.A, f.Bc, p.mean_type, false);
+            r.v[k] = fminf(fmaxf(x, -1.0f), 1.0f);
+            if (k < 3) r.raw[k] = x, r.x0c[k] = r.v[k];
+        }
+        if (k < 3) r.is_free[k] = !given;
+    }
+    return r;
+}
+
+// Translation channel k of row tid < n, with g = dE / d centre_k: the gradient in normalised units goes to the optional output, and
+// where `move` holds on an active step the free element's model output is moved (both halves of a guided one).
+__device__ __forceinline__ void steer_store(const SteerArgs& p, const SteerScene& f, const SteerRow& r, int b, int tid, int k, double g,
+                                            bool move) {
+    const int64_t row = f.row, half = f.half;
+    const double gn = g * p.c_span[k] * 0.5;                                                  // d centre / d x0 = span / 2
+    if (p.grad) p.grad[((int64_t)b * p.n + tid) * 3 + k] = (float)gn;
+    if (!move || !f.active || !r.is_free[k]) return;
+    const double wg = (double)f.w * gn;
+    if (wg == 0. || (!f.is_x0 && f.Bc == 0.f)) return;
+    const double d = wg + ((double)r.raw[k] - (double)r.x0c[k]);
+    const double delta = f.is_x0 ? -d : d / (double)f.Bc;
+    if (p.scale) {
+        const float c0 = p.mo[row + k], u0 = p.mo[half + row + k];
+        p.mo[row + k] = (float)((double)c0 + delta);
+        p.mo[half + row + k] = (float)((double)u0 + delta);
+    } else {
+        p.mo[row + k] = (float)((double)p.mo[row + k] + delta);
+    }
+}
+
 __global__ __launch_bounds__(256) void steer_boxes_kernel(const SteerArgs p) {
     __shared__ double red[4];
     __shared__ double lo[STEER_MAXN][3], hi[STEER_MAXN][3];                                   // 7.5 KB
     __shared__ float valid[STEER_MAXN];
-    const int b = blockIdx.x, tid = threadIdx.x, N = p.n, C = p.c;
-    const bool first = tid == 0;
-    const bool is_x0 = p.mean_type == DSC_MEAN_X0;
-    int64_t tv;
-    if (p.t) tv = dsc_checked_index(p.t[b], p.T, first);
-    else tv = dsc_checked_index(p.times[dsc_checked_index(p.step[0], p.S, first && b == 0)], p.T, first && b == 0);
-    int64_t cnt = 0;
-    if (p.counts) cnt = dsc_checked_index(p.counts[b], (int64_t)p.pmax + 1, first);
-    const float w = p.weight[b];
-    const bool active = w != 0.f && tv < p.t_below[0];
-    if (!active && !p.energy && !p.grad) return;                                             // the whole block: nothing is stored
-    const float A = is_x0 ? 0.f : p.ca[tv], Bc = is_x0 ? 0.f : p.cb[tv];
-    const float s = p.scale ? p.scale[b] : 0.f;
-    const int64_t base = (int64_t)b * N * C, half = (int64_t)p.b * N * C;
-    const int64_t row = base + (int64_t)tid * C;
+    const int b = blockIdx.x, tid = threadIdx.x, N = p.n;
+    const SteerScene f = steer_scene(p, b, tid);
+    if (!f.active && !p.energy && !p.grad) return;                                           // the whole block: nothing is stored
     double li[3] = {0., 0., 0.}, hi_i[3] = {0., 0., 0.};
-    float raw[3] = {0.f, 0.f, 0.f}, x0c[3] = {0.f, 0.f, 0.f};
-    bool is_free[3] = {false, false, false}, ok = false;
+    SteerRow r{};
+    bool ok = false;
     if (tid < N) {
-        const bool row_given = p.counts && tid < cnt;
-        const int64_t grow = ((int64_t)b * p.pmax + tid) * C;
-        float v[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int ch = k < 8 ? k : p.empty_col;
-            const bool given = row_given || (p.mask && p.mask[row + ch] != 0);
-            if (given) {
-                v[k] = row_given ? p.partial[grow + ch] : p.known[row + ch];
-            } else {
-                float m = p.mo[row + ch];
-                if (p.scale) m = cfg_mix(m, p.mo[half + row + ch], s);
-                const float r = predict_x0(is_x0 ? 0.f : p.xt[row + ch], m, A, Bc, p.mean_type, false);
-                v[k] = fminf(fmaxf(r, -1.0f), 1.0f);
-                if (k < 3) raw[k] = r, x0c[k] = v[k];
-            }
-            if (k < 3) is_free[k] = !given;
-        }
+        r = steer_x0_row(p, f, b, tid);
+        const float* v = r.v;
         double ctr[3], sz[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -287,25 +336,10 @@ __global__ __launch_bounds__(256) void steer_boxes_kernel(const SteerArgs p) {
         }
     }
     const double E = block_sum_steer(e, red);
-    if (p.energy && first) p.energy[b] = (float)E;
+    if (p.energy && tid == 0) p.energy[b] = (float)E;
     if (tid >= N) return;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double gn = g[k] * p.c_span[k] * 0.5;                                           // d centre / d x0 = span / 2
-        if (p.grad) p.grad[((int64_t)b * N + tid) * 3 + k] = (float)gn;
-        if (!active || !ok || !is_free[k]) continue;
-        const double wg = (double)w * gn;
-        if (wg == 0. || (!is_x0 && Bc == 0.f)) continue;
-        const double d = wg + ((double)raw[k] - (double)x0c[k]);
-        const double delta = is_x0 ? -d : d / (double)Bc;
-        if (p.scale) {
-            const float c0 = p.mo[row + k], u0 = p.mo[half + row + k];
-            p.mo[row + k] = (float)((double)c0 + delta);
-            p.mo[half + row + k] = (float)((double)u0 + delta);
-        } else {
-            p.mo[row + k] = (float)((double)p.mo[row + k] + delta);
-        }
-    }
+    for (int k = 0; k < 3; ++k) steer_store(p, f, r, b, tid, k, g[k], ok);
 }
 
 // Floor-plan steering, the field: once per call, never inside the loop.  The mask image (h rows along z, w columns
@@ -366,60 +400,24 @@ __global__ __launch_bounds__(256) void floor_field_kernel(const float* __restric
 // float64 after the float32 x0 and the float32 field, one final rounding.  An inactive launch without optional outputs returns before
 // it reads the scene.  field_b == 1: one field shared by every scene.  room_side is read through its pointer, as weight and t_below.
 struct WallArgs {
-    const float* xt; float* mo;
-    const int64_t *t, *step, *times;
-    const float *ca, *cb, *partial;
-    const int64_t* counts;
-    const float* known;
-    const uint8_t* mask;
-    const float *scale, *weight;
-    const int64_t* t_below;
+    SteerArgs s;
     const float *field, *room_side;
-    float *energy, *grad;
     int32_t* outside;
-    int mean_type, b, n, pmax, c, empty_col, S, T, field_b, h, w;
-    double c_lo[3], c_span[3], s_lo[3], s_span[3];
+    int field_b, h, w;
 };
 
-__global__ __launch_bounds__(256) void steer_walls_kernel(const WallArgs p) {
+__global__ __launch_bounds__(256) void steer_walls_kernel(const WallArgs q) {
     __shared__ double red[4];
-    const int b = blockIdx.x, tid = threadIdx.x, N = p.n, C = p.c, H = p.h, W = p.w;
-    const bool first = tid == 0;
-    const bool is_x0 = p.mean_type == DSC_MEAN_X0;
-    int64_t tv;
-    if (p.t) tv = dsc_checked_index(p.t[b], p.T, first);
-    else tv = dsc_checked_index(p.times[dsc_checked_index(p.step[0], p.S, first && b == 0)], p.T, first && b == 0);
-    int64_t cnt = 0;
-    if (p.counts) cnt = dsc_checked_index(p.counts[b], (int64_t)p.pmax + 1, first);
-    const float w = p.weight[b];
-    const bool active = w != 0.f && tv < p.t_below[0];
-    if (!active && !p.energy && !p.grad && !p.outside) return;                               // the whole block: nothing is stored
-    const float A = is_x0 ? 0.f : p.ca[tv], Bc = is_x0 ? 0.f : p.cb[tv];
-    const float s = p.scale ? p.scale[b] : 0.f;
-    const int64_t base = (int64_t)b * N * C, half = (int64_t)p.b * N * C;
-    const int64_t row = base + (int64_t)tid * C;
-    float raw[3] = {0.f, 0.f, 0.f}, x0c[3] = {0.f, 0.f, 0.f};
-    bool is_free[3] = {false, false, false}, ok = false;
+    const SteerArgs& p = q.s;
+    const int b = blockIdx.x, tid = threadIdx.x, N = p.n, H = q.h, W = q.w;
+    const SteerScene f = steer_scene(p, b, tid);
+    if (!f.active && !p.energy && !p.grad && !q.outside) return;                             // the whole block: nothing is stored
+    SteerRow r{};
+    bool ok = false;
     double g[3] = {0., 0., 0.}, e = 0., out = 0.;
     if (tid < N) {
-        const bool row_given = p.counts && tid < cnt;
-        const int64_t grow = ((int64_t)b * p.pmax + tid) * C;
-        float v[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-            const int ch = k < 8 ? k : p.empty_col;
-            const bool given = row_given || (p.mask && p.mask[row + ch] != 0);
-            if (given) {
-                v[k] = row_given ? p.partial[grow + ch] : p.known[row + ch];
-            } else {
-                float m = p.mo[row + ch];
-                if (p.scale) m = cfg_mix(m, p.mo[half + row + ch], s);
-                const float r = predict_x0(is_x0 ? 0.f : p.xt[row + ch], m, A, Bc, p.mean_type, false);
-                v[k] = fminf(fmaxf(r, -1.0f), 1.0f);
-                if (k < 3) raw[k] = r, x0c[k] = v[k];
-            }
-            if (k < 3) is_free[k] = !given;
-        }
+        r = steer_x0_row(p, f, b, tid);
+        const float* v = r.v;
         ok = v[8] < 0.f;
         if (ok) {
             const double cx = ((double)v[0] + 1.0) * 0.5 * p.c_span[0] + p.c_lo[0];
@@ -430,11 +428,11 @@ __global__ __launch_bounds__(256) void steer_walls_kernel(const WallArgs p) {
             const double hyp = sqrt(cs * cs + sn * sn);
             double rc = 1.0, rsn = 0.0;
             if (hyp > 0.) rc = cs / hyp, rsn = sn / hyp;
-            const double side = (double)p.room_side[0];
+            const double side = (double)q.room_side[0];
             const double dx = 2.0 * side / (double)W, dz = 2.0 * side / (double)H;
             const double rdx = 1.0 / dx, rdz = 1.0 / dz;                                      // a float64 division is a long serial chain: two per box
             const double umax = (double)(W - 1), vmax = (double)(H - 1);
-            const float* F = p.field + (p.field_b == 1 ? 0 : (int64_t)b * H * W);
+            const float* F = q.field + (q.field_b == 1 ? 0 : (int64_t)b * H * W);
             double esum = 0., gx = 0., gz = 0.;
             bool any = false;
             for (int a = -1; a <= 1; ++a) {
@@ -468,26 +466,12 @@ __global__ __launch_bounds__(256) void steer_walls_kernel(const WallArgs p) {
     }
     const double E = block_sum_steer(e, red);
     const double O = block_sum_steer(out, red);
-    if (p.energy && first) p.energy[b] = (float)E;
-    if (p.outside && first) p.outside[b] = (int32_t)O;
+    if (p.energy && tid == 0) p.energy[b] = (float)E;
+    if (q.outside && tid == 0) q.outside[b] = (int32_t)O;
     if (tid >= N) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double gn = g[k] * p.c_span[k] * 0.5;                                           // d centre / d x0 = span / 2
-        if (p.grad) p.grad[((int64_t)b * N + tid) * 3 + k] = (float)gn;
-        if (k == 1 || !active || !ok || !is_free[k]) continue;
-        const double wg = (double)w * gn;
-        if (wg == 0. || (!is_x0 && Bc == 0.f)) continue;
-        const double d = wg + ((double)raw[k] - (double)x0c[k]);
-        const double delta = is_x0 ? -d : d / (double)Bc;
-        if (p.scale) {
-            const float c0 = p.mo[row + k], u0 = p.mo[half + row + k];
-            p.mo[row + k] = (float)((double)c0 + delta);
-            p.mo[half + row + k] = (float)((double)u0 + delta);
-        } else {
-            p.mo[row + k] = (float)((double)p.mo[row + k] + delta);
-        }
-    }
+    steer_store(p, f, r, b, tid, 0, g[0], ok);
+    steer_store(p, f, r, b, tid, 1, g[1], false);                                            // y: the zero gradient is reported, never applied
+    steer_store(p, f, r, b, tid, 2, g[2], ok);
 }
 
 // Which elements of a scene are given (completion, in-painting) instead of sampled: none, the first counts[b] rows, or a byte mask.
@@ -1167,12 +1151,12 @@ extern "C" int dsc_ddim_masked_cfg_step_f32(const float* x_t, const float* model
     return launch_step<true, GIVEN_MASK, true>(a, stream);
 }
 
-extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
-                                   const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
-                                   const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
-                                   const float* bounds, float* energy_out, float* grad_out, int32_t mean_type, int32_t b, int32_t n,
-                                   int32_t pmax, int32_t c, int32_t bbox_dim, int32_t class_dim, int32_t num_steps,
-                                   int32_t num_timesteps, dsc_stream_t stream) {
+// The checks and operands both steering launches share: DSC_EINVAL cases first, then DSC_ERANGE.
+static int fill_steer_args(SteerArgs& p, const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                           const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                           const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below, const float* bounds,
+                           float* energy_out, float* grad_out, int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c,
+                           int32_t bbox_dim, int32_t class_dim, int32_t num_steps, int32_t num_timesteps) {
     if (!model_out || !weight || !t_below || !bounds || b < 1 || n < 1 || c < 1 || num_timesteps < 1) return DSC_EINVAL;
     if (t ? step || times : !step || !times || num_steps < 1) return DSC_EINVAL;            // one time source
     if (bad_mean_args(mean_type, ca, cb) || (mean_type != DSC_MEAN_X0 && !x_t)) return DSC_EINVAL;
@@ -1180,7 +1164,6 @@ extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int
     if (partial && (pmax < 1 || pmax > n)) return DSC_EINVAL;
     if (class_dim < 1 || bbox_dim < 1 || bbox_dim + class_dim > c) return DSC_EINVAL;        // a re-arrangement sub-shape has no such layout
     if (bbox_dim != 8 || n > STEER_MAXN) return DSC_ERANGE;                                  // [translation 3 | size 3 | cos, sin]
-    SteerArgs p{};
     p.xt = x_t, p.mo = model_out, p.t = t, p.step = step, p.times = times, p.ca = ca, p.cb = cb;
     p.partial = partial, p.counts = counts, p.known = known, p.mask = mask, p.scale = cfg_scale, p.weight = weight, p.t_below = t_below;
     p.energy = energy_out, p.grad = grad_out;
@@ -1190,6 +1173,20 @@ extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int
         p.c_lo[k] = bounds[k], p.c_span[k] = (double)bounds[3 + k] - (double)bounds[k];
         p.s_lo[k] = bounds[6 + k], p.s_span[k] = (double)bounds[9 + k] - (double)bounds[6 + k];
     }
+    return 0;
+}
+
+extern "C" int dsc_steer_boxes_f32(const float* x_t, float* model_out, const int64_t* t, const int64_t* step, const int64_t* times,
+                                   const float* ca, const float* cb, const float* partial, const int64_t* counts, const float* known,
+                                   const uint8_t* mask, const float* cfg_scale, const float* weight, const int64_t* t_below,
+                                   const float* bounds, float* energy_out, float* grad_out, int32_t mean_type, int32_t b, int32_t n,
+                                   int32_t pmax, int32_t c, int32_t bbox_dim, int32_t class_dim, int32_t num_steps,
+                                   int32_t num_timesteps, dsc_stream_t stream) {
+    SteerArgs p{};
+    if (const int rc = fill_steer_args(p, x_t, model_out, t, step, times, ca, cb, partial, counts, known, mask, cfg_scale, weight, t_below,
+                                       bounds, energy_out, grad_out, mean_type, b, n, pmax, c, bbox_dim, class_dim, num_steps,
+                                       num_timesteps))
+        return rc;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(steer_boxes_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     DSC_LAUNCH_CHECK();
@@ -1213,26 +1210,15 @@ extern "C" int dsc_steer_walls_f32(const float* x_t, float* model_out, const int
                                    int32_t* outside_out, int32_t mean_type, int32_t b, int32_t n, int32_t pmax, int32_t c,
                                    int32_t bbox_dim, int32_t class_dim, int32_t num_steps, int32_t num_timesteps, int32_t field_b,
                                    int32_t h, int32_t w, dsc_stream_t stream) {
-    if (!model_out || !weight || !t_below || !bounds || !field || !room_side || b < 1 || n < 1 || c < 1 || num_timesteps < 1)
-        return DSC_EINVAL;
-    if (t ? step || times : !step || !times || num_steps < 1) return DSC_EINVAL;            // one time source
-    if (bad_mean_args(mean_type, ca, cb) || (mean_type != DSC_MEAN_X0 && !x_t)) return DSC_EINVAL;
-    if ((partial != nullptr) != (counts != nullptr) || (known != nullptr) != (mask != nullptr) || (partial && known)) return DSC_EINVAL;
-    if (partial && (pmax < 1 || pmax > n)) return DSC_EINVAL;
-    if (class_dim < 1 || bbox_dim < 1 || bbox_dim + class_dim > c) return DSC_EINVAL;        // a re-arrangement sub-shape has no such layout
-    if (field_b != 1 && field_b != b) return DSC_EINVAL;
-    if (bbox_dim != 8 || n > STEER_MAXN) return DSC_ERANGE;                                  // [translation 3 | size 3 | cos, sin]
-    if (h < 2 || w < 2 || h > WALL_MAXHW || w > WALL_MAXHW) return DSC_ERANGE;
+    // Its own DSC_EINVAL cases come before the shared DSC_ERANGE ones, its own DSC_ERANGE cases after.
+    if (!field || !room_side || (field_b != 1 && field_b != b)) return DSC_EINVAL;
     WallArgs p{};
-    p.xt = x_t, p.mo = model_out, p.t = t, p.step = step, p.times = times, p.ca = ca, p.cb = cb;
-    p.partial = partial, p.counts = counts, p.known = known, p.mask = mask, p.scale = cfg_scale, p.weight = weight, p.t_below = t_below;
-    p.field = field, p.room_side = room_side, p.energy = energy_out, p.grad = grad_out, p.outside = outside_out;
-    p.mean_type = mean_type, p.b = b, p.n = n, p.pmax = partial ? pmax : 0, p.c = c, p.empty_col = bbox_dim + class_dim - 1;
-    p.S = t ? 0 : num_steps, p.T = num_timesteps, p.field_b = field_b, p.h = h, p.w = w;
-    for (int k = 0; k < 3; ++k) {
-        p.c_lo[k] = bounds[k], p.c_span[k] = (double)bounds[3 + k] - (double)bounds[k];
-        p.s_lo[k] = bounds[6 + k], p.s_span[k] = (double)bounds[9 + k] - (double)bounds[6 + k];
-    }
+    if (const int rc = fill_steer_args(p.s, x_t, model_out, t, step, times, ca, cb, partial, counts, known, mask, cfg_scale, weight,
+                                       t_below, bounds, energy_out, grad_out, mean_type, b, n, pmax, c, bbox_dim, class_dim, num_steps,
+                                       num_timesteps))
+        return rc;
+    if (h < 2 || w < 2 || h > WALL_MAXHW || w > WALL_MAXHW) return DSC_ERANGE;
+    p.field = field, p.room_side = room_side, p.outside = outside_out, p.field_b = field_b, p.h = h, p.w = w;
     DSC_CLEAR_STALE_ERROR();
     hipLaunchKernelGGL(steer_walls_kernel, dim3(b), dim3(256), 0, static_cast<hipStream_t>(stream), p);
     DSC_LAUNCH_CHECK();

@@ -18,10 +18,9 @@ each a generator of states (x_T, then the state after every step), and two indep
   the given part   _FREE (nothing), _GivenRows / _GivenRagged (a dense / ragged row prefix), _GivenMask (a byte mask): drawn for and
                    written over the state in place BEFORE every model call, restored in the last state; x_T is cloned only if it is
                    written
-  the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine); under ``collision_scale`` _steered wraps either:
-                   the model call, collision steering of its output in place (dsc_steer_boxes_f32), then the guidance mix
-                   under ``wall_scale`` _walled wraps any of them: floor-plan steering (dsc_steer_walls_f32) at the head of the ``post``
-                   hook of the model call -- after the collision steering, before the solver's launch and the guidance mix
+  the model call   _model (plain) or _guided_model (the denoiser at 2 B, then cfg_combine); under ``collision_scale`` / ``wall_scale``
+                   _corrected hands either one a ``post`` hook that issues, on the output in place and before the guidance mix, collision
+                   steering (dsc_steer_boxes_f32), floor-plan steering (dsc_steer_walls_f32), then the solver's launch
   the solver       ``sampling_solver="dpmpp_2m"`` (strided loops): _strided_states hands the model call a ``post`` hook that issues
                    dsc_multistep_x0_f32 on the (steered) output, before the guidance mix, on every pair but the last; the step is unchanged
 A ``noise_fn`` that is a scene_noise.SceneNoise (per-scene seeds) is armed by the core it runs under -- told whether the loop has a given
@@ -193,53 +192,36 @@ def _guided_model(denoise_fn, cond2, cross2, scale):
     return call
 
 
-def _steered(model, diff, device, steer, part, scale=None):
-    """The model call of a steered loop: ``model`` -- under guidance the denoiser at 2 B, ``scale`` its (B,) scales --, then collision
-    steering of its output in place (dsc_steer_boxes_f32), [``post`` on the steered output,] then the guidance mix: the launches of the
-    captured loop, in its order."""
-    weight, k, bounds, bbox_dim, class_dim = steer
+def _corrected(model, diff, device, part, scale=None, steer=None, walls=None):
+    """The model call of a loop under steering: ``model`` -- _model or, with its (B,) ``scale``, _guided_model -- with the corrections of
+    its output issued in place through the ``post`` hook, in the order of the captured loop: collision steering (dsc_steer_boxes_f32,
+    ``steer`` of _steer_inputs), floor-plan steering (dsc_steer_walls_f32, ``walls`` of _wall_inputs), then the caller's ``post`` (the
+    multistep launch); under guidance on the 2 B output, before the mix."""
     ca, cb = diff._coeffs(diff.tables(device))
-    spec = (weight, torch.full((1,), k, device=device, dtype=torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim)
+    one = lambda v, dtype: torch.full((1,), v, device=device, dtype=dtype)  # noqa: E731
+    recs = []
+    if steer is not None:
+        weight, k, bounds, bbox_dim, class_dim = steer
+        recs.append(("steer_rec", (weight, one(k, torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim)))
+    if walls is not None:
+        weight, k, bounds, bbox_dim, class_dim, field, room_side = walls
+        recs.append(("walls_rec", (weight, one(k, torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim, field,
+                                   one(room_side, torch.float32))))
 
     def call(x, t_, post=None):
-        mo = model(x, t_).contiguous()
-        ops.issue(ops.steer_rec(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale, **part.steer_operands()))
-        if post is not None:
-            post(x, mo)
-        return mo if scale is None else ops.cfg_combine(mo, scale)
+        def corrections(x, mo):
+            for rec, spec in recs:
+                ops.issue(getattr(ops, rec)(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale,
+                                            **part.steer_operands()))
+            if post is not None:
+                post(x, mo)
+        return model(x, t_, corrections)
     return call
 
 
 def _steer_kw(collision_scale, collision_steps):
     """The steering keyword a public loop hands to _loop: none at all without it, so that call stays what it was."""
     return {} if collision_scale is None and collision_steps is None else dict(steer=(collision_scale, collision_steps))
-
-
-def _walled(model, diff, device, walls, part, scale=None):
-    """The model call of a loop under floor-plan steering: ``model`` -- any of the calls above -- with one more launch
-    (dsc_steer_walls_f32) at the head of its ``post`` hook: on the output after collision steering, before the multistep launch and the
-    guidance mix, the place it has in the captured loop.  ``scale``: the (B,) guidance scales of a guided ``model``."""
-    weight, k, bounds, bbox_dim, class_dim, field, room_side = walls
-    ca, cb = diff._coeffs(diff.tables(device))
-    spec = (weight, torch.full((1,), k, device=device, dtype=torch.int64), ops.steer_bounds(bounds), bbox_dim, class_dim, field,
-            torch.full((1,), room_side, device=device, dtype=torch.float32))
-
-    def call(x, t_, post=None):
-        def walls_then(x, mo):
-            ops.issue(ops.walls_rec(x.contiguous(), mo, _MEAN[diff.model_mean_type], (ca, cb), spec, t=t_, scale=scale,
-                                    **part.steer_operands()))
-            if post is not None:
-                post(x, mo)
-        return model(x, t_, walls_then)
-    return call
-
-
-def _renamed_bounds(diff):
-    """box_bounds of ``diff`` with the floor-plan keyword in its refusal."""
-    try:
-        return diff.box_bounds()
-    except ValueError as e:
-        raise ValueError(str(e).replace("collision_scale", "wall_scale")) from None
 
 
 def _wall_kw(wall_scale, wall_steps, room_side, room_mask):
@@ -676,15 +658,9 @@ class GaussianDiffusion:
                          **({} if walls is None else dict(walls=walls)), **jump_kw)
         part = _FREE if kind is None else {"dense": _GivenRows, "ragged": _GivenRagged, "mask": _GivenMask}[kind](
             self, device, noise_fn, *((shape,) if kind == "mask" else ()), *values)
-        if steer is None:
-            model = _model(denoise_fn, condition, condition_cross) if scale is None else _guided_model(denoise_fn, condition, condition_cross, scale)
-        elif scale is None:
-            model = _steered(_model(denoise_fn, condition, condition_cross), self, device, steer, part)
-        else:                                   # the denoiser at 2 B, steered with the scales, then mixed
-            model = _steered(lambda x, t_: denoise_fn(torch.cat([x, x], dim=0), torch.cat([t_, t_]), condition, condition_cross),
-                             self, device, steer, part, scale)
-        if walls is not None:
-            model = _walled(model, self, device, walls, part, scale)
+        model = _model(denoise_fn, condition, condition_cross) if scale is None else _guided_model(denoise_fn, condition, condition_cross, scale)
+        if steer is not None or walls is not None:
+            model = _corrected(model, self, device, part, scale, steer, walls)
         if strided is not None:
             states = self._strided_states(model, shape, device, noise_fn, S, eta, part,
                                           *(() if multistep is None else ((scale,),)), **jump_kw)
@@ -858,17 +834,18 @@ class GaussianDiffusion:
         return cond2, cross2, scale
 
     # ------------------------------------------------------------------ collision steering
-    def box_bounds(self):
+    def box_bounds(self, keyword="collision_scale"):
         """The de-normalisation bounds of the boxes, 12 floats (translation lo[3], hi[3], size lo[3], hi[3]), from the train-stats file
-        (``bounds_translations`` / ``bounds_sizes``); loaded on first use whether or not ``loss_iou`` is set."""
+        (``bounds_translations`` / ``bounds_sizes``); loaded on first use whether or not ``loss_iou`` is set.  ``keyword``: the one a
+        refusal names."""
         hit = getattr(self, "_box_bounds", None)
         if hit is None:
             if self.loss_iou:
                 c, s = np.concatenate(self._centroids), np.concatenate(self._sizes)
             else:
                 if not self.train_stats_file:
-                    raise ValueError("collision_scale needs the de-normalisation bounds of the boxes: set train_stats_file "
-                                     "(diffusion_kwargs) to the dataset's statistics file")
+                    raise ValueError("%s needs the de-normalisation bounds of the boxes: set train_stats_file "
+                                     "(diffusion_kwargs) to the dataset's statistics file" % keyword)
                 with open(self.train_stats_file, "r") as f:
                     train_stats = json.load(f)
                 c, s = train_stats["bounds_translations"], train_stats["bounds_sizes"]
@@ -877,6 +854,18 @@ class GaussianDiffusion:
                 raise ValueError("train_stats_file: bounds_translations and bounds_sizes must hold 6 numbers each")
         return hit
 
+    def _check_steer_layout(self, shape, noun, what):
+        """The refusals every steering term shares: it reads boxes in the full object layout, one thread per box."""
+        B, N, C = shape
+        if (self.translation_dim, self.size_dim, self.angle_dim) != (3, 3, 2):
+            raise ValueError("%s: %s needs translation_dim = 3, size_dim = 3 and angle_dim = 2 (cos, sin), got %d / %d / %d"
+                             % (what, noun, self.translation_dim, self.size_dim, self.angle_dim))
+        if self.class_dim < 1 or C < self.bbox_dim + self.class_dim:
+            raise ValueError("%s: %s needs the full object layout, at least %d channels, got %d"
+                             % (what, noun, self.bbox_dim + max(self.class_dim, 1), C))
+        if N > ops.STEER_MAX_OBJECTS:
+            raise ValueError("%s: %s handles at most %d objects per scene, got %d" % (what, noun, ops.STEER_MAX_OBJECTS, N))
+
     def _steer_inputs(self, shape, device, collision_scale, collision_steps, what):
         """(weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim) of a steered loop (ops.steer_rec), or ValueError -- before
         anything is drawn.  At every step whose t < K the clamped x0 estimate of scene b moves by -weight[b] * d E / d x0[:, 0:3], E the
@@ -884,14 +873,7 @@ class GaussianDiffusion:
         B, N, C = shape
         if collision_scale is None:
             raise ValueError("%s: collision_steps goes with collision_scale" % what)
-        if (self.translation_dim, self.size_dim, self.angle_dim) != (3, 3, 2):
-            raise ValueError("%s: collision steering needs translation_dim = 3, size_dim = 3 and angle_dim = 2 (cos, sin), got %d / %d / %d"
-                             % (what, self.translation_dim, self.size_dim, self.angle_dim))
-        if self.class_dim < 1 or C < self.bbox_dim + self.class_dim:
-            raise ValueError("%s: collision steering needs the full object layout, at least %d channels, got %d"
-                             % (what, self.bbox_dim + max(self.class_dim, 1), C))
-        if N > ops.STEER_MAX_OBJECTS:
-            raise ValueError("%s: collision steering handles at most %d objects per scene, got %d" % (what, ops.STEER_MAX_OBJECTS, N))
+        self._check_steer_layout(shape, "collision steering", what)
         weight = ops.collision_scales(collision_scale, B, "cpu")
         k = ops.collision_steps(collision_steps, self.num_timesteps)
         return weight.to(device), k, self.box_bounds(), self.bbox_dim, self.class_dim
@@ -911,18 +893,10 @@ class GaussianDiffusion:
         if room_mask is None:
             raise ValueError("%s: wall_scale needs the room_mask" % what)
         ops.room_mask_dims(room_mask, B)
-        if (self.translation_dim, self.size_dim, self.angle_dim) != (3, 3, 2):
-            raise ValueError("%s: floor-plan steering needs translation_dim = 3, size_dim = 3 and angle_dim = 2 (cos, sin), got %d / %d / %d"
-                             % (what, self.translation_dim, self.size_dim, self.angle_dim))
-        if self.class_dim < 1 or C < self.bbox_dim + self.class_dim:
-            raise ValueError("%s: floor-plan steering needs the full object layout, at least %d channels, got %d"
-                             % (what, self.bbox_dim + max(self.class_dim, 1), C))
-        if N > ops.STEER_MAX_OBJECTS:
-            raise ValueError("%s: floor-plan steering handles at most %d objects per scene, got %d" % (what, ops.STEER_MAX_OBJECTS, N))
+        self._check_steer_layout(shape, "floor-plan steering", what)
         weight = ops.wall_scales(wall_scale, B, "cpu")
         k = ops.wall_steps(wall_steps, self.num_timesteps)
-        bounds = _renamed_bounds(self)
-        return (weight.to(device), k, bounds, self.bbox_dim, self.class_dim,
+        return (weight.to(device), k, self.box_bounds("wall_scale"), self.bbox_dim, self.class_dim,
                 ops.floor_field(room_mask.to(device), side) if field else None, side)
 
     @torch.no_grad()

@@ -341,9 +341,8 @@ class DiffusionSceneLayout_DDPM(Module):
         self._check_room(room_mask, batch_size)
         if guidance_scale is not None:
             self._check_guidance(text, partial_boxes, input_boxes, ret_traj)
-        steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, ret_traj)
-        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
-                                       (batch_size, num_points, point_dim), input_boxes, ret_traj))
+        steer = self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                                     (batch_size, num_points, point_dim), input_boxes, ret_traj)
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta)
         if sampling_timesteps is not None and (partial_boxes is not None or input_boxes is not None):
             raise NotImplementedError("sampling_timesteps (DDIM) is defined for generation only: scene completion and "
@@ -395,15 +394,26 @@ class DiffusionSceneLayout_DDPM(Module):
         return self.diffusion.gen_samples(noise.shape, device, condition=condition, condition_cross=condition_cross,
                                           clip_denoised=clip_denoised, **seeded, **steer)
 
+    def _check_steering(self, collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask, shape, input_boxes=None,
+                        ret_traj=False, what="sample"):
+        """_check_steer and _check_walls -> the steering keywords the loop receives."""
+        steer = self._check_steer(collision_scale, collision_steps, shape, input_boxes, ret_traj, what)
+        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, shape, input_boxes, ret_traj, what))
+        return steer
+
+    def _refuse_steering(self, keyword, input_boxes, ret_traj):
+        """Where no steering term applies: re-arrangement and trajectories."""
+        if input_boxes is not None or self.room_arrange_condition:
+            raise ValueError("%s: re-arrangement diffuses [translation | angle] only, the boxes are not steered there" % keyword)
+        if ret_traj:
+            raise ValueError("%s: the steered loops return the final scenes only (ret_traj is not supported)" % keyword)
+
     def _check_steer(self, collision_scale, collision_steps, shape, input_boxes=None, ret_traj=False, what="sample"):
         """The refusals of ``collision_scale`` / ``collision_steps``, before anything is computed or drawn -> the keywords the loop
         receives: none at all without steering, so that call stays what it was."""
         if collision_scale is None and collision_steps is None:
             return {}
-        if input_boxes is not None or self.room_arrange_condition:
-            raise ValueError("collision_scale: re-arrangement diffuses [translation | angle] only, the boxes are not steered there")
-        if ret_traj:
-            raise ValueError("collision_scale: the steered loops return the final scenes only (ret_traj is not supported)")
+        self._refuse_steering("collision_scale", input_boxes, ret_traj)
         self.diffusion.diffusion._steer_inputs(tuple(int(v) for v in shape), "cpu", collision_scale, collision_steps, what)
         return dict(collision_scale=collision_scale, collision_steps=collision_steps)
 
@@ -412,10 +422,7 @@ class DiffusionSceneLayout_DDPM(Module):
         receives (the room mask among them): none at all without floor-plan steering, so that call stays what it was."""
         if wall_scale is None and wall_steps is None and room_side is None:
             return {}
-        if input_boxes is not None or self.room_arrange_condition:
-            raise ValueError("wall_scale: re-arrangement diffuses [translation | angle] only, the boxes are not steered there")
-        if ret_traj:
-            raise ValueError("wall_scale: the steered loops return the final scenes only (ret_traj is not supported)")
+        self._refuse_steering("wall_scale", input_boxes, ret_traj)
         self.diffusion.diffusion._wall_inputs(tuple(int(v) for v in shape), "cpu", wall_scale, wall_steps, room_side, room_mask, what,
                                               field=False)
         return dict(wall_scale=wall_scale, wall_steps=wall_steps, room_side=room_side, room_mask=room_mask)
@@ -544,8 +551,8 @@ class DiffusionSceneLayout_DDPM(Module):
         self._check_room(room_mask, batch_size, "complete_scene")
         if jumps and sampling_timesteps is None:                  # sample() does not take the keyword: the T-step call of complete_scene_batched
             shape = (batch_size, num_points, point_dim)
-            steer = self._check_steer(collision_scale, collision_steps, shape, what="complete_scene")
-            steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, shape, what="complete_scene"))
+            steer = self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                                         shape, what="complete_scene")
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
             samples = self._complete_tstep(room_mask, num_points, point_dim, padded, counts, batch_size, clip_denoised, seeded, steer, jumps,
@@ -553,9 +560,8 @@ class DiffusionSceneLayout_DDPM(Module):
             return self.delete_empty_from_network_samples(samples, device=device, keep_empty=keep_empty)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
-            steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene")
-            steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
-                                           (batch_size, num_points, point_dim), what="complete_scene"))
+            steer = self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                                         (batch_size, num_points, point_dim), what="complete_scene")
             seeded = self._seeded(scene_seeds, batch_seeds, batch_size, room_mask.device)
             padded, counts = self._ragged_partial(partial_boxes, None, batch_size, num_points, point_dim, room_mask.device)
             samples = self._complete_strided(room_mask, num_points, point_dim, padded, counts, batch_size, S, eta, seeded, steer, solver,
@@ -575,9 +581,8 @@ class DiffusionSceneLayout_DDPM(Module):
         """reference :342-347.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead of the T-step loop.
         ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
         ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
-        self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
-        self._check_walls(wall_scale, wall_steps, room_side, room_mask,
-                          (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
+        self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                             (batch_size, num_points, point_dim), input_boxes, what="arrange_scene")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene")
         self._check_room(room_mask, batch_size, "arrange_scene")
         if sampling_timesteps is not None:
@@ -733,9 +738,8 @@ class DiffusionSceneLayout_DDPM(Module):
         jumps = self._check_resample(resample, resample_steps, sampling_solver, False, "complete_scene_batched")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "complete_scene_batched")
         self._check_room(room_mask, batch_size, "complete_scene_batched")
-        steer = self._check_steer(collision_scale, collision_steps, (batch_size, num_points, point_dim), what="complete_scene_batched")
-        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask,
-                                       (batch_size, num_points, point_dim), what="complete_scene_batched"))
+        steer = self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                                     (batch_size, num_points, point_dim), what="complete_scene_batched")
         seeded = self._seeded(scene_seeds, batch_seeds, batch_size, device)
         if sampling_timesteps is not None:
             S, eta = self._check_strided(sampling_timesteps, ddim_sampling_eta)
@@ -770,9 +774,8 @@ class DiffusionSceneLayout_DDPM(Module):
         each post-filtered on its own.  ``sampling_timesteps=S`` runs ``arrange_samples_ddim`` (S strided steps) instead.
         ``collision_scale`` / ``collision_steps`` are refused (ValueError): the loop diffuses [translation | angle] only.
         ``sampling_solver``: "dpmpp_2m" with ``sampling_timesteps`` (see ``sample``)."""
-        self._check_steer(collision_scale, collision_steps, (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
-        self._check_walls(wall_scale, wall_steps, room_side, room_mask,
-                          (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
+        self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                             (1, num_points, point_dim), input_boxes, what="arrange_scene_batched")
         solver = self._check_solver(sampling_solver, sampling_timesteps, ddim_sampling_eta, "arrange_scene_batched")
         if not isinstance(input_boxes, torch.Tensor) or input_boxes.dim() != 3:
             raise ValueError("input_boxes must be a (B, %d, %d) tensor" % (num_points, point_dim))
@@ -885,8 +888,8 @@ class DiffusionSceneLayout_DDPM(Module):
         B, N, C = int(batch_size), int(num_points), int(point_dim)
         self._check_room(room_mask, B, "inpaint_scene_batched")
         scale = None if guidance_scale is None else ops.guidance_scales(guidance_scale, B, "cpu")   # checked on the host; the loop uploads it
-        steer = self._check_steer(collision_scale, collision_steps, (B, N, C), what="inpaint_scene_batched")
-        steer.update(self._check_walls(wall_scale, wall_steps, room_side, room_mask, (B, N, C), what="inpaint_scene_batched"))
+        steer = self._check_steering(collision_scale, collision_steps, wall_scale, wall_steps, room_side, room_mask,
+                                     (B, N, C), what="inpaint_scene_batched")
         seeded = self._seeded(scene_seeds, batch_seeds, B, device)
         if isinstance(boxes, (list, tuple)):
             if len(boxes) != B:

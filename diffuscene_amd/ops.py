@@ -701,11 +701,16 @@ def guidance_scales(scale, b, device):
     """The per-scene guidance scales of the guided kernels as a contiguous (b,) f32 tensor on ``device``.  ``scale``: a float (every
     scene), or a length-b sequence / 1-d tensor (one scale per scene).  ValueError on NaN / inf, on a wrong length and on anything that
     is not a number."""
+    return _scene_scales(scale, b, device, "guidance_scale")
+
+
+def _scene_scales(scale, b, device, name, weights=False):
+    """guidance_scales under the keyword ``name`` of its messages; ``weights``: steering weights, which also refuse a value below 0."""
     b = int(b)
-    bad = "guidance_scale must be a number or a sequence of %d numbers, got %r" % (b, scale)
+    bad = "%s must be a number or a sequence of %d numbers, got %r" % (name, b, scale)
     if isinstance(scale, torch.Tensor):
         if scale.dim() > 1 or scale.dtype == torch.bool:
-            raise ValueError("guidance_scale: a tensor must be a scalar or (%d,) of numbers, got %s %s" % (b, tuple(scale.shape), scale.dtype))
+            raise ValueError("%s: a tensor must be a scalar or (%d,) of numbers, got %s %s" % (name, b, tuple(scale.shape), scale.dtype))
         scale = scale.tolist()
     if isinstance(scale, (bool, str, bytes)) or scale is None:
         raise ValueError(bad)
@@ -717,11 +722,15 @@ def guidance_scales(scale, b, device):
         except (TypeError, ValueError):
             raise ValueError(bad) from None
     if len(host) != b:
-        raise ValueError("guidance_scale has %d entries for a batch of %d scenes" % (len(host), b))
+        raise ValueError("%s has %d entries for a batch of %d scenes" % (name, len(host), b))
     for i, v in enumerate(host):
         if v != v or v in (float("inf"), float("-inf")):
-            raise ValueError("guidance_scale: scene %d: %r is not finite" % (i, v))
-    return torch.tensor(host, dtype=torch.float32).to(device).contiguous()
+            raise ValueError("%s: scene %d: %r is not finite" % (name, i, v))
+    w = torch.tensor(host, dtype=torch.float32)
+    for i, v in enumerate(w.tolist() if weights else ()):
+        if v < 0:
+            raise ValueError("%s: scene %d: %r is negative" % (name, i, v))
+    return w.to(device).contiguous()
 
 
 def scene_seeds(value, batch_size, device):
@@ -882,23 +891,20 @@ STEER_MAX_OBJECTS = 160            # one block per scene, one thread per box (cs
 def collision_scales(scale, b, device):
     """The per-scene steering weights of dsc_steer_boxes_f32 as a contiguous (b,) f32 tensor on ``device``.  ``scale``: a float (every
     scene) or b values, as guidance_scales takes them, each finite and >= 0; 0 leaves that scene unsteered.  ValueError otherwise."""
-    try:
-        w = guidance_scales(scale, b, "cpu")
-    except ValueError as e:
-        raise ValueError(str(e).replace("guidance_scale", "collision_scale")) from None
-    for i, v in enumerate(w.tolist()):
-        if v < 0:
-            raise ValueError("collision_scale: scene %d: %r is negative" % (i, v))
-    return w.to(device).contiguous()
+    return _scene_scales(scale, b, device, "collision_scale", weights=True)
 
 
 def collision_steps(steps, num_timesteps):
     """K of dsc_steer_boxes_f32: a step at timestep t is steered iff t < K.  ``steps``: None (every step, K = num_timesteps) or an
     integer in [0, num_timesteps] -- the last K timesteps of the schedule; a strided loop steers the pairs whose t is below K."""
+    return _steered_steps(steps, num_timesteps, "collision_steps")
+
+
+def _steered_steps(steps, num_timesteps, name):
     if steps is None:
         return int(num_timesteps)
     if isinstance(steps, bool) or not isinstance(steps, numbers.Integral) or not 0 <= int(steps) <= num_timesteps:
-        raise ValueError("collision_steps must be None or an integer in [0, %d], got %r" % (num_timesteps, steps))
+        raise ValueError("%s must be None or an integer in [0, %d], got %r" % (name, num_timesteps, steps))
     return int(steps)
 
 
@@ -916,15 +922,18 @@ def steer_bounds(bounds):
     return (C.c_float * 12)(*host)
 
 
-def steer_rec(x_t, model_out, mean_type, tables, steer, t=None, clip=None, strided=None, rows=None, mask=None, q=(), scale=None,
-              x_dup=None, energy_out=None, grad_out=None):
-    """The launch record of collision steering (dsc_steer_boxes_f32): ``model_out`` (B, N, C) -- (2 B, N, C) under ``scale`` -- is
-    corrected in place between the model call and the step.  It takes the operand groups of step_rec under the same keywords, so a loop
-    hands both records the same dictionaries: the time source ``t`` or ``strided`` (its step counter and times), ``tables`` (ca, cb
-    first; the rest, ``clip``, ``q`` and ``x_dup`` belong to the step and are not read here), the given part ``rows`` = (partial, _,
-    counts) or ``mask`` = (known, _, mask), guidance ``scale``.  ``steer`` = (weight (B,) f32, t_below (1,) int64 -- both on the device,
-    read at launch --, bounds (steer_bounds), bbox_dim, class_dim).  ``x_t`` may be None for mean type x0.  ``energy_out`` (B,) /
-    ``grad_out`` (B, N, 3): the optional outputs."""
+# The parameters of the two steering entry points in the order of include/diffuscene_hip.h without the stream: the shared operands, with
+# what floor-plan steering adds where the header has it.
+_STEER_IN = "x_t model_out t step times ca cb partial counts known mask scale weight t_below bounds"
+_STEER_DIMS = "mean_type b n pmax c bbox_dim class_dim S T"
+STEER_PARAMS = (_STEER_IN + " energy_out grad_out " + _STEER_DIMS).split()
+WALLS_PARAMS = (_STEER_IN + " field room_side energy_out grad_out outside_out " + _STEER_DIMS + " field_b h w").split()
+
+
+def _steer_operands(noun, x_t, model_out, mean_type, tables, steer, t=None, clip=None, strided=None, rows=None, mask=None, q=(),
+                    scale=None, x_dup=None, energy_out=None, grad_out=None):
+    """The operands both steering records share, checked, by the names of STEER_PARAMS (a tensor or None, a host value as it is).
+    ``noun`` names the steering in the messages."""
     weight, t_below, bounds, bbox_dim, class_dim = steer
     if rows is not None and mask is not None:
         raise ValueError("diffuscene_amd: steer_boxes takes one given part, rows or mask")
@@ -946,43 +955,57 @@ def steer_rec(x_t, model_out, mean_type, tables, steer, t=None, clip=None, strid
     if tuple(weight.shape) != (b,) or t_below.numel() != 1:
         raise RuntimeError("diffuscene_amd: weight must be (%d,) f32 and t_below hold one int64" % b)
     if n > STEER_MAX_OBJECTS:
-        raise ValueError("diffuscene_amd: collision steering handles at most %d objects per scene, got %d" % (STEER_MAX_OBJECTS, n))
+        raise ValueError("diffuscene_amd: %s handles at most %d objects per scene, got %d" % (noun, STEER_MAX_OBJECTS, n))
     if bbox_dim != 8 or class_dim < 1 or bbox_dim + class_dim > c:
-        raise ValueError("diffuscene_amd: collision steering needs the layout [translation 3 | size 3 | cos, sin | classes ...], got "
-                         "bbox_dim=%d, class_dim=%d, %d channels" % (bbox_dim, class_dim, c))
-    bounds = steer_bounds(bounds)
-    ca, cb = tables[0], tables[1]
+        raise ValueError("diffuscene_amd: %s needs the layout [translation 3 | size 3 | cos, sin | classes ...], got "
+                         "bbox_dim=%d, class_dim=%d, %d channels" % (noun, bbox_dim, class_dim, c))
     # the timestep is held to the rows of the schedule tables; a model that predicts x0 indexes none here, and without any table of the
     # step at hand only a negative timestep is out of range
-    T = _table_rows(*tables) if any(tb is not None for tb in tables) else 2 ** 31 - 1
-    tp = sp = tmp = None
-    S = 0
+    v = dict.fromkeys(STEER_PARAMS)
+    v.update(x_t=x_t, model_out=model_out, ca=tables[0], cb=tables[1], scale=scale, weight=weight, t_below=t_below,
+             bounds=steer_bounds(bounds), energy_out=energy_out, grad_out=grad_out, mean_type=mean_type, b=b, n=n, pmax=0, c=c,
+             bbox_dim=bbox_dim, class_dim=class_dim, S=0, T=_table_rows(*tables) if any(tb is not None for tb in tables) else 2 ** 31 - 1)
     if strided is not None:
-        (sp, tmp, _, _, _, _), S = _strided_run(*strided)
+        (v["step"], v["times"], _, _, _, _), v["S"] = _strided_run(*strided)
     else:
         _scene_t(t, b)
-        tp = t.data_ptr()
-    partial = counts = known = mk = None
-    pmax = 0
+        v["t"] = t
     if rows is not None:
         partial, counts = _c(rows[0], "partial"), _dev(rows[2], "counts", torch.int64)
         pmax = partial.shape[1]
         if tuple(partial.shape) != (b, pmax, c) or not 1 <= pmax <= n or tuple(counts.shape) != (b,) or not counts.is_contiguous():
             raise RuntimeError("diffuscene_amd: partial must be (%d, Pmax <= %d, %d) with (%d,) counts, got %s / %s"
                                % (b, n, c, b, tuple(partial.shape), tuple(counts.shape)))
+        v.update(partial=partial, counts=counts, pmax=pmax)
     if mask is not None:
         known, mk = _c(mask[0], "known"), _dev(mask[2], "mask", torch.uint8)
         if tuple(known.shape) != shape or tuple(mk.shape) != shape or not mk.is_contiguous():
             raise RuntimeError("diffuscene_amd: known / mask must be %s, got %s / %s" % (shape, tuple(known.shape), tuple(mk.shape)))
+        v.update(known=known, mask=mk)
     if scale is not None and (tuple(_c(scale, "scale").shape) != (b,)):
         raise RuntimeError("diffuscene_amd: scale must be a (%d,) f32 tensor (ops.guidance_scales), got %s" % (b, tuple(scale.shape)))
     for o, want, name in ((energy_out, (b,), "energy_out"), (grad_out, (b, n, 3), "grad_out")):
         if o is not None and tuple(_c(o, name).shape) != want:
             raise RuntimeError("diffuscene_amd: %s must be %s, got %s" % (name, want, tuple(o.shape)))
-    args = (_opt(x_t), model_out.data_ptr(), tp, sp, tmp, _opt(ca), _opt(cb), _opt(partial), _opt(counts), _opt(known), _opt(mk),
-            _opt(scale), weight.data_ptr(), t_below.data_ptr(), bounds, _opt(energy_out), _opt(grad_out), mean_type, b, n, pmax, c,
-            bbox_dim, class_dim, S, T)
-    return "dsc_steer_boxes_f32", args, (x_t, model_out, tables, steer, bounds, t, strided, rows, mask, scale, energy_out, grad_out)
+    return v
+
+
+def _steer_record(name, params, v, keep):
+    """(entry point, its arguments laid out from ``params``, what the launch keeps alive)."""
+    args = tuple(a.data_ptr() if isinstance(a, torch.Tensor) else a for a in (v[p] for p in params))
+    return name, args, (tuple(v.values()), keep)
+
+
+def steer_rec(x_t, model_out, mean_type, tables, steer, **operands):
+    """The launch record of collision steering (dsc_steer_boxes_f32): ``model_out`` (B, N, C) -- (2 B, N, C) under ``scale`` -- is
+    corrected in place between the model call and the step.  It takes the operand groups of step_rec under the same keywords, so a loop
+    hands both records the same dictionaries: the time source ``t`` or ``strided`` (its step counter and times), ``tables`` (ca, cb
+    first; the rest, ``clip``, ``q`` and ``x_dup`` belong to the step and are not read here), the given part ``rows`` = (partial, _,
+    counts) or ``mask`` = (known, _, mask), guidance ``scale``.  ``steer`` = (weight (B,) f32, t_below (1,) int64 -- both on the device,
+    read at launch --, bounds (steer_bounds), bbox_dim, class_dim).  ``x_t`` may be None for mean type x0.  ``energy_out`` (B,) /
+    ``grad_out`` (B, N, 3): the optional outputs."""
+    v = _steer_operands("collision steering", x_t, model_out, mean_type, tables, steer, **operands)
+    return _steer_record("dsc_steer_boxes_f32", STEER_PARAMS, v, (tables, steer, operands))
 
 
 def steer_boxes(x_t, model_out, weight, t_below, bounds, mean_type, ca=None, cb=None, bbox_dim=8, class_dim=1, energy_out=None,
@@ -1013,22 +1036,14 @@ def box_repulsion(x0, bounds, bbox_dim=8, class_dim=1):
 WALL_MAX_SIDE = 256                # pixels per side of the room mask (csrc/diffusion.hip: WALL_MAXHW)
 
 
-def _renamed(fn, old, new, *args, **kw):
-    """``fn(*args, **kw)`` of collision steering with the names of another steering part in its messages."""
-    try:
-        return fn(*args, **kw)
-    except ValueError as e:
-        raise ValueError(str(e).replace(old, new)) from None
-
-
 def wall_scales(scale, b, device):
     """The per-scene weights of dsc_steer_walls_f32: collision_scales under the name ``wall_scale``."""
-    return _renamed(collision_scales, "collision_scale", "wall_scale", scale, b, device)
+    return _scene_scales(scale, b, device, "wall_scale", weights=True)
 
 
 def wall_steps(steps, num_timesteps):
     """K of dsc_steer_walls_f32: collision_steps under the name ``wall_steps``."""
-    return _renamed(collision_steps, "collision_steps", "wall_steps", steps, num_timesteps)
+    return _steered_steps(steps, num_timesteps, "wall_steps")
 
 
 def room_side_value(room_side):
@@ -1082,19 +1097,19 @@ def walls_rec(x_t, model_out, mean_type, tables, walls, energy_out=None, grad_ou
     bounds (steer_bounds), bbox_dim, class_dim, field (B or 1, H, W) f32, room_side (1,) f32) -- weight, t_below, field and room_side on
     the device, read at launch.  ``outside_out`` (B,) int32: the third optional output."""
     weight, t_below, bounds, bbox_dim, class_dim, field, room_side = walls
-    _, a, keep = _renamed(steer_rec, "collision steering", "floor-plan steering", x_t, model_out, mean_type, tables,
-                          (weight, t_below, bounds, bbox_dim, class_dim), energy_out=energy_out, grad_out=grad_out, **operands)
-    b = a[18]
+    v = _steer_operands("floor-plan steering", x_t, model_out, mean_type, tables,
+                        (weight, t_below, bounds, bbox_dim, class_dim), energy_out=energy_out, grad_out=grad_out, **operands)
+    b = v["b"]
     _c(field, "field"); _c(room_side, "room_side")
-    if field.dim() != 3 or field.shape[0] not in (1, b) or not all(2 <= int(v) <= WALL_MAX_SIDE for v in field.shape[1:]):
+    if field.dim() != 3 or field.shape[0] not in (1, b) or not all(2 <= int(d) <= WALL_MAX_SIDE for d in field.shape[1:]):
         raise RuntimeError("diffuscene_amd: field must be (%d or 1, H, W) with 2 <= H, W <= %d, got %s" % (b, WALL_MAX_SIDE, tuple(field.shape)))
     if room_side.numel() != 1:
         raise RuntimeError("diffuscene_amd: room_side must hold one f32")
     if outside_out is not None and (tuple(_dev(outside_out, "outside_out", torch.int32).shape) != (b,) or not outside_out.is_contiguous()):
         raise RuntimeError("diffuscene_amd: outside_out must be a contiguous (%d,) int32 tensor" % b)
-    fb, h, w = field.shape
-    args = a[:15] + (field.data_ptr(), room_side.data_ptr()) + a[15:17] + (_opt(outside_out),) + a[17:] + (fb, h, w)
-    return "dsc_steer_walls_f32", args, (keep, field, room_side, outside_out)
+    v.update(field=field, room_side=room_side, outside_out=outside_out)
+    v["field_b"], v["h"], v["w"] = field.shape
+    return _steer_record("dsc_steer_walls_f32", WALLS_PARAMS, v, (tables, walls, operands))
 
 
 def steer_walls(x_t, model_out, weight, t_below, bounds, field, room_side, mean_type, ca=None, cb=None, bbox_dim=8, class_dim=1,

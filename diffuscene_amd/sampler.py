@@ -553,13 +553,26 @@ class _Steer:
     on what the model call returned -- under guidance the 2 B output, with the scales, so the fused and the unfused guidance see the same
     corrected halves.  ``weight`` (B,) f32 and ``t_below`` (1,) int64 are buffers of the graph, captured by pointer and refreshed in
     place: one graph serves every per-scene weight and every number of steered steps, and a weight of 0 or a timestep at or above
-    t_below stores nothing.  ``layout`` = (bounds, bbox_dim, class_dim) is baked into the launch and part of the cache key."""
+    t_below stores nothing.  ``layout`` = (bounds, bbox_dim, class_dim) is baked into the launch and part of the cache key.
+    The base of every steering part: ``key`` and ``loaded`` split the inputs tuple of the loop (GaussianDiffusion._steer_inputs) into
+    the layout and what ``load`` takes.  A part with further buffers hands them to __init__ as ``more``, in the order of its record's
+    tuple, and extends ``key``, ``loaded``, ``load`` and ``_rec``."""
 
-    def __init__(self, g, layout):
+    def __init__(self, g, layout, more=()):
         bounds, bbox_dim, class_dim = layout
         self.weight = torch.zeros((g.shape[0],), device=g.device, dtype=torch.float32)
         self.t_below = torch.zeros((1,), device=g.device, dtype=torch.int64)
-        self.spec = (self.weight, self.t_below, ops.steer_bounds(bounds), bbox_dim, class_dim)
+        self.spec = (self.weight, self.t_below, ops.steer_bounds(bounds), bbox_dim, class_dim) + more
+
+    @staticmethod
+    def key(inputs):
+        weight, k, bounds, bbox_dim, class_dim = inputs
+        return tuple(float(v) for v in bounds), int(bbox_dim), int(class_dim)
+
+    @staticmethod
+    def loaded(inputs):
+        weight, k, bounds, bbox_dim, class_dim = inputs
+        return weight, k
 
     def load(self, weight, t_below):
         self.weight.copy_(weight)               # in place: the graph holds these pointers
@@ -567,10 +580,13 @@ class _Steer:
 
     def apply(self, g, mo):
         scale = dict(scale=g.guide.scale) if g.guide else {}
-        ops.issue(ops.steer_rec(g.x, mo, g.mean_type, steer=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
+        ops.issue(self._rec(g.x, mo, g.mean_type, **g.sched, **g.part.steer_operands(g), **scale))
+
+    def _rec(self, *args, **operands):
+        return ops.steer_rec(*args, steer=self.spec, **operands)
 
 
-class _Walls:
+class _Walls(_Steer):
     """Floor-plan steering (dsc_steer_walls_f32): one launch after collision steering (if any) and before the multistep launch, on
     the same output with the same operands as _Steer -- walls have the last word.  ``weight`` (B,) f32, ``t_below`` (1,) int64, ``field``
     (B, H, W) f32 and ``room_side`` (1,) f32 are buffers of the graph, captured by pointer and refreshed in place: one graph serves
@@ -579,22 +595,28 @@ class _Walls:
     of the cache key."""
 
     def __init__(self, g, layout):
-        bounds, bbox_dim, class_dim, h, w = layout
-        self.weight = torch.zeros((g.shape[0],), device=g.device, dtype=torch.float32)
-        self.t_below = torch.zeros((1,), device=g.device, dtype=torch.int64)
+        *steer, h, w = layout
         self.field = torch.zeros((g.shape[0], h, w), device=g.device, dtype=torch.float32)
         self.room_side = torch.ones((1,), device=g.device, dtype=torch.float32)
-        self.spec = (self.weight, self.t_below, ops.steer_bounds(bounds), bbox_dim, class_dim, self.field, self.room_side)
+        super().__init__(g, steer, (self.field, self.room_side))
+
+    @staticmethod
+    def key(inputs):
+        *steer, field, room_side = inputs
+        return _Steer.key(steer) + tuple(field.shape[1:])
+
+    @staticmethod
+    def loaded(inputs):
+        *steer, field, room_side = inputs
+        return _Steer.loaded(steer) + (field, room_side)
 
     def load(self, weight, t_below, field, room_side):
-        self.weight.copy_(weight)               # in place: the graph holds these pointers
-        self.t_below.fill_(int(t_below))
+        super().load(weight, t_below)
         self.field.copy_(field)                 # (B, H, W), or (1, H, W) broadcast
         self.room_side.fill_(float(room_side))
 
-    def apply(self, g, mo):
-        scale = dict(scale=g.guide.scale) if g.guide else {}
-        ops.issue(ops.walls_rec(g.x, mo, g.mean_type, walls=self.spec, **g.sched, **g.part.steer_operands(g), **scale))
+    def _rec(self, *args, **operands):
+        return ops.walls_rec(*args, walls=self.spec, **operands)
 
 
 class _Multistep:
@@ -920,10 +942,9 @@ def _front_end(name, cls):
             n_main, n_given = js.calls + js.jumps + (0 if cls.strided else 1), js.calls
             jump_spec = (int(jumps[2]), n_main, n_given)
             jump_key = ("resample",) + (jump_spec if isinstance(a["noise_fn"], NoiseReplay) else jump_spec[:1])
-        # steer = (weight (B,) f32 on the device, K, bounds, bbox_dim, class_dim): the first two live in buffers, the rest is the key
-        layout = None if steer is None else (tuple(float(v) for v in steer[2]), int(steer[3]), int(steer[4]))
-        # walls = (weight, K, bounds, bbox_dim, class_dim, field (B or 1, H, W) f32 on the device, room_side): the key is the layout and (H, W)
-        wall_layout = None if walls is None else (tuple(float(v) for v in walls[2]), int(walls[3]), int(walls[4])) + tuple(walls[5].shape[1:])
+        # of either inputs tuple the layout is the key and the rest lives in buffers: _Steer.key / .loaded, _Walls.key / .loaded
+        layout = None if steer is None else _Steer.key(steer)
+        wall_layout = None if walls is None else _Walls.key(walls)
         what = cls.what or (jumps is not None and "the resampled T-step loop") or None
         check = what and _replay_check((what % sched if "%" in what else what) + (" with resampling jumps" if jumps is not None and cls.what else ""), n_main,
                                            shape if cls.guided or cls.given is _Masked else None, *((n_given, gshape or shape) if given else ()))
@@ -937,8 +958,8 @@ def _front_end(name, cls):
                                            **({} if jumps is None else dict(resample=jump_spec))),
             lambda g, x_T, buf, pbuf, dtab: g.run(x_T, dtab if cls.strided else total, *([a["scale"]] if cls.guided else []), *given,
                                                   noise_buffer=_head(buf, n_main), given_noise=_head(pbuf, n_given),
-                                                  steer=None if steer is None else steer[:2], multistep=multistep,
-                                                  **({} if walls is None else dict(walls=walls[:2] + walls[5:])),
+                                                  steer=None if steer is None else _Steer.loaded(steer), multistep=multistep,
+                                                  **({} if walls is None else dict(walls=_Walls.loaded(walls))),
                                                   **({} if jumps is None else dict(jumps=jumps[:2]))),
             mult=2 if cls.guided else 1, check=check or None, ddim=(sched, a["eta"]) if cls.strided else None)
         if cls.given is _Dense and given:

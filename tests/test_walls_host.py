@@ -277,18 +277,18 @@ def test_the_eager_model_call_issues_walls_after_collision_and_before_multistep(
     walls = gd._wall_inputs(shape, "cpu", 0.05, None, 3.1, torch.ones(1, 1, 8, 8), "loop", field=False)
     post = lambda x, mo: names.append("dsc_multistep_x0_f32")  # noqa: E731
     plain = D._model(lambda x, t_, c, cc: x.clone(), None, None)
-    D._walled(D._steered(plain, gd, "cpu", steer, D._FREE), gd, "cpu", walls, D._FREE)(x, t, post)
+    D._corrected(plain, gd, "cpu", D._FREE, steer=steer, walls=walls)(x, t, post)
     assert names == ["dsc_steer_boxes_f32", "dsc_steer_walls_f32", "dsc_multistep_x0_f32"]
     del names[:]
-    D._walled(plain, gd, "cpu", walls, D._FREE)(x, t)                                # walls alone, no solver
+    D._corrected(plain, gd, "cpu", D._FREE, walls=walls)(x, t)                            # walls alone, no solver
     assert names == ["dsc_steer_walls_f32"]
     del names[:]
     scale = torch.ones(2)
     guided = D._guided_model(lambda x, t_, c, cc: x.clone(), None, None, scale)     # under guidance: on the 2 B output, before the mix
-    D._walled(guided, gd, "cpu", walls, D._FREE, scale)(x, t, post)
+    D._corrected(guided, gd, "cpu", D._FREE, scale, walls=walls)(x, t, post)
     assert names == ["dsc_steer_walls_f32", "dsc_multistep_x0_f32", "dsc_cfg_combine_f32"]
     del names[:]
-    D._steered(plain, gd, "cpu", steer, D._FREE)(x, t, post)                         # without the keyword: no such launch
+    D._corrected(plain, gd, "cpu", D._FREE, steer=steer)(x, t, post)                      # without the keyword: no such launch
     plain(x, t)
     assert names == ["dsc_steer_boxes_f32", "dsc_multistep_x0_f32"]
     assert D._wall_kw(None, None, None, torch.ones(1, 1, 8, 8)) == {}               # a room mask alone asks for nothing
