@@ -1,5 +1,6 @@
 """GPU: every C-ABI kernel against a plain fp32/fp64 torch restatement of the same reference op (oracle pieces).
-Tolerances are written per test; elementwise diffusion steps must be BIT-EXACT."""
+Tolerances are written per test; elementwise diffusion steps must be BIT-EXACT.
+The edge shapes of the forward block kernels (csrc/blocks.hip), with canaries and per-unit bounds: tests/test_gpu_blocks_kernels.py."""
 import math
 import os
 

@@ -162,13 +162,15 @@ def slabs(scenes, n):
     return lambda a: a.reshape(scenes, n, 4, 32).transpose(0, 2, 1, 3).reshape(scenes * 4, -1)
 
 
-def bounded(entry, tensor, case, got, ref64, t32, units=whole, dymax=1.0):
-    """-> (ok, line) for one output tensor under the bound of the module docstring."""
+def bounded(entry, tensor, case, got, ref64, t32, units=whole, dymax=1.0, prefix="train_bwd", caps=None, floors=None):
+    """-> (ok, line) for one output tensor under the bound of the module docstring.  (prefix, caps, floors: the log tag and the CAPS /
+    FLOORS tables of a sibling module that states the same rule; the defaults are this module's.)"""
+    caps, floors = CAPS if caps is None else caps, FLOORS if floors is None else floors
     g, r, t = (units(np.asarray(host(a) if torch.is_tensor(a) else a, np.float64)) for a in (got, ref64, t32))
     assert g.shape == r.shape == t.shape, (entry, tensor, g.shape, r.shape, t.shape)
     assert np.isfinite(g).all(), (entry, tensor, case)
-    floor = FLOORS.get((entry, tensor), FLOOR)
-    assert floor <= max(CAPS.get(entry, FLOOR), FLOOR)
+    floor = floors.get((entry, tensor), FLOOR)
+    assert floor <= max(caps.get(entry, FLOOR), FLOOR)
     scale = np.abs(r).max(1)
     zero = scale <= 1e-12 * dymax
     ok, err, e32 = True, 0.0, 0.0
@@ -178,8 +180,8 @@ def bounded(entry, tensor, case, got, ref64, t32, units=whole, dymax=1.0):
         err = (np.abs(g - r)[~zero].max(1) / scale[~zero]).max()
         e32 = (np.abs(t - r)[~zero].max(1) / scale[~zero]).max()
     bound = max(4.0 * e32, floor)
-    line = "train_bwd %s | %s | %s: err %.3g (bound %.3g, err_torch32 %.3g)%s" % (
-        entry, tensor, case, err, bound, e32, " zero units: max|got| %.3g" % np.abs(g[zero]).max() if zero.any() else "")
+    line = "%s %s | %s | %s: err %.3g (bound %.3g, err_torch32 %.3g)%s" % (
+        prefix, entry, tensor, case, err, bound, e32, " zero units: max|got| %.3g" % np.abs(g[zero]).max() if zero.any() else "")
     _log(line)
     return bool(ok and err <= bound), line
 
